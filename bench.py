@@ -2,7 +2,13 @@
 """Headline benchmark: captions/sec of one full training step (forward + backward +
 optimisers) of the CVAE captioning trainer on synthetic data resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg1]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg4|cfg2|cfg3|cfg1] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the result line, nothing more.  --full adds everything else the benchmark
+reports: the CPU baseline legs, the roofline of the dominant kernel family (HIP events live in the timed region), cfg4's strong_n1
+point, cfg1's greedy-decode leg and the data-parallel bucket waits / compute-only step.  --dump-outputs DIR writes what the last
+timed step computed as DIR/<name>.npy (training: the losses and a fixed, seeded sample of every parameter after the update;
+cfg5: the kept beams' token ids and scores), so that two builds can be compared output for output.
 
 Workloads (BASELINE.json configs):
   cfg4 (default, the configuration the metric is quoted on): Normal CVAE + --fine_tune,
@@ -48,6 +54,61 @@ def make_params(w):
     if w.get("generate"):
         p.mode, p.gen_z_samples, p.beam_size = "inference", w["z"], w["beam"]
     return p
+
+
+DUMP_SAMPLE = 1 << 16   # --dump-outputs: arrays above this many elements are written as a fixed, seeded sample of this many
+
+
+def _dump_sample(name, t):
+    """All of `t` (a torch tensor or numpy array) as a flat float32 array if it is small, else DUMP_SAMPLE elements at sorted indices
+    drawn from a generator seeded by the name alone (the same elements whatever the build); large device tensors are gathered on
+    the device, so the full array never crosses to the host."""
+    import zlib
+    n = int(np.prod(t.shape))
+    if n <= DUMP_SAMPLE:
+        idx = None
+    else:
+        idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, DUMP_SAMPLE, replace=False))
+    if isinstance(t, np.ndarray):
+        flat = t.reshape(-1)
+        return (flat if idx is None else flat[idx]).astype(np.float32)
+    import torch
+    flat = t.detach().reshape(-1)
+    if idx is not None:
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def _dump_name(name):
+    return name.replace("/", "__")
+
+
+def dump_training_outputs(d, tr, losses):
+    """What a caller of the timed training step receives after the last step: the four losses (kld, rec_loss, lower_bound,
+    annealing) as losses.npy (float64), and every trainable variable after the update (Trainer.state_dict's names; VGG16's
+    straight from the device) as param__<scope>__<name>.npy -- whole up to DUMP_SAMPLE elements, a seeded sample above."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "losses.npy"), np.array(losses, dtype=np.float64))
+    params = dict(tr.cap.state_dict())
+    if tr.vgg is not None:
+        params.update({n: tr.vgg.store.param(n) for n in tr.vgg.store.names()})
+    for name in sorted(params):
+        np.save(os.path.join(d, "param__%s.npy" % _dump_name(name)), _dump_sample(name, params[name]))
+
+
+def dump_beams(d, res, beam):
+    """cfg5: the last call's kept beams per image, descending score -- beam_ids.npy [images, beam, longest] (token ids as float32,
+    -1 past a caption's end and for beams an image did not keep) and beam_scores.npy [images, beam] (float64, NaN where no beam)."""
+    os.makedirs(d, exist_ok=True)
+    L = max([len(s) for r in res for s, _ in r] + [1])
+    ids = np.full((len(res), beam, L), -1.0, np.float32)
+    scores = np.full((len(res), beam), np.nan, np.float64)
+    for b, r in enumerate(res):
+        for k, (s, sc) in enumerate(r[:beam]):
+            ids[b, k, :len(s)] = s
+            scores[b, k] = sc
+    np.save(os.path.join(d, "beam_ids.npy"), ids)
+    np.save(os.path.join(d, "beam_scores.npy"), scores)
 
 
 def conv_flops_per_image():
@@ -188,7 +249,7 @@ def main():
                          "dominant kernels can be bracketed by HIP events inside the timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--strong-n1", type=int, default=1,
-                    help="cfg4 at N = 1 (weak): after the timed region also run the 512-image GLOBAL batch on this one GPU (3 warm-up + 10 timed "
+                    help="with --full, cfg4 at N = 1 (weak): after the timed region also run the 512-image GLOBAL batch on this one GPU (3 warm-up + 10 timed "
                          "steps, ~3 s) and report it as `strong_n1` -- SURVEY.md section 8d's single-GPU point of the strong-scaling curve")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--images-per-gpu", type=int, default=0, help="override the workload's images per GPU (sweeps; the default is BASELINE's)")
@@ -206,6 +267,13 @@ def main():
                          "(hi, lo) bf16 pairs, three bf16 MFMAs per k-step, f32 accumulate (~1e-5 relative product error) -- a separately "
                          "reported line, never the default")
     ap.add_argument("--num-captions", type=int, default=0, help="captions per image (secondary line nc = 1; default: the reference's 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run and report everything beyond the headline figure: CPU baselines (unless --no-cpu-baseline), the "
+                         "roofline from HIP events in the timed region, strong_n1 (cfg4, unless --strong-n1 0), cfg1's greedy leg, the "
+                         "data-parallel bucket waits and compute-only step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64, a seeded sample "
+                         "of large arrays; rank 0)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
@@ -249,7 +317,7 @@ def main():
     # The CPU baseline leg (rank 0, N = 1) runs FIRST: the GPU's timed region is then the last thing the process does (a driver
     # that samples GPU activity over the whole run otherwise sees mostly the numpy baseline).
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not w.get("generate"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not w.get("generate"):
         cpu_base = cpu_baseline(args.workload, w, args.seed)
     vocab = args.vocab
     p.vocab_size = vocab
@@ -273,14 +341,14 @@ def main():
         if fresh:
             tr.set_batch(fresh[i % len(fresh)])
         tr._step()
-    timer = KernelTimer(all_gemms=tr.vgg is None)   # caption-only workloads: the dominant family is every dense product of the step
+    timer = KernelTimer(all_gemms=tr.vgg is None) if args.full else None   # caption-only workloads: the dominant family is every dense product of the step
     if use_graph:
         tr.capture(warmup=0)
-    else:  # HIP-event pairs around the dominant kernel launches, live in the timed region
+    elif timer is not None:  # HIP-event pairs around the dominant kernel launches, live in the timed region
         tr.cap.timer = timer
         if tr.vgg is not None:
             tr.vgg.timer = timer
-    if world > 1:
+    if world > 1 and args.full:
         tr.dp_stats = []
     torch.cuda.synchronize()
     if world > 1:
@@ -302,6 +370,8 @@ def main():
         dt = float(t.item())
     kld, rec, lb, ann = tr.losses()
     assert np.isfinite(rec) and np.isfinite(lb), "non-finite loss"
+    if args.dump_outputs and rank == 0:   # before anything below runs another step
+        dump_training_outputs(args.dump_outputs, tr, (kld, rec, lb, ann))
     dp_info = None
     if world > 1:  # per-bucket stall of the compute stream on the gradient all-reduce (ms per step, mean over the timed steps)
         from vae_captioning_amd import dp as dpm
@@ -316,6 +386,7 @@ def main():
             for i, nbytes, e0, e1 in tr.dp_stats:
                 waits.setdefault(i, []).append(e0.elapsed_time(e1))
             dp_info["bucket_wait_ms"] = [round(float(np.mean(waits[i])), 4) for i in sorted(waits)]
+    if world > 1 and args.full:
         # exposed communication = step - compute-only step (the same step with every collective muted), max over ranks like the step time
         tr.dp_stats = None
         restore = tr.mute_collectives()
@@ -335,6 +406,46 @@ def main():
         dp_info["exposed_comm_ms"] = round(1000 * dt / args.steps - dp_info["compute_only_ms_per_step"], 3)
 
     # ---- roofline of the dominant kernel family from the HIP events of the timed region
+    roof = roofline_figures(args, tr, timer, B, use_graph) if args.full else None
+    out = {
+        "metric": "captions/sec training (224x224, seq20, vocab~10k)",
+        "value": round(N * world * args.steps / dt, 2),
+        "unit": "captions/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1000 * dt / args.steps, 3),
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f32" if args.precision == "f32" else ("bf16x3 split operands, f32 accumulate (dense products, LSTM recurrence products" + (", VGG16 weight gradients; forward / data-gradient convolutions f32 Winograd" if p.fine_tune else "") + "; element-wise work in f32)"),
+        "data": "synthetic",
+        "config": {"workload": "%s: %s" % (args.workload, json.dumps(w, sort_keys=True)), "images_per_gpu": B, "precision": args.precision,
+                   "captions_per_image": p.num_captions, "caption_rows_per_gpu": N, "global_caption_rows": N * world,
+                   "seq_len": T_LEN, "vocab": vocab, "variable_len": bool(args.variable_len), "gen_z_samples": p.gen_z_samples,
+                   "hipgraph": use_graph, "parallelism": "dp%d" % world, "rccl_world_size": dist.get_world_size() if world > 1 else 1,
+                   "inputs": ("%d host batches rotated through set_batch inside the timed region" % len(fresh)) if fresh
+                             else "one batch resident in HBM"},
+        "final_losses": {"rec_loss": round(rec, 5), "kld": round(kld, 5)},
+    }
+    if roof is not None:
+        out["roofline"] = roof
+    if dp_info:
+        out["data_parallel"] = dp_info
+    if cpu_base is not None:
+        out["cpu_baseline"] = cpu_base
+    if args.full and world == 1 and args.workload == "cfg1" and p.no_encoder:
+        out["greedy_decode"] = greedy_leg(args, lib, w, p, vocab, tr, with_cpu=(rank == 0 and not args.no_cpu_baseline))
+    if args.full and world == 1 and args.workload == "cfg4" and args.scaling == "weak" and args.strong_n1 and not args.images_per_gpu and not use_graph:
+        del tr
+        torch.cuda.empty_cache()
+        out["strong_n1"] = strong_n1_point(args, lib, w, vocab)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def roofline_figures(args, tr, timer, B, use_graph):
+    """--full: the roofline of the dominant kernel family from the HIP events of the timed region (graph replays carry none:
+    one extra eager, instrumented pass), the HBM-bound kernels, and the traffic replayed from profiles/traffic_<workload>.json."""
     instrumented_pass = False
     if use_graph:  # events cannot be recorded inside a replayed graph: one extra eager, instrumented pass
         instrumented_pass = True
@@ -363,39 +474,7 @@ def main():
             nsteps_t = max(2, args.steps // 4) if instrumented_pass else args.steps
             roof["algorithmic_bytes_per_launch"] = round(alg * nsteps_t / roof["launches"])
             roof["traffic_over_algorithmic"] = round(roof["traffic"] / roof["algorithmic_bytes_per_launch"], 3)
-    out = {
-        "metric": "captions/sec training (224x224, seq20, vocab~10k)",
-        "value": round(N * world * args.steps / dt, 2),
-        "unit": "captions/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1000 * dt / args.steps, 3),
-        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "f32" if args.precision == "f32" else ("bf16x3 split operands, f32 accumulate (dense products, LSTM recurrence products" + (", VGG16 weight gradients; forward / data-gradient convolutions f32 Winograd" if p.fine_tune else "") + "; element-wise work in f32)"),
-        "data": "synthetic",
-        "config": {"workload": "%s: %s" % (args.workload, json.dumps(w, sort_keys=True)), "images_per_gpu": B, "precision": args.precision,
-                   "captions_per_image": p.num_captions, "caption_rows_per_gpu": N, "global_caption_rows": N * world,
-                   "seq_len": T_LEN, "vocab": vocab, "variable_len": bool(args.variable_len), "gen_z_samples": p.gen_z_samples,
-                   "hipgraph": use_graph, "parallelism": "dp%d" % world, "rccl_world_size": dist.get_world_size() if world > 1 else 1,
-                   "inputs": ("%d host batches rotated through set_batch inside the timed region" % len(fresh)) if fresh
-                             else "one batch resident in HBM"},
-        "final_losses": {"rec_loss": round(rec, 5), "kld": round(kld, 5)},
-        "roofline": roof,
-    }
-    if dp_info:
-        out["data_parallel"] = dp_info
-    if cpu_base is not None:
-        out["cpu_baseline"] = cpu_base
-    if world == 1 and args.workload == "cfg1" and p.no_encoder:
-        out["greedy_decode"] = greedy_leg(args, lib, w, p, vocab, tr, with_cpu=(rank == 0 and not args.no_cpu_baseline))
-    if world == 1 and args.workload == "cfg4" and args.scaling == "weak" and args.strong_n1 and not args.images_per_gpu and not use_graph:
-        del tr
-        torch.cuda.empty_cache()
-        out["strong_n1"] = strong_n1_point(args, lib, w, vocab)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return roof
 
 
 def self_launch(n):
@@ -459,12 +538,13 @@ def bench_generation(args, torch, dist, lib, w, p, world, rank):
     cv = np.zeros((B, 90), np.float32)
     eps = rng.standard_normal((p.gen_z_samples, B, p.latent_size), dtype=np.float32)   # injected noise: the CPU leg decodes the SAME captions
     cpu_base = cpu_ids = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # first, so that the GPU's timed region is the last thing the process does
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # first, so that the GPU's timed region is the last thing the process does
         cpu_base, cpu_ids = cpu_baseline_generate("beam", p, feats.cpu().numpy(), cv, eps, beam=w["beam"], images=8)
     run = lambda: gen.beam_search(feats, cv, eps, synth.BOS, synth.EOS, beam_size=w["beam"], max_len=p.gen_max_len)
     for _ in range(args.warmup):
         run()
-    eng.timer = KernelTimer(all_gemms=True)
+    if args.full:
+        eng.timer = KernelTimer(all_gemms=True)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -479,19 +559,24 @@ def bench_generation(args, torch, dist, lib, w, p, world, rank):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    roof = roofline_from_timer(eng.timer, False)
-    roof["instrumented_pass"] = False
-    roof["note"] += ("; cfg5: decoder rounds replayed from hipGraphs carry no events -- the bracketed launches are each call's LAST round (run eagerly: "
-                     "29 rounds = 7 replayed chunks of 4 + 1) of both image slices, whose logits products [320, 512] x [512, V] share the CUs with the "
-                     "other slice's kernels (two streams), and the small products outside the rounds; every kernel's in-graph duration is in "
-                     "profiles/r06_cfg5_kernel_stats.md")
+    if args.dump_outputs and rank == 0:
+        dump_beams(args.dump_outputs, res, w["beam"])
+    roof = None
+    if args.full:
+        roof = roofline_from_timer(eng.timer, False)
+        roof["instrumented_pass"] = False
+        roof["note"] += ("; cfg5: decoder rounds replayed from hipGraphs carry no events -- the bracketed launches are each call's LAST round (run eagerly: "
+                         "29 rounds = 7 replayed chunks of 4 + 1) of both image slices, whose logits products [320, 512] x [512, V] share the CUs with the "
+                         "other slice's kernels (two streams), and the small products outside the rounds; every kernel's in-graph duration is in "
+                         "profiles/r06_cfg5_kernel_stats.md")
     out = {"metric": "captions/sec generated (beam search)", "value": round(B * world * args.steps / dt, 2), "unit": "captions/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * dt / args.steps, 3),
            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": "cfg5: %s" % json.dumps(w, sort_keys=True), "images_per_gpu": B, "beam_size": w["beam"],
                       "gen_z_samples": w["z"], "gen_max_len": p.gen_max_len, "vocab": VOCAB, "parallelism": "replicas%d" % world,
-                      "mean_caption_len": round(float(np.mean([len(r[0][0]) for r in res])), 2)},
-           "roofline": roof}
+                      "mean_caption_len": round(float(np.mean([len(r[0][0]) for r in res])), 2)}}
+    if roof is not None:
+        out["roofline"] = roof
     if cpu_base is not None:
         # (random-init weights give near-uniform word distributions: a beam may legitimately differ where fp32 and the oracle's
         # arithmetic order disagree in the last bit; the parity tests use peaked weights -- this is a report, not a gate)

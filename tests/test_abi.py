@@ -200,3 +200,39 @@ def test_bench_without_a_launcher_starts_its_own_ranks(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert not seen and "--gpus 4 but WORLD_SIZE=2" in str(e.value.code)
+
+
+def test_bench_dump_outputs_sample_is_fixed_by_the_name():
+    """bench.py --dump-outputs: an array up to DUMP_SAMPLE elements is written whole; above that, the same DUMP_SAMPLE elements (sorted
+    indices from a generator seeded by the variable's name alone) whether the array is a host array or a tensor, so that two builds'
+    dumps line up element for element."""
+    import numpy as np
+    import torch
+    import bench
+    small = np.arange(12, dtype=np.float32).reshape(3, 4)
+    np.testing.assert_array_equal(bench._dump_sample("a/b", small), small.reshape(-1))
+    big = np.arange(3 * (bench.DUMP_SAMPLE + 7), dtype=np.float32).reshape(-1, 3)   # distinct values (exact in float32)
+    s1 = bench._dump_sample("cnn/fc1/weights", big)
+    assert s1.dtype == np.float32 and s1.shape == (bench.DUMP_SAMPLE,)
+    np.testing.assert_array_equal(s1, bench._dump_sample("cnn/fc1/weights", big.copy()))
+    np.testing.assert_array_equal(s1, bench._dump_sample("cnn/fc1/weights", torch.from_numpy(big)))
+    assert not np.array_equal(s1, bench._dump_sample("cnn/fc2/weights", big))
+    assert len(np.unique(s1)) == bench.DUMP_SAMPLE and (np.diff(s1) > 0).all()   # distinct elements in array order
+    assert bench._dump_name("decoder/rnn_logits/kernel") == "decoder__rnn_logits__kernel"
+
+
+def test_bench_dump_outputs_of_beam_search(tmp_path):
+    """cfg5's dump: per image the kept beams in the order beam_search returns them, token ids padded with -1, scores NaN where an
+    image kept fewer beams than the beam width."""
+    import numpy as np
+    import bench
+    res = [[([1, 5, 6, 2], -1.5), ([1, 7, 2], -2.0)], [([1, 9, 9, 9, 2], -0.25)]]
+    bench.dump_beams(str(tmp_path), res, 3)
+    ids, sc = np.load(tmp_path / "beam_ids.npy"), np.load(tmp_path / "beam_scores.npy")
+    assert ids.dtype == np.float32 and ids.shape == (2, 3, 5) and sc.dtype == np.float64 and sc.shape == (2, 3)
+    np.testing.assert_array_equal(ids[0, 0], [1, 5, 6, 2, -1])
+    np.testing.assert_array_equal(ids[0, 1], [1, 7, 2, -1, -1])
+    np.testing.assert_array_equal(ids[0, 2], [-1] * 5)
+    np.testing.assert_array_equal(ids[1, 0], [1, 9, 9, 9, 2])
+    np.testing.assert_array_equal(sc[0, :2], [-1.5, -2.0])
+    assert np.isnan(sc[0, 2]) and np.isnan(sc[1, 1:]).all() and sc[1, 0] == -0.25

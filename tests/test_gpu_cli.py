@@ -267,7 +267,7 @@ def test_bench_two_ranks_through_torchrun_on_one_gpu(tmp_path):
     env = dict(os.environ, PYTHONPATH=ROOT, VC_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--workload", "cfg1", "--no-cpu-baseline"]
+           "--workload", "cfg1", "--no-cpu-baseline", "--full"]   # (--full: the roofline and the data-parallel waits asserted below)
     r = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -318,6 +318,35 @@ def test_bench_gpus_2_without_a_launcher(tmp_path):
     # a launcher whose world size disagrees with --gpus is an error message, not a traceback
     r = subprocess.run(cmd, cwd=tmp_path, env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=1" in r.stderr
+
+
+@pytest.mark.parametrize("workload", ["cfg1", "cfg5"])
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_ones_outputs(tmp_path, workload):
+    """A plain `bench.py --gpus 1` run is the headline alone: the result line carries metric / value / unit / higher_is_better / dtype /
+    ms_per_step for exactly --steps timed steps, and none of what --full adds (roofline, CPU baseline, greedy leg).  --dump-outputs DIR
+    writes what the last timed step computed: the training step's losses (the line's final_losses) and its parameters; cfg5's beams."""
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", workload,
+           "--dump-outputs", str(d)]
+    r = subprocess.run(cmd, cwd=tmp_path, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "captions/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"]
+    assert not {"roofline", "cpu_baseline", "greedy_decode", "strong_n1"} & set(line)
+    files = sorted(os.listdir(d))
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    arrays = {f[:-4]: np.load(d / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).any() for a in arrays.values())
+    if workload == "cfg5":
+        assert set(arrays) == {"beam_ids", "beam_scores"} and arrays["beam_ids"].shape[:2] == (128, 5)
+        assert (arrays["beam_ids"][:, 0, 0] == synth.BOS).all()
+    else:
+        kld, rec = arrays["losses"][:2]
+        assert abs(rec - line["final_losses"]["rec_loss"]) < 1e-4 and abs(kld - line["final_losses"]["kld"]) < 1e-4
+        assert "param__decoder__rnn_logits__kernel" in arrays and np.isfinite(arrays["param__decoder__rnn_logits__kernel"]).all()
 
 
 def test_gen_caption_cli_single_image(tmp_path, lib):

@@ -51,7 +51,7 @@ def test_bench_on_two_gpus_reports_an_rccl_world_of_two(workload):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--workload", workload,
-                        "--no-cpu-baseline", "--strong-n1", "0"], env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
+                        "--no-cpu-baseline", "--strong-n1", "0", "--full"], env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0

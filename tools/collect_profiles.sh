@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 # 1. the driver's command (headline line incl. the CPU baseline leg)
-python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 # 2. kernel traces of the same command (cfg4) and of cfg2: per-kernel table + per-family sum / union of dispatch intervals; cfg4 also
 #    with ONE VGG stream (VC_VGG_STREAMS=1: nothing overlaps, the per-kernel durations are the kernels' own)
 for WL in cfg4 cfg2 cfg3 cfg5; do   # (round 6: cfg3 and cfg5 too -- every BASELINE config's bench line follows from a tracked table)
@@ -30,23 +30,23 @@ done
 python tools/pmc_summary.py /tmp/pmc $OUT/${TAG}_traffic_cfg4.json > $OUT/${TAG}_cfg4_pmc.md
 # 4. comparison points: the NHWC implicit-GEMM kernels behind layout conversions (VC_CONV_WINO=0: the checker / fallback path), one stream,
 #    F(2x2,3x3) on the 56-wide layers (the round-3 preference rule)
-VC_CONV_WINO=0 python bench.py --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_nowino.json 2>/dev/null
-VC_WINO4_MIN_COVERAGE=0.85 python bench.py --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_conv3_f23.json 2>/dev/null
-VC_VGG_STREAMS=1 python bench.py --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_1stream.json 2>/dev/null
+VC_CONV_WINO=0 python bench.py --full --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_nowino.json 2>/dev/null
+VC_WINO4_MIN_COVERAGE=0.85 python bench.py --full --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_conv3_f23.json 2>/dev/null
+VC_VGG_STREAMS=1 python bench.py --full --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_1stream.json 2>/dev/null
 # 5. the step a user runs: fresh host batches through set_batch inside the timed region
-python bench.py --no-cpu-baseline --strong-n1 0 --fresh-batch 4 > $OUT/${TAG}_bench_fresh_cfg4.json 2>/dev/null
-python bench.py --no-cpu-baseline --workload cfg2 > $OUT/${TAG}_bench_cfg2.json 2>/dev/null
-python bench.py --no-cpu-baseline --workload cfg2 --fresh-batch 4 > $OUT/${TAG}_bench_fresh_cfg2.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --strong-n1 0 --fresh-batch 4 > $OUT/${TAG}_bench_fresh_cfg4.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --workload cfg2 > $OUT/${TAG}_bench_cfg2.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --workload cfg2 --fresh-batch 4 > $OUT/${TAG}_bench_fresh_cfg2.json 2>/dev/null
 # 6. secondary lines: V = 11313, variable lengths, one caption per image; the other workloads
-python bench.py --no-cpu-baseline --workload cfg2 --vocab 11313 > $OUT/${TAG}_bench_cfg2_v11313.json 2>/dev/null
-python bench.py --no-cpu-baseline --workload cfg2 --variable-len > $OUT/${TAG}_bench_cfg2_varlen.json 2>/dev/null
-python bench.py --no-cpu-baseline --workload cfg2 --num-captions 1 > $OUT/${TAG}_bench_cfg2_nc1.json 2>/dev/null
-python bench.py --workload cfg1 --graph 1 > $OUT/${TAG}_bench_cfg1.json 2>/dev/null      # (with its CPU-baseline legs: training step + greedy decode of 32 images)
-python bench.py --no-cpu-baseline --workload cfg3 > $OUT/${TAG}_bench_cfg3.json 2>/dev/null
-python bench.py --workload cfg5 --steps 30 --warmup 4 > $OUT/${TAG}_bench_cfg5.json 2>/dev/null   # (with the beam-search CPU-baseline leg, 8 images)
+python bench.py --full --no-cpu-baseline --workload cfg2 --vocab 11313 > $OUT/${TAG}_bench_cfg2_v11313.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --workload cfg2 --variable-len > $OUT/${TAG}_bench_cfg2_varlen.json 2>/dev/null
+python bench.py --full --no-cpu-baseline --workload cfg2 --num-captions 1 > $OUT/${TAG}_bench_cfg2_nc1.json 2>/dev/null
+python bench.py --full --workload cfg1 --graph 1 > $OUT/${TAG}_bench_cfg1.json 2>/dev/null      # (with its CPU-baseline legs: training step + greedy decode of 32 images)
+python bench.py --full --no-cpu-baseline --workload cfg3 > $OUT/${TAG}_bench_cfg3.json 2>/dev/null
+python bench.py --full --workload cfg5 --steps 30 --warmup 4 > $OUT/${TAG}_bench_cfg5.json 2>/dev/null   # (with the beam-search CPU-baseline leg, 8 images)
 # 6b. the split-bf16 (bf16x3) mode: every dense product on the bf16 matrix pipe, reported BESIDE the f32 lines above (never instead of them)
-for WL in cfg2 cfg3 cfg1; do python bench.py --no-cpu-baseline --workload $WL --precision bf16x3 > $OUT/${TAG}_bench_${WL}_bf16x3.json 2>/dev/null; done
-python bench.py --no-cpu-baseline --strong-n1 0 --precision bf16x3 > $OUT/${TAG}_bench_cfg4_bf16x3.json 2>/dev/null
+for WL in cfg2 cfg3 cfg1; do python bench.py --full --no-cpu-baseline --workload $WL --precision bf16x3 > $OUT/${TAG}_bench_${WL}_bf16x3.json 2>/dev/null; done
+python bench.py --full --no-cpu-baseline --strong-n1 0 --precision bf16x3 > $OUT/${TAG}_bench_cfg4_bf16x3.json 2>/dev/null
 rm -rf /tmp/kt_bx
 (cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/kt_bx -- python $ROOT/bench.py --workload cfg2 --precision bf16x3 --no-cpu-baseline > $OUT/${TAG}_cfg2_bf16x3_kt.log 2>&1)
 python tools/rocpd_stats.py "$(find /tmp/kt_bx -name "*_results.db" | head -1)" 40 > $OUT/${TAG}_cfg2_bf16x3_kernel_stats.md
@@ -75,8 +75,8 @@ python tools/microbench.py winoab winow 2>/dev/null | grep -v amdgpu.ids > $OUT/
 (echo "== python tools/microbench.py lstm (VC_LSTM_MODES=3,1)"; python tools/microbench.py lstm 2>&1 | grep "^lstm") > $OUT/${TAG}_lstm_steps.txt
 # 7b. round 6: F(4x4,3x3) on a once-transformed input (MODE 2, vc_conv3x3_wino4v_*) against the fused kernel per layer, and inside the step
 (for b in 32 64; do python tools/experiments/wino4v_try.py $b 2>&1 | grep "^conv\|^sum"; done) > $OUT/${TAG}_wino4v_layers_rerun.txt
-for v in 1 0; do VC_WINO4V=$v python bench.py --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_wino4v$v.json 2>/dev/null; done
-VC_DECODE_GRAPH=0 python bench.py --no-cpu-baseline --workload cfg5 --steps 30 --warmup 4 > $OUT/${TAG}_bench_cfg5_eager.json 2>/dev/null
+for v in 1 0; do VC_WINO4V=$v python bench.py --full --no-cpu-baseline --strong-n1 0 > $OUT/${TAG}_bench_wino4v$v.json 2>/dev/null; done
+VC_DECODE_GRAPH=0 python bench.py --full --no-cpu-baseline --workload cfg5 --steps 30 --warmup 4 > $OUT/${TAG}_bench_cfg5_eager.json 2>/dev/null
 # 8. SQ counters of the Winograd forward / data-gradient kernel per layer shape (fused and MODE 2)
 bash tools/sq_probe_wino.sh ${TAG} > /dev/null 2>&1
 # 9. round 6: counters of the AG heads GEMM (cfg3) and of one decode round's logits GEMM (cfg5)
