@@ -4,7 +4,7 @@
 
     python gen_caption.py --img_path cat.jpg --checkpoint ./checkpoints/last_run.ckpt \\
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
-        [--gen_method greedy|beam_search|sample] [--beam_size 2] [--vgg_weights ./utils/vgg16_weights.npz]
+        [--gen_method greedy|beam_search|sample|diverse] [--beam_size 2] [--diverse_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
 VGG16 fc2 features [1, 4096], imf_emb -> decoder (prior z) -> greedy / beam search, print the caption.
@@ -116,8 +116,9 @@ class Generator(object):
         fc2 = self._vgg.forward(torch.from_numpy(x).cuda())
         return fc2.cpu().numpy(), img
 
-    def generate_caption(self, img_path, beam_size=2):
-        """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130)."""
+    def generate_caption(self, img_path, beam_size=2, diverse_draws=None):
+        """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
+        "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first."""
         from vae_captioning_amd.vae_model.decoder import Decoder
         if not img_path or not os.path.exists(img_path):
             raise ValueError("Image not found")
@@ -131,7 +132,9 @@ class Generator(object):
         if self.gen_method in ("greedy", "sample"):
             sent, _ = decoder.online_inference(None, im_id, feature_vector, None, c_v=c_v)
             return sent
-        raise ValueError("gen_method must be greedy, beam_search or sample")
+        if self.gen_method == "diverse":
+            return decoder.diverse_inference(None, im_id, feature_vector, None, c_v, draws=diverse_draws)
+        raise ValueError("gen_method must be greedy, beam_search, sample or diverse")
 
 
 if __name__ == "__main__":
@@ -141,14 +144,19 @@ if __name__ == "__main__":
     parser.add_argument("--vocab_path", default="./pickles/capt_vocab.pickle", help="Indices to words dictionary")
     parser.add_argument("--gpu", default="", help="Specify GPU number if use GPU")
     parser.add_argument("--c_v_generator", default=None, help="If use cluster vectors, specify tensorflow api model (unused, as in the reference)")
-    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search or sample")
+    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample or diverse")
     parser.add_argument("--params_path", default=None, help="specify params pickle file")
     parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size")
     parser.add_argument("--vgg_weights", default=None, help="vgg16_weights.npz for the feature extractor (additive flag)")
+    parser.add_argument("--diverse_draws", type=int, default=None, help="--gen_method diverse: latent draws (default: the params' diverse_draws)")
     args = parser.parse_args()
     if args.gpu != "":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
                           gen_method=args.gen_method, vgg_weights=args.vgg_weights)
-    caption = generator.generate_caption(args.img_path, args.beam_size)
-    print(caption[0]["caption"])
+    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws)
+    if args.gen_method == "diverse":
+        for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
+            print("%.4f x%d %s" % (score, count, text))
+    else:
+        print(caption[0]["caption"])

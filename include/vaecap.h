@@ -31,6 +31,8 @@ extern "C" {
  *      direct split-bf16 forward / data-gradient convolutions (vc_conv3x3_bx_* except the weight gradient, vc_conv3x3_bx2_*), which no
  *      product path called.  New: the F(4x4,3x3) convolution with a pre-transformed input (vc_conv3x3_wino4v_*), the decode-round
  *      entries vc_softmax_topk_rows_f32 / vc_beam_gather_f32 / vc_eos_track_i32 / vc_beam_init.
+ *      Added within 4 (additive, no layout change): the diverse-captioning entries vc_diverse_latent_f32 / vc_decode_pick_f32 /
+ *      vc_decode_round_end_i32 / vc_diverse_rank.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -467,6 +469,29 @@ int vc_beam_gather_f32(void* stream, const float* c, const float* h, const int32
 /* Stop-word bookkeeping of greedy / sampled decoding (vae_model/decoder.py:186-194), on device: done[b] |= (tok[b] == eos);
  * pending[0] = number of rows that have not emitted eos yet (a float, like the other device scalars). */
 int vc_eos_track_i32(void* stream, const int32_t* tok, int B, int eos, int32_t* done, float* pending);
+
+/* ------------------------------------------------------------------------------------
+ * Diverse captioning (the AG-CVAE paper's use of z: K latent draws per image, each decoded, the candidates of an image merged by token
+ * sequence and ranked).  Candidate rows are image-major: row r = b*K + k is draw k of image b.
+ *   diverse_latent   z[r, s, l] = pm[r / K, l] + std * eps[r, s, l]  ([rows, S, L]; pm [rows / K, L] or NULL = zeros).  eps NULL: the
+ *                    N(0,1) draws come from Philox, bit-identical to vc_philox_normal_f32(out, rows*S*L, seed, offset, step).
+ *   decode_pick      one decoder round per row from one read of logits [rows, V] (ld): tok[r] = argmax (u NULL; first maximum, as
+ *                    vc_argmax_rows_f32) or the inverse-CDF draw at `temperature` with u[round[0] * rows + r] (vc_multinomial_rows_f32's
+ *                    partition and expressions: the same token); round NULL = 0, clamped to u_rounds - 1.  For rows with done[r] == 0 the
+ *                    token is appended to seq [rows, Lmax] at len[r] (< Lmax), logprob[r] += its log-softmax at temperature 1 (f32 term,
+ *                    f64 sum), len[r] += 1, and done[r] = (tok == eos).
+ *   decode_round_end pending[0] = rows with done == 0 (float); round[0] += 1 when round is not NULL.  One workgroup.
+ *   diverse_rank     per image (one workgroup, K <= 256, rows == B*K): score = logprob / (1 + len)^len_norm_f; candidates with equal token
+ *                    sequences merged (best score kept, ties: lower draw); ranked <EOS>-ended first, then score descending, then lower
+ *                    draw.  Writes n_distinct [B] and, per image, rep (draw index) / count / score [B, K] in rank order (slots past
+ *                    n_distinct: rep -1, count 0, score 0). */
+int vc_diverse_latent_f32(void* stream, long rows, int K, int S, int L, const float* pm, float std_, const float* eps, uint64_t seed,
+                          uint64_t offset, const int32_t* step, float* z);
+int vc_decode_pick_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, const float* u, int u_rounds,
+                       const int32_t* round, int eos, int32_t* tok, int32_t* done, int32_t* seq, int Lmax, int32_t* len, double* logprob);
+int vc_decode_round_end_i32(void* stream, const int32_t* done, long rows, float* pending, int32_t* round);
+int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32_t* seq, const int32_t* len, const int32_t* ended,
+                    const double* logprob, double len_norm_f, int32_t* n_distinct, int32_t* rep, int32_t* count, double* score);
 
 /* ------------------------------------------------------------------------------------
  * Host-side helper (the only entry point that takes HOST pointers): CRC-32C (Castagnoli) of a byte

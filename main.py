@@ -225,7 +225,11 @@ def main(params):
             ids = ["synthetic_%06d" % (it * params.batch_size + i) for i in range(params.batch_size)]
             pics = b["images"] if params.fine_tune else b["features"]
             c_v = b.get("c_v")
-            if params.sample_gen == "beam_search":
+            if params.sample_gen == "diverse":   # every distinct caption of every image, best first
+                sent = decoder.diverse_inference(None, ids, pics, None, c_v)
+                for r in sent:
+                    say("%s: %s" % (r["image_id"], " | ".join("%s (x%d)" % (t, n) for t, n in zip(r["captions"], r["counts"]))))
+            elif params.sample_gen == "beam_search":
                 sent = decoder.beam_search(None, ids, pics, None, c_v, beam_size=params.beam_size)
             else:
                 sent, _ = decoder.online_inference(None, ids, pics, None, c_v=c_v)

@@ -82,6 +82,39 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
     return t;
 }
 
+// ---- Philox4x32-10 (Salmon et al. 2011), counter = (quad index lo, hi, offset lo, hi) -----
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&o)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// the four N(0,1) floats of one Philox quad (Box-Muller); shared by vc_philox_normal_f32 and vc_diverse_latent_f32, whose draws agree
+// bit for bit
+__device__ __forceinline__ void box_muller4(const uint32_t (&r)[4], float (&f)[4]) {
+    const float u1 = ((float)r[0] + 1.0f) * 2.3283064365386963e-10f;  // (0,1]
+    const float u2 = (float)r[1] * 2.3283064365386963e-10f;
+    const float u3 = ((float)r[2] + 1.0f) * 2.3283064365386963e-10f;
+    const float u4 = (float)r[3] * 2.3283064365386963e-10f;
+    const float ra = sqrtf(-2.f * __logf(u1)), rb = sqrtf(-2.f * __logf(u3));
+    float s, c;
+    __sincosf(6.283185307179586f * u2, &s, &c);
+    f[0] = ra * c; f[1] = ra * s;
+    __sincosf(6.283185307179586f * u4, &s, &c);
+    f[2] = rb * c; f[3] = rb * s;
+}
+
 // gemm.hip: split-K partial products for consumers that reduce them in their own kernel (lstm.hip)
 int gemm_partials_f32(hipStream_t st, int ta, int tb, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
                       float* ws, size_t ws_bytes, int max_splits, int* splits_out);

@@ -151,24 +151,6 @@ __global__ __launch_bounds__(256) void momentum_kernel(float* __restrict__ p, co
     }
 }
 
-// ---- Philox4x32-10 (Salmon et al. 2011), counter = (quad index lo, hi, offset lo, hi) -----
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
 // mode 0: raw uint32; 1: N(0,1) via Box-Muller; 2: Bernoulli(keep) as 0/1 floats; 3: uniform [0,1)
 // `step` (nullable, device): added to the high KEY word so that a captured graph draws a fresh
 // stream every replay without any host-side argument change.  (Counter words stay (element quad,
@@ -183,16 +165,7 @@ __global__ __launch_bounds__(256) void philox_kernel(void* __restrict__ out, lon
         philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed, k1, r);
         float f[4];
         if (mode == 1) {
-            const float u1 = ((float)r[0] + 1.0f) * 2.3283064365386963e-10f;  // (0,1]
-            const float u2 = (float)r[1] * 2.3283064365386963e-10f;
-            const float u3 = ((float)r[2] + 1.0f) * 2.3283064365386963e-10f;
-            const float u4 = (float)r[3] * 2.3283064365386963e-10f;
-            const float ra = sqrtf(-2.f * __logf(u1)), rb = sqrtf(-2.f * __logf(u3));
-            float s, c;
-            __sincosf(6.283185307179586f * u2, &s, &c);
-            f[0] = ra * c; f[1] = ra * s;
-            __sincosf(6.283185307179586f * u4, &s, &c);
-            f[2] = rb * c; f[3] = rb * s;
+            box_muller4(r, f);
         } else if (mode == 2) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) f[j] = ((float)r[j] * 2.3283064365386963e-10f < keep) ? 1.f : 0.f;

@@ -68,6 +68,44 @@ def beams_from_host(ints, dbls, io, B, n, L, last):
     return res
 
 
+DIVERSE_MAX_DRAWS = 256   # vc_diverse_rank: one workgroup of 256 lanes per image, one lane per draw
+
+
+def diverse_fields(B, K, L):
+    """(name, size) of the int32 result buffer of a diverse-captioning pass over B images x K draws, candidates of <= L tokens, in
+    buffer order (rows r = b*K + k).  The float64 buffer holds score [B, K] (rank order) then logprob [B*K] (row order)."""
+    M = B * K
+    return [("n_distinct", B), ("rep", M), ("count", M), ("ended", M), ("len", M), ("seq", M * L)]
+
+
+def diverse_from_host(ints, dbls, io, B, K, L, n_best=None, candidates=False):
+    """Per image the ranked distinct captions [(tokens, score, count), ...] of a pass from its result buffers (host copies).
+    ints: the int32 fields of diverse_fields at the offsets `io`: n_distinct [B]; rep / count [B, K] in rank order (rep = the draw whose
+    tokens represent the entry); ended / len [B*K] and seq [B*K, L] per candidate row.  dbls: score [B, K] in rank order, then logprob
+    [B*K] per row.  n_best: keep the first n_best entries of each image (None: all).  candidates=True also returns per image the K
+    candidates (tokens, logprob, ended) in draw order."""
+    M = B * K
+    small = ints[:io["seq"]].tolist()
+    nd = small[io["n_distinct"]:io["n_distinct"] + B]
+    rep, cnt = small[io["rep"]:io["rep"] + M], small[io["count"]:io["count"] + M]
+    ln, en = small[io["len"]:io["len"] + M], small[io["ended"]:io["ended"] + M]
+    seq = ints[io["seq"]:io["seq"] + M * L].tolist()
+    sc = dbls[:M].tolist()
+    res = []
+    for b in range(B):
+        n = nd[b] if n_best is None else min(nd[b], int(n_best))
+        out = []
+        for j in range(n):
+            r = b * K + rep[b * K + j]
+            out.append((seq[r * L:r * L + ln[r]], sc[b * K + j], cnt[b * K + j]))
+        res.append(out)
+    if not candidates:
+        return res
+    lp = dbls[M:2 * M].tolist()
+    cands = [[(seq[r * L:r * L + ln[r]], lp[r], bool(en[r])) for r in range(b * K, (b + 1) * K)] for b in range(B)]
+    return res, cands
+
+
 class CaptionGenerator(object):
     def __init__(self, engine):
         self.e = engine
@@ -82,6 +120,8 @@ class CaptionGenerator(object):
         self._xproj_version = None
         self._side = []          # extra streams of a sliced beam search
         self.slices, self.slice_rows = 2, 256   # beam search: images decoded as `slices` independent slices when each has >= slice_rows rows
+        self.diverse_rows = 4096  # diverse captioning: candidate rows (images x draws) per pass
+        self.last_candidates = None   # diverse(): per image the K candidates (tokens, logprob, ended) of the last call, in draw order
 
     def _b(self, name, shape, dtype=torch.float32):
         t = self.buf.get(name)
@@ -384,6 +424,182 @@ class CaptionGenerator(object):
             if check_every and steps % check_every == 0 and bool((ids[:steps] == eos).any(0).all().item()):
                 break
         return self._trim(ids[:steps], eos)
+
+    # ------------------------------------------------------------------ diverse captioning (K latent draws per image)
+    def _diverse_init(self, features, c_v, eps, K):
+        """The decoder state of B images x K latent draws ([B*K, H], rows b*K + k), as init_state(features[b:b+1], c_v[b:b+1],
+        eps[k][:, None]) would give it: imf_emb, cv_emb and the LSTM steps before the z step run on the B image rows; their state is
+        tiled to B*K rows and only the draws (vc_diverse_latent_f32: no [rows*S, L] mean / std tensors), the z_rnn product and the z
+        step run on B*K rows.  eps: [K, S, B, L] or None (Philox on device).  One hipGraph from the second call of a shape on."""
+        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        B = int(features.shape[0])
+        M = B * K
+        E, Hd, L, Sm, F = p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples, p.cnn_feature_size
+        n_pre = e.n_init_d - int(e.enc)   # steps that depend on the image only
+        tag = "dvi%d_%d_" % (B, K)
+        feats = self._b(tag + "feats", (B, F))
+        self._load(feats, features)
+        X = self._b(tag + "X", (n_pre, B, E))
+        cv = epsd = z = Xz = pmd = act1 = None
+        if e.feed_cv:
+            cv = self._b(tag + "cv", (B, K_CL))
+            self._load(cv, c_v)
+        if e.enc:
+            z, Xz = self._b(tag + "z", (M, Sm, L)), self._b(tag + "Xz", (1, M, E))
+            if eps is not None:
+                epsd = self._b(tag + "eps", (M, Sm, L))
+                self._load(epsd, np.transpose(np.asarray(eps, np.float32), (2, 0, 1, 3)))   # [K, S, B, L] -> rows b*K + k
+            pm = self.prior_mean(np.asarray(c_v) if c_v is not None else None)
+            if pm is not None:
+                pmd = self._b(tag + "pm", (B, L))
+                self._load(pmd, pm)
+            act1 = self._b(tag + "act1", (1, M, 4 * Hd))
+        act0, cs0, hs0 = self._b(tag + "act0", (n_pre, B, 4 * Hd)), self._b(tag + "cs0", (n_pre + 1, B, Hd)), self._b(tag + "hs0", (n_pre + 1, B, Hd))
+        cs1, hs1 = self._b(tag + "cs1", (2, M, Hd)), self._b(tag + "hs1", (2, M, Hd))
+        lens = self.buf.get(tag + "lens")
+        if lens is None:
+            lens = self.buf[tag + "lens"] = torch.full((B,), n_pre, dtype=torch.int32, device=e.dev)
+        ones = self._ones_for(M)
+        e._need_ws(lib.vc_lstm_seq_workspace_bytes(n_pre, B, E, Hd))
+        e._need_ws(lib.vc_lstm_seq_workspace_bytes(1, M, E, Hd))
+        for sh in ((B, E, F), (B, E, K_CL), (M, E, Sm * L)):
+            e._need_ws(lib.vc_gemm_workspace_bytes(*sh))
+        W, bias = S.param(spec.DEC_CELL + "kernel"), S.param(spec.DEC_CELL + "bias")
+
+        def launches(timed):
+            st, tg = _stream(), ("gemm" if timed else None)
+            e.gemm(0, 0, B, E, F, feats, F, S.param("imf_emb/kernel"), E, X[0], E, S.param("imf_emb/bias"), tag=tg)
+            if e.feed_cv:
+                e.gemm(0, 0, B, E, K_CL, cv, K_CL, S.param("cv_emb/kernel"), E, X[1], E, S.param("cv_emb/bias"), tag=tg)
+            lib.vc_fill_f32(st, P(cs0[0]), B * Hd, 0.0)
+            lib.vc_fill_f32(st, P(hs0[0]), B * Hd, 0.0)
+            lib.vc_lstm_seq_fwd_f32(st, n_pre, B, E, Hd, P(X), P(W), P(bias), P(lens), P(act0), P(cs0), P(hs0), P(e.ws), e.ws_bytes, e.lstm_flags)
+            dst = (cs1[0], hs1[0]) if e.enc else (cs1[1], hs1[1])
+            lib.vc_tile_rows_f32(st, P(cs0[n_pre]), B, K, Hd, P(dst[0]))
+            lib.vc_tile_rows_f32(st, P(hs0[n_pre]), B, K, Hd, P(dst[1]))
+            if e.enc:   # decoder.py:72-74 and 111, per draw
+                lib.vc_diverse_latent_f32(st, M, K, Sm, L, P(pmd) if pmd is not None else None, float(p.std), P(epsd) if epsd is not None else None,
+                                          e.seed * 1000003 + 17, 6 << 32, P(e.step), P(z))
+                e.gemm(0, 0, M, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, Xz[0], E, S.param("decoder/net/z_rnn/bias"), tag=tg)
+                lib.vc_lstm_seq_fwd_f32(st, 1, M, E, Hd, P(Xz), P(W), P(bias), P(ones), P(act1), P(cs1), P(hs1), P(e.ws), e.ws_bytes, e.lstm_flags)
+
+        key = self._graph_key("dvinit", B, K, eps is None, pmd is not None, float(p.std), e.lstm_flags, e.seed,
+                              tensors=[feats, X, cv, epsd, z, Xz, pmd, act0, act1, cs0, hs0, cs1, hs1, lens, ones])
+        graph = self._graphs.get(key)
+        if graph is not None:
+            graph.replay()
+        else:
+            launches(True)
+            self._capture(key, lambda: launches(False))   # (a capture executes nothing: the eager launches above are this call's)
+        return cs1[1], hs1[1]
+
+    def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every):
+        """One pass of diverse(): the B*K candidate rows of B images decoded together, ranked per image on device (vc_diverse_rank),
+        results in two flat buffers brought back by two copies into pinned memory."""
+        lib, e, p = self.lib, self.e, self.p
+        c0, h0 = self._diverse_init(features, c_v, eps, K)
+        M, V = int(c0.shape[0]), e.V
+        B = M // K
+        i32 = torch.int32
+        tag = "dv%d_%d_%d_" % (B, K, max_len)
+        fields = diverse_fields(B, K, max_len)
+        ibuf, dbuf = self._b(tag + "ibuf", (sum(n for _, n in fields),), i32), self._b(tag + "dbuf", (2 * M,), torch.float64)
+        io, o = {}, 0
+        for name, n in fields:
+            io[name] = o
+            o += n
+        f = {name: ibuf[io[name]:io[name] + n] for name, n in fields}
+        score, logprob = dbuf[:M], dbuf[M:]
+        tok, rnd, pending = self._b(tag + "tok", (M,), i32), self._b(tag + "round", (1,), i32), self._b(tag + "pending", (1,))
+        A, Bb = self._round_bufs(tag + "A_", M), self._round_bufs(tag + "B_", M)
+        ud = None
+        if method == "sample":
+            ud = self._b(tag + "u", (max_len, M))
+            if uniforms is not None:
+                self._load(ud, np.transpose(np.asarray(uniforms, np.float32), (1, 2, 0)))   # [K, T, B] -> [T, rows b*K + k]
+            else:
+                lib.vc_philox_uniform_f32(_stream(), P(ud), ud.numel(), e.seed * 1000003 + 29, 7 << 32, P(e.step))
+        temp = float(p.temperature) if method == "sample" else 1.0
+
+        def reset():
+            tok.fill_(bos); f["ended"].zero_(); f["len"].zero_(); logprob.zero_(); rnd.zero_()
+
+        def one(r, timed):
+            src, dst = (Bb, A) if r % 2 == 0 else (A, Bb)
+            logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
+            lib.vc_decode_pick_f32(_stream(), P(logits), M, V, V, temp, P(ud) if ud is not None else None, max_len, P(rnd), int(eos), P(tok),
+                                   P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob))
+            lib.vc_decode_round_end_i32(_stream(), P(f["ended"]), M, P(pending), P(rnd))
+
+        Kc = int(check_every) if check_every and check_every % 2 == 0 else 4   # rounds per captured chunk (even: the state ends where it started)
+        self._pack_wh(M)
+        Bb["c2"].copy_(c0); Bb["h2"].copy_(h0)    # state before round 0 lives in set B; round r reads set (B, A, B, ...) and writes the other
+        baked = [tok, rnd, pending, ibuf, dbuf, ud, self._ones_for(M)] + list(A.values()) + list(Bb.values())
+        kargs = ("diverse", B, K, Kc, max_len, int(eos), method, temp)
+        key = self._graph_key(*kargs, tensors=baked)
+        if key not in self._graphs:   # (the first call of a shape runs one round eagerly: it sizes the workspace a captured chunk bakes)
+            reset()
+            one(0, True)
+            key = self._graph_key(*kargs, tensors=baked)
+        reset()
+        graph = self._capture(key, lambda: [one(r, False) for r in range(Kc)])
+        steps = 0
+        while steps < max_len:
+            k = min(Kc, max_len - steps)
+            if graph is not None and k == Kc:
+                graph.replay()
+            else:
+                for r in range(k):
+                    one(r, True)
+            steps += k
+            if steps < max_len and check_every and pending.item() == 0:
+                break
+        lib.vc_diverse_rank(_stream(), M, B, K, max_len, P(f["seq"]), P(f["len"]), P(f["ended"]), P(logprob), float(len_norm_f),
+                            P(f["n_distinct"]), P(f["rep"]), P(f["count"]), P(score))
+        ihost, dhost = self._pinned(tag + "ihost", ibuf.numel(), i32), self._pinned(tag + "dhost", dbuf.numel(), torch.float64)
+        ihost.copy_(ibuf, non_blocking=True)
+        dhost.copy_(dbuf, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return diverse_from_host(ihost.numpy(), dhost.numpy(), io, B, K, max_len, n_best, candidates=True)
+
+    def diverse(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, method="greedy", n_best=None, max_len=None, len_norm_f=0.7,
+                uniforms=None, check_every=4):
+        """Diverse captioning (the AG-CVAE paper's purpose of z): per image `draws` = K independent latent draws, each decoded with
+        `greedy` (argmax) or `sample` (inverse CDF at params.temperature) up to and including its first <EOS> (at most max_len tokens),
+        log-likelihood = sum of the emitted tokens' log-softmax at temperature 1 (f32 terms, f64 sum), score = logprob / (1 + n)**len_norm_f
+        (the 1 counts <BOS>, decoder.py:285-286).  Candidates with identical tokens are merged (best score and its draw kept, ties: lower
+        draw; count = draws that produced it); <EOS>-ended captions rank before captions cut at max_len (decoder.py:296-299), then score
+        descending, then lower draw.  Returns per image the first n_best (None: all) entries (tokens, score, count).
+        eps: [K, S, B, L] N(0,1) draws (Philox on device when None); uniforms: [K, max_len, B] in [0, 1) for method="sample" (draw k
+        consumes uniforms[k] as sample(..., uniforms=uniforms[k]) does; Philox when None).  Rounds replay as hipGraph chunks of
+        check_every rounds with a 4-byte "all ended" read between chunks; VC_DECODE_GRAPH=0 keeps the eager loop (same outputs).  Images
+        are decoded in passes of <= diverse_rows candidate rows, every image with all of its draws in one pass.
+        self.last_candidates: per image the K candidates (tokens, logprob, ended) in draw order."""
+        K = int(draws)
+        if not 1 <= K <= DIVERSE_MAX_DRAWS:
+            raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
+        if method not in ("greedy", "sample"):
+            raise ValueError("method must be 'greedy' or 'sample' (got %r)" % (method,))
+        p = self.p
+        max_len = int(max_len or p.gen_max_len)
+        B = int(features.shape[0])
+        if eps is not None and tuple(np.shape(eps)) != (K, p.gen_z_samples, B, p.latent_size):
+            raise ValueError("eps must be [draws, gen_z_samples, images, latent_size] = %s" % ((K, p.gen_z_samples, B, p.latent_size),))
+        if uniforms is not None and tuple(np.shape(uniforms)) != (K, max_len, B):
+            raise ValueError("uniforms must be [draws, max_len, images] = %s" % ((K, max_len, B),))
+        if c_v is not None:
+            c_v = np.asarray(c_v)
+        G = max(1, self.diverse_rows // K)
+        res, cands = [], []
+        for g0 in range(0, B, G):
+            sl = slice(g0, min(B, g0 + G))
+            r, c = self._diverse_pass(features[sl], c_v[sl] if c_v is not None else None, np.asarray(eps)[:, :, sl] if eps is not None else None,
+                                      K, method, bos, eos, max_len, len_norm_f, n_best,
+                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every)
+            res += r
+            cands += c
+        self.last_candidates = cands
+        return res
 
     # ------------------------------------------------------------------ beam search
     def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused):

@@ -4,7 +4,9 @@ Counterpart of the reference's `inference(params, decoder, val_gen, test_gen, im
 (ops/inference.py:4-56): same argument list, same output files -- `./val_{gen_name}.json` and `./test_{gen_name}.json`,
 each a list of `{"image_id": ..., "caption": ...}` -- produced by the batched on-device decoders of
 `vae_model/decoder.py`.  Validation images use `params.sample_gen` (beam search or greedy / sampling); the test set is
-always decoded with `online_inference`, as in the reference."""
+always decoded with `online_inference`, as in the reference.  `sample_gen == "diverse"` (additive): the validation images go through
+`diverse_inference`; `./val_{gen_name}.json` keeps the COCO shape with each image's top caption and
+`./val_{gen_name}_diverse.json` holds the full per-image lists (captions, scores, counts)."""
 import json
 import os
 
@@ -20,6 +22,8 @@ def _cluster_rows(c_v, wanted):
 
 
 def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
+    if allow_beam and params.sample_gen == "diverse":
+        return decoder.diverse_inference(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "beam_search":
         return decoder.beam_search(sess, ids, images, placeholder, c_v, beam_size=params.beam_size)
     return decoder.online_inference(sess, ids, images, placeholder, c_v=c_v)[0]
@@ -52,6 +56,9 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
     records = []
     for images, _caps, _lens, ids, c_v in val_gen.next_val_batch(get_image_ids=True, use_obj_vectors=params.use_c_v):
         records += _decode(decoder, params, sess, image_f_inputs, ids, images, _cluster_rows(c_v, val_cv), allow_beam=True)
+    if params.sample_gen == "diverse":
+        _store("./val_{}_diverse.json".format(params.gen_name), records)
+        records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]
     _store("./val_{}.json".format(params.gen_name), records)
     if test_gen is None:
         return

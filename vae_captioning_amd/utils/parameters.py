@@ -25,6 +25,7 @@ _DEFAULTS = dict(
     image_net_weights_path="./utils/vgg16_weights.npz",
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
+    diverse_draws=20, diverse_method="greedy",
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -44,13 +45,16 @@ _FLAGS = [
     ("--max_steps", "max_steps", int, None), ("--captions_json", "captions_json", str, None),
     ("--features_pickle", "features_pickle", str, None), ("--cluster_pickle", "cluster_pickle", str, None),
     ("--ckpt_format", "ckpt_format", str, ["tf", "npz"]),
+    ("--diverse_draws", "diverse_draws", int, None), ("--diverse_method", "diverse_method", str, ["greedy", "sample"]),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
          "--captions_json": "COCO captions json (with --features_pickle: in-memory real-data path)",
          "--features_pickle": "pickle {file_name: fc2 feature [1, 4096]} (the reference's ./pickles/<split>.pickle format)",
          "--cluster_pickle": "pickle {file_name: 91-vector} (the reference's ./obj_vectors/c_v.pickle)",
-         "--ckpt_format": "tf = TensorFlow V2 checkpoint files (what tf.train.Saver writes), npz = numpy archive"}
+         "--ckpt_format": "tf = TensorFlow V2 checkpoint files (what tf.train.Saver writes), npz = numpy archive",
+         "--diverse_draws": "--sample_gen diverse: latent draws per image (1..256; default 20)",
+         "--diverse_method": "--sample_gen diverse: decoding of each draw (greedy or sample; default greedy)"}
 
 
 class Parameters(object):

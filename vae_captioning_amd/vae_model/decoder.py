@@ -89,3 +89,22 @@ class Decoder(object):
             texts = [" ".join(d.idx2word[t] for t in s if t not in (bos, eos)) for s, _ in beams]
             cap_list.append({"image_id": pid, "caption": texts if ret_beams else texts[0]})
         return cap_list
+
+    def diverse_inference(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, draws=None, method=None, n_best=None,
+                          len_norm_f=0.7):
+        """Diverse captioning (the purpose of z in the AG-CVAE paper): `draws` latent draws per image (params.diverse_draws), each decoded
+        with `method` (params.diverse_method: greedy or sample), identical captions merged and ranked (generate.py: diverse).  Returns
+        cap_list: per image {"image_id", "caption": the best text, "captions": [texts], "scores": [...], "counts": [...]}."""
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        draws = int(draws if draws is not None else self.params.diverse_draws)
+        method = method if method is not None else self.params.diverse_method
+        res = self._gen().diverse(self._features(in_pictures), use_cv, None, bos, eos, draws=draws, method=method, n_best=n_best,
+                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+        cap_list = []
+        for pid, entries in zip(picture_ids, res):
+            texts = [" ".join(d.idx2word[t] for t in s if t not in (bos, eos)) for s, _, _ in entries]
+            cap_list.append({"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
+                             "scores": [float(sc) for _, sc, _ in entries], "counts": [int(n) for _, _, n in entries]})
+        return cap_list
