@@ -375,3 +375,51 @@ def test_greedy_edge_lengths_match_the_oracle(lib, max_len, check_every):
         for b in range(feats.shape[0]):
             ref = od.greedy(P64, p, feats[b].astype(np.float64), cv[b].astype(np.float64), None, BOS, EOS, c_means=cm, max_len=max_len)
             assert got[b] == ref, (call, b, got[b], ref)
+
+
+def test_beam_chunk_captured_after_the_first_round_grew_the_workspace_is_replayed(lib, monkeypatch):
+    """The first beam round's logits product can be K-split ([B n, H] x [H, V] at H = 512: skinny rows, split-K through the engine's
+    workspace) and grow the workspace that every captured chunk bakes.  The chunk captured at the end of the first call must be keyed
+    by the workspace it bakes: the next identical call replays it instead of running eagerly and capturing a second graph."""
+    import torch
+    from vae_captioning_amd.abi import ptr
+    p = Parameters()
+    p.embed_size, p.encoder_hidden, p.decoder_hidden = 64, 64, 512
+    p.latent_size, p.gen_z_samples, p.cnn_feature_size = 10, 4, 48
+    p.mode, p.num_captions, p.prior = "inference", 1, "Normal"
+    V, B, n, T = 10000, 16, 4, 10
+    rng = np.random.default_rng(12)
+    P0 = spec.init_caption_params(p, V, seed=12)
+    for k in P0:
+        P0[k] = (P0[k] * 3).astype(np.float32) if not k.endswith("bias") else rng.normal(0, 0.5, P0[k].shape).astype(np.float32)
+    feats = np.maximum(rng.standard_normal((B, p.cnn_feature_size)), 0).astype(np.float32)
+    eps = rng.standard_normal((p.gen_z_samples, B, p.latent_size)).astype(np.float32)
+    eng = CaptionEngine(p, V, lib=lib)   # fresh: nothing has sized its workspace yet
+    eng.load_params(P0)
+    gen = CaptionGenerator(eng)
+    at_part = []
+    part = CaptionGenerator._beam_part
+    monkeypatch.setattr(CaptionGenerator, "_beam_part",
+                        lambda self, *a, **k: (at_part.append((ptr(self.e.ws) if self.e.ws is not None else 0, self.e.ws_bytes)), part(self, *a, **k))[1])
+    replayed = []
+    replay = torch.cuda.CUDAGraph.replay
+    monkeypatch.setattr(torch.cuda.CUDAGraph, "replay", lambda g: (replayed.append(g), replay(g))[1])
+    run = lambda g, f, e_: g.beam_search(f, None, e_, BOS, EOS, beam_size=n, max_len=T)
+    beam_graphs = lambda: {k: g for k, g in gen._graphs.items() if k[0] == "beam"}
+
+    first = run(gen, feats, eps)
+    ws0, nb0 = at_part[0]
+    need = lib.vc_gemm_workspace_bytes(B * n, V, p.decoder_hidden)
+    assert need > 0 and need > nb0, (need, nb0)            # the preconditions: a K-split logits product, larger than any sized before
+    assert ptr(eng.ws) != ws0                               # ... so the first round re-allocated the workspace
+    keys = beam_graphs()
+    assert len(keys) == 1 and all(ptr(eng.ws) in k for k in keys), "the captured chunk is keyed by the workspace it bakes"
+    replayed.clear()
+    assert run(gen, feats, eps) == first
+    assert beam_graphs().keys() == keys.keys(), "an identical second call captures nothing new"
+    assert any(g in keys.values() for g in replayed), "... and replays the chunk of the first"
+    assert first == run(CaptionGenerator(eng), feats, eps)
+    feats2 = np.maximum(rng.standard_normal(feats.shape), 0).astype(np.float32)
+    eps2 = rng.standard_normal(eps.shape).astype(np.float32)
+    third = run(gen, feats2, eps2)
+    assert third == run(CaptionGenerator(eng), feats2, eps2) and third != first

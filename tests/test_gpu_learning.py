@@ -95,6 +95,38 @@ def test_a_generator_used_before_training_decodes_with_the_trained_weights(lib):
     assert decode_all(old) == before
 
 
+@pytest.mark.parametrize("H", [128, 512], ids=["H128-xproj", "H512-packed-Wh"])
+def test_a_generator_used_before_captured_training_steps_decodes_with_the_trained_weights(lib, H):
+    """After Trainer.capture() a training step is one graph replay: the optimiser kernels rewrite the parameters with neither torch's
+    version counter nor CaptionEngine.apply_gradients (not called from Python) noticing.  A replay must still count as a parameter
+    update, or a generator made before it keeps decoding with its stale vocabulary projection table (beam search) and, at H = 512,
+    its stale packed decoder Wh (greedy and beam search)."""
+    p = _params(num_captions=1, batch_size=8, learning_rate=4e-3, prior="Normal", decoder_hidden=H)
+    V, B, T = 60, 8, 7
+    rng = np.random.default_rng(7)
+    batch = synth.make_batch(rng, B, 1, T, V, variable_len=True, feature_size=p.cnn_feature_size)
+    tr = Trainer(p, V, lib=lib, seed=5)
+    tr.load_state_dict(spec.init_caption_params(p, V, seed=3))
+    tr.set_batch(batch)
+    tr.capture()
+    eps = rng.standard_normal((p.gen_z_samples, B, p.latent_size)).astype(np.float32)
+    old = CaptionGenerator(tr.cap)
+    decode_all = lambda g: (g.greedy(batch["features"], None, eps, synth.BOS, synth.EOS, max_len=T + 3),
+                            g.beam_search(batch["features"], None, eps, synth.BOS, synth.EOS, beam_size=3, max_len=T + 3))
+    before = decode_all(old)
+    v0 = tr.cap.param_version
+    for _ in range(40):
+        tr.train_step()
+    assert tr.graph is not None and tr.cap.param_version != v0
+    after = decode_all(old)
+    assert after == decode_all(CaptionGenerator(tr.cap)) and after != before
+    P64 = {k: v.astype(np.float64) for k, v in tr.state_dict().items()}
+    for b in (0, 3, 6):
+        ref = decode.greedy(P64, p, batch["features"][b].astype(np.float64), None, eps[:, b:b + 1].astype(np.float64), synth.BOS, synth.EOS,
+                            max_len=T + 3)
+        assert after[0][b] == ref, (b, after[0][b], ref)
+
+
 @pytest.mark.parametrize("name,lr,kw", [("normal", 5e-4, dict(prior="Normal")), ("ag_cv", 2e-4, dict(prior="AG", use_c_v=True))])
 def test_fifty_consecutive_steps_stay_on_the_oracles_trajectory(lib, name, lr, kw):
     """AG runs at lr = 2e-4: at 5e-4 its KL term (482 at the start, Q3's per-row sum) reaches its floor after ~40 steps, and from there

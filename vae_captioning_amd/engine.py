@@ -951,7 +951,8 @@ class CaptionEngine(object):
     @property
     def param_version(self):
         """Changes whenever the parameter values may have: torch counts in-place writes through the flat buffer or a view of it
-        (load_params, checkpoint restore, p.copy_), apply_gradients counts its own optimiser kernels.  Derived operands (the
+        (load_params, checkpoint restore, p.copy_), apply_gradients counts its own optimiser kernels and Trainer.train_step each replay
+        of a captured step (whose optimiser kernels run without apply_gradients being called).  Derived operands (the
         generator's packed Wh, its vocabulary projection table) are rebuilt when this differs from the version they were built at."""
         return (self.store.p._version, self.param_updates, self.store.p.data_ptr(), self.gemm_flags)
 

@@ -655,9 +655,11 @@ class CaptionGenerator(object):
             lib.vc_count_nonzero_i32(_stream(), P(pcount), B, P(alive))
 
         pt.one, pt.chunk_fn, pt.alive, pt.pcount = one, chunk_fn, alive, pcount
-        pt.key = self._graph_key("beam", B, n, L, K, int(eos), float(len_norm_f),
-                                 tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot, c_free, c_sent,
-                                          parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M)] + list(bufs.values()))
+        # (the key names the engine's workspace: recomputed before the capture, since the eager rounds of a first call may grow it)
+        pt.key_fn = lambda: self._graph_key("beam", B, n, L, K, int(eos), float(len_norm_f),
+                                            tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot,
+                                                     c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M)] + list(bufs.values()))
+        pt.key = pt.key_fn()
         pt.graph = self._graphs.get(pt.key) if fused else None
         pt.ibuf, pt.dbuf, pt.ioff = ibuf, dbuf, {k_: v[0] for k_, v in iv.items()}
         pt.ihost, pt.dhost = self._pinned(tag + "ihost", ibuf.numel(), i32), self._pinned(tag + "dhost", 2 * M, f64)
@@ -762,5 +764,6 @@ class CaptionGenerator(object):
         if fused and rounds > K:
             for pt in parts:
                 if pt.graph is None:
+                    pt.key = pt.key_fn()
                     self._capture(pt.key, pt.chunk_fn)   # (the results are on the host: the capture touches no state)
         return res

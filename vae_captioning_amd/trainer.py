@@ -798,6 +798,7 @@ class Trainer(object):
     def train_step(self):
         if self.graph is not None:
             self.graph.replay()
+            self.cap.param_updates += 1   # the replayed optimiser kernels rewrote the parameters (CaptionEngine.param_version)
         else:
             self._step()
 
