@@ -33,6 +33,8 @@ extern "C" {
  *      entries vc_softmax_topk_rows_f32 / vc_beam_gather_f32 / vc_eos_track_i32 / vc_beam_init.
  *      Added within 4 (additive, no layout change): the diverse-captioning entries vc_diverse_latent_f32 / vc_decode_pick_f32 /
  *      vc_decode_round_end_i32 / vc_diverse_rank.
+ *      Added within 4 (additive, no layout change): the consensus re-ranking entries vc_l2_normalize_rows_f32 / vc_topk_rows_wide_f32 /
+ *      vc_topk_rows_wide_workspace_bytes / vc_ngram_vectors / vc_consensus_score.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -492,6 +494,39 @@ int vc_decode_pick_f32(void* stream, const float* logits, long rows, int V, long
 int vc_decode_round_end_i32(void* stream, const int32_t* done, long rows, float* pending, int32_t* round);
 int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32_t* seq, const int32_t* len, const int32_t* ended,
                     const double* logprob, double len_norm_f, int32_t* n_distinct, int32_t* rep, int32_t* count, double* score);
+
+/* ------------------------------------------------------------------------------------
+ * Consensus re-ranking of diverse captions (consensus.py: ConsensusIndex; Devlin et al. 2015).  An index of D images (fc2 feature row,
+ * one or more human captions); a query's k nearest index images by cosine, their captions pooled (neighbour order), every candidate
+ * caption scored by the float64 mean of its m' = min(m, |pool|) largest CIDEr-D values against the pool.  Words: token ids without
+ * <BOS>, <EOS> and PAD (0), at most 64, ids <= 65535.  n-gram keys (n = 1..4): the n ids packed 16 bits each, last word in the low bits.
+ *   l2_normalize_rows   y[r] = x[r] / |x[r]| (f32 sum of squares; zero rows stay zero).  y == x allowed.
+ *   topk_rows_wide      the first k (<= 256) entries of each row under (value descending, index ascending): with exclude NULL (or -1)
+ *                       bit-identical to vc_topk_rows_f32 for non-NaN rows (+0 and -0 tie by index).  exclude[r] >= 0 drops column
+ *                       exclude[r] of row r; slots past the row's eligible columns get index -1, value -inf.  One read of each row:
+ *                       the best k of each 4096-column chunk (one workgroup) selected in LDS, the k-lists merged 4096 keys per
+ *                       workgroup per launch.
+ *                       ws: vc_topk_rows_wide_workspace_bytes(rows, cols, k) bytes (0 when cols <= 4096).
+ *   ngram_vectors       per token row r of tok [n, ld] (the first len[r] entries): words[r] = its number of words L; the sorted distinct
+ *                       n-gram keys of its words with weight count * idf in f32 (idf: the entry of the sorted df_keys [n_df] table, or
+ *                       idf_unseen) at keys / w [off[r], off[r + 1]) (nnz[r] of them; the host sizes the range for L words:
+ *                       sum_n max(0, L - n + 1)); norm[r, n-1] = |v_n| (sum of squares in f64, stored f32).  One wave per row.
+ *   consensus_score     image b (< B) has candidates cand_img[b] .. cand_img[b+1] - 1 (at most max_cands <= 256) and neighbours
+ *                       nbr [B, k] (k <= 256; -1 = none); index image i has the captions img_cap[i] .. img_cap[i+1] - 1 (pool <= 2048).
+ *                       Captions (r_*) and candidates (c_*) are ngram_vectors outputs (off, nnz, keys, w, norm [.,4], words).  CIDEr-D(c, r)
+ *                       = 10 exp(-(L(c) - L(r))^2 / 72) / 4 sum_n sum_g min(c_g, r_g) r_g / (|c_n| |r_n|) (0 when a norm is 0), in f32;
+ *                       score[c] = f64 mean of the m' largest over the pool.  One workgroup per image and 4 candidates, ~53 KiB LDS. */
+int vc_l2_normalize_rows_f32(void* stream, const float* x, long rows, int cols, long ld, float* y, long ldy);
+size_t vc_topk_rows_wide_workspace_bytes(long rows, int cols, int k);
+int vc_topk_rows_wide_f32(void* stream, const float* x, long rows, int cols, long ld, int k, const int32_t* exclude, float* out_val,
+                          int32_t* out_idx, void* ws, size_t ws_bytes);
+int vc_ngram_vectors(void* stream, const int32_t* tok, long n, long ld, const int32_t* len, int bos, int eos, const uint64_t* df_keys,
+                     const float* idf, long n_df, float idf_unseen, const int32_t* off, uint64_t* keys, float* w, int32_t* nnz, float* norm,
+                     int32_t* words);
+int vc_consensus_score(void* stream, int B, int k, const int32_t* nbr, const int32_t* img_cap, const int32_t* r_off, const int32_t* r_nnz,
+                       const uint64_t* r_keys, const float* r_w, const float* r_norm, const int32_t* r_len, const int32_t* cand_img,
+                       int max_cands, const int32_t* c_off, const int32_t* c_nnz, const uint64_t* c_keys, const float* c_w,
+                       const float* c_norm, const int32_t* c_len, int m, double* score);
 
 /* ------------------------------------------------------------------------------------
  * Host-side helper (the only entry point that takes HOST pointers): CRC-32C (Castagnoli) of a byte

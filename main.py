@@ -74,6 +74,27 @@ def coco_batches(gen, params, epoch_rule=False, world=1):
             return
 
 
+def consensus_index(params, tr, cap_dict, coco_train):
+    """--diverse_rerank consensus: the index of training images (fc2 features + captions) that diverse captions are re-ranked against.
+    MSCOCO: the training generator's images (train + repartitioned val, never the held-out ones); --synthetic: 512 seeded images with
+    5 captions each."""
+    from vae_captioning_amd.consensus import ConsensusIndex, index_data_from_generator
+    if params.fine_tune:
+        raise SystemExit("--diverse_rerank consensus needs precomputed fc2 features for its index of training images; "
+                         "an index from a fine-tuned VGG16 is not supported (drop --fine_tune)")
+    if coco_train is not None:
+        feats, caps = index_data_from_generator(coco_train)
+    elif params.synthetic:
+        b = synth.make_batch(np.random.default_rng(params.seed + 11), 512, 5, 12, params.vocab_size, feature_size=params.cnn_feature_size)
+        feats = b["features"]
+        caps = [[[int(t) for t in r] for r in b["cap_enc"][i * 5:(i + 1) * 5]] for i in range(512)]   # "w.. <EOS>", 11 words
+    else:
+        raise SystemExit("--diverse_rerank consensus needs the MSCOCO training images (--coco_dir) or --synthetic")
+    bos, eos = cap_dict.word2idx["<BOS>"], cap_dict.word2idx["<EOS>"]
+    print("consensus index: %d images, k = %d, m = %d" % (len(caps), params.consensus_k, params.consensus_m))
+    return ConsensusIndex(tr.cap, feats, caps, bos, eos, k=params.consensus_k, m=params.consensus_m, vocab_size=cap_dict.vocab_size)
+
+
 def main(params):
     import torch
     import torch.distributed as dist
@@ -211,6 +232,8 @@ def main(params):
     if params.mode == "inference":
         # ops/inference.py:4-39: captions for the validation images -> ./val_{gen_name}.json
         decoder = Decoder(None, None, None, params, cap_dict)
+        if params.sample_gen == "diverse" and params.diverse_rerank == "consensus":
+            decoder.consensus_index = consensus_index(params, tr, cap_dict, coco_train)
         if coco_val is not None:  # ops/inference.py:4-56 on the validation / test image sets
             from vae_captioning_amd.ops.inference import inference
             if rank == 0:

@@ -6,7 +6,9 @@ each a list of `{"image_id": ..., "caption": ...}` -- produced by the batched on
 `vae_model/decoder.py`.  Validation images use `params.sample_gen` (beam search or greedy / sampling); the test set is
 always decoded with `online_inference`, as in the reference.  `sample_gen == "diverse"` (additive): the validation images go through
 `diverse_inference`; `./val_{gen_name}.json` keeps the COCO shape with each image's top caption and
-`./val_{gen_name}_diverse.json` holds the full per-image lists (captions, scores, counts)."""
+`./val_{gen_name}_diverse.json` holds the full per-image lists (captions, scores, counts).  With `params.diverse_rerank ==
+"consensus"` (a `consensus.ConsensusIndex` attached to the decoder) the top caption is the consensus winner and the lists also hold
+the consensus scores."""
 import json
 import os
 

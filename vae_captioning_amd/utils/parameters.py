@@ -25,7 +25,7 @@ _DEFAULTS = dict(
     image_net_weights_path="./utils/vgg16_weights.npz",
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
-    diverse_draws=20, diverse_method="greedy",
+    diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -46,6 +46,8 @@ _FLAGS = [
     ("--features_pickle", "features_pickle", str, None), ("--cluster_pickle", "cluster_pickle", str, None),
     ("--ckpt_format", "ckpt_format", str, ["tf", "npz"]),
     ("--diverse_draws", "diverse_draws", int, None), ("--diverse_method", "diverse_method", str, ["greedy", "sample"]),
+    ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus"]), ("--consensus_k", "consensus_k", int, None),
+    ("--consensus_m", "consensus_m", int, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -54,7 +56,11 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--cluster_pickle": "pickle {file_name: 91-vector} (the reference's ./obj_vectors/c_v.pickle)",
          "--ckpt_format": "tf = TensorFlow V2 checkpoint files (what tf.train.Saver writes), npz = numpy archive",
          "--diverse_draws": "--sample_gen diverse: latent draws per image (1..256; default 20)",
-         "--diverse_method": "--sample_gen diverse: decoding of each draw (greedy or sample; default greedy)"}
+         "--diverse_method": "--sample_gen diverse: decoding of each draw (greedy or sample; default greedy)",
+         "--diverse_rerank": "--sample_gen diverse: order of each image's captions (likelihood, or consensus with the captions of its "
+                             "nearest training images; default likelihood)",
+         "--consensus_k": "--diverse_rerank consensus: nearest training images per image (1..256; default 90)",
+         "--consensus_m": "--diverse_rerank consensus: best-matching pool captions averaged per candidate (>= 1; default 125)"}
 
 
 class Parameters(object):
@@ -71,7 +77,8 @@ class Parameters(object):
         return ap
 
     def parse_args(self, argv=None):
-        args = vars(self.build_parser().parse_args(argv))
+        ap = self.build_parser()
+        args = vars(ap.parse_args(argv))
         for flag, attr, conv, _ in _FLAGS:
             val = args[flag.lstrip("-")]
             if attr is None:
@@ -85,6 +92,10 @@ class Parameters(object):
                 setattr(self, attr, conv(val))
             else:
                 setattr(self, attr, getattr(self, attr))  # materialise the default on the instance (it is pickled by --save_params)
+        if not 1 <= self.consensus_k <= 256:
+            ap.error("--consensus_k must be 1..256 (got %d)" % self.consensus_k)
+        if self.consensus_m < 1:
+            ap.error("--consensus_m must be >= 1 (got %d)" % self.consensus_m)
         if self.synthetic:
             self.vocab_size = int(args["vocab"]) if args["vocab"] is not None else 10000
         self.hdf5_file = self.coco_dir + os.path.basename(self.hdf5_file)  # the image array lives next to the data set

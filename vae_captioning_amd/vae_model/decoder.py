@@ -22,6 +22,7 @@ class Decoder(object):
         self.c_i = None
         self.c_i_ph = None
         self.cap_clusters = None
+        self.consensus_index = None  # consensus.ConsensusIndex: --diverse_rerank consensus re-ranks diverse captions against it
 
     def px_z_fi(self, observed, gen_mode=False):
         """Training graph: returns (model, x_logits, shpe, (initial_state, final_state, sample)) like
@@ -94,17 +95,30 @@ class Decoder(object):
                           len_norm_f=0.7):
         """Diverse captioning (the purpose of z in the AG-CVAE paper): `draws` latent draws per image (params.diverse_draws), each decoded
         with `method` (params.diverse_method: greedy or sample), identical captions merged and ranked (generate.py: diverse).  Returns
-        cap_list: per image {"image_id", "caption": the best text, "captions": [texts], "scores": [...], "counts": [...]}."""
+        cap_list: per image {"image_id", "caption": the best text, "captions": [texts], "scores": [...], "counts": [...]}.
+        params.diverse_rerank == "consensus": every distinct caption is re-ranked by its consensus against the attached
+        `consensus_index` (consensus.py) before n_best cuts the list; the records gain "consensus" (aligned with "captions") and
+        "caption" is the consensus winner."""
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
         draws = int(draws if draws is not None else self.params.diverse_draws)
         method = method if method is not None else self.params.diverse_method
-        res = self._gen().diverse(self._features(in_pictures), use_cv, None, bos, eos, draws=draws, method=method, n_best=n_best,
+        consensus = getattr(self.params, "diverse_rerank", "likelihood") == "consensus"
+        if consensus and self.consensus_index is None:
+            raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
+                               "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
+        feats = self._features(in_pictures)
+        res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus else n_best,
                                   max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+        if consensus:
+            res = self.consensus_index.rerank(feats, res, n_best=n_best)
         cap_list = []
         for pid, entries in zip(picture_ids, res):
-            texts = [" ".join(d.idx2word[t] for t in s if t not in (bos, eos)) for s, _, _ in entries]
-            cap_list.append({"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
-                             "scores": [float(sc) for _, sc, _ in entries], "counts": [int(n) for _, _, n in entries]})
+            texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
+            rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
+                   "scores": [float(e[1]) for e in entries], "counts": [int(e[2]) for e in entries]}
+            if consensus:
+                rec["consensus"] = [float(e[3]) for e in entries]
+            cap_list.append(rec)
         return cap_list
