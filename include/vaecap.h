@@ -35,6 +35,8 @@ extern "C" {
  *      vc_decode_round_end_i32 / vc_diverse_rank.
  *      Added within 4 (additive, no layout change): the consensus re-ranking entries vc_l2_normalize_rows_f32 / vc_topk_rows_wide_f32 /
  *      vc_topk_rows_wide_workspace_bytes / vc_ngram_vectors / vc_consensus_score.
+ *      Added within 4 (additive, no layout change): the caption-scoring entries vc_logits_logprob_f32 /
+ *      vc_logits_logprob_workspace_bytes / vc_score_reduce_f64.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -527,6 +529,25 @@ int vc_consensus_score(void* stream, int B, int k, const int32_t* nbr, const int
                        const uint64_t* r_keys, const float* r_w, const float* r_norm, const int32_t* r_len, const int32_t* cand_img,
                        int max_cands, const int32_t* c_off, const int32_t* c_nnz, const uint64_t* c_keys, const float* c_w,
                        const float* c_norm, const int32_t* c_len, int m, double* score);
+
+/* ------------------------------------------------------------------------------------
+ * Scoring given captions (generate.py: CaptionGenerator.score; csrc/score.hip).  Forward only.
+ *   logits_logprob   lp[r] = (hs[r] . W[:, labels[r]] + bias[labels[r]]) - log sum_{v < V} exp(hs[r] . W[:, v] + bias[v]) for every row of
+ *                    hs [rows, H] (row pitch `pitch`), W [H, ldw] (columns >= V, the padding of the stored logits kernel, never enter the
+ *                    sum), bias [V] or NULL.  labels[r] < 0 or >= V: row not scored, lp[r] = 0.  f32 MFMA products, f32 accumulate;
+ *                    H % 32 == 0.  The [rows, V] logits are never written: every 128 x 128 tile of them is reduced on chip to one
+ *                    (max, sum of exp) pair per row, and a second kernel merges a row's cdiv(V, 128) pairs in ascending tile order.
+ *                    No atomics: two calls give identical bits, and a row's value does not depend on `rows`.
+ *                    ws: vc_logits_logprob_workspace_bytes(rows, V, H) = rows * (2 * cdiv(V, 128) + 1) floats, 8-byte aligned; a smaller
+ *                    one is VC_EWORKSPACE.
+ *   score_reduce     lp [T, C*K] (time-major; column c*K + k = caption c under draw k), len [C] (tokens scored, clamped to 0..T):
+ *                    logprob [C, K] = sum_{t < len[c]} lp (float64, ascending t); marginal [C] = log sum_k exp(logprob[c, k]) - log K
+ *                    (float64, max-shifted).  One wave per caption, K <= 256.
+ * ---------------------------------------------------------------------------------- */
+size_t vc_logits_logprob_workspace_bytes(long rows, int V, int H);
+int vc_logits_logprob_f32(void* stream, long rows, int V, int H, const float* hs, long pitch, const float* W, long ldw, const float* bias,
+                          const int32_t* labels, float* lp, float* ws, size_t ws_bytes);
+int vc_score_reduce_f64(void* stream, const float* lp, int T, int C, int K, const int32_t* len, double* logprob, double* marginal);
 
 /* ------------------------------------------------------------------------------------
  * Host-side helper (the only entry point that takes HOST pointers): CRC-32C (Castagnoli) of a byte

@@ -242,7 +242,7 @@ def main(params):
                 dist.destroy_process_group()
             return
         rng = np.random.default_rng(params.seed + 5)
-        captions_gen = []
+        captions_gen, scores = [], []
         for it in range(2):
             b = synth.make_batch(rng, params.batch_size, 1, 20, params.vocab_size, use_ci=spec.uses_ci(params), images=params.fine_tune)
             ids = ["synthetic_%06d" % (it * params.batch_size + i) for i in range(params.batch_size)]
@@ -257,10 +257,19 @@ def main(params):
             else:
                 sent, _ = decoder.online_inference(None, ids, pics, None, c_v=c_v)
             captions_gen += sent
+            if params.score_draws:   # held-out likelihood of the batch's own ("human") captions under the prior
+                from vae_captioning_amd.ops.inference import human_captions
+                scores += decoder.score_captions(ids, pics, human_captions((b["cap_dec"], b["cap_enc"]), b["lengths"]), c_v)
         say("Generated {} captions".format(len(captions_gen)))
         if rank == 0:
             with open("./val_{}.json".format(params.gen_name), "w") as wj:
                 json.dump(captions_gen, wj)
+            if params.sample_gen == "diverse":   # the full per-image lists under the name ops/inference.py gives them
+                with open("./val_{}_diverse.json".format(params.gen_name), "w") as wj:
+                    json.dump(captions_gen, wj)
+            if params.score_draws:
+                from vae_captioning_amd.ops.inference import store_scores
+                store_scores(params, scores)
     if world > 1:
         dist.destroy_process_group()
 

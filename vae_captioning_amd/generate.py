@@ -11,6 +11,7 @@ tie order, score = logprob / len**0.7 for completed captions, `<BOS>` consumed t
 Per-image semantics of the z input are those of batch 1: row b of the z_rnn input is the S
 samples of image b (the Q1 reshape is the identity at N = 1).
 """
+import gc
 import os
 import types
 
@@ -24,7 +25,7 @@ from .engine import K_CL, _stream
 # vae_model/decoder.py:56 -- category ids absent from MSCOCO (obj_vectors/category_index.pickle)
 UN_CLUSTERS = {0, 66, 68, 69, 71, 12, 45, 83, 26, 29, 30}
 
-PHASE_TIMES = None   # diagnostics (tools/experiments/prof_beam.py): a dict here makes beam_search synchronise at its phase boundaries and add up seconds
+PHASE_TIMES = None   # diagnostics (tools/experiments/prof_beam.py, score_time.py): a dict here makes beam_search / score synchronise at its phase boundaries and add up seconds
 
 
 def _phase(name, t0):
@@ -106,6 +107,17 @@ def diverse_from_host(ints, dbls, io, B, K, L, n_best=None, candidates=False):
     return res, cands
 
 
+SCORE_MAX_TOKENS = 256   # score(): tokens scored per caption (human captions may be longer than gen_max_len)
+
+
+def rerank_by_marginal(entries, marginals, eos, len_norm_f):
+    """diverse(rerank="marginal"): entries [(tokens, score, count), ...] in likelihood order and their marginals ->
+    [(tokens, marginal / (1 + n)**len_norm_f, count, marginal), ...]: <EOS>-ended before cut captions, then the new score descending;
+    exact ties keep the likelihood order (a stable sort)."""
+    new = [(t, m / (1 + len(t)) ** len_norm_f, n, m) for (t, _, n), m in zip(entries, marginals)]
+    return sorted(new, key=lambda x: (not (len(x[0]) > 0 and x[0][-1] == eos), -x[1]))
+
+
 class CaptionGenerator(object):
     def __init__(self, engine):
         self.e = engine
@@ -122,6 +134,9 @@ class CaptionGenerator(object):
         self.slices, self.slice_rows = 2, 256   # beam search: images decoded as `slices` independent slices when each has >= slice_rows rows
         self.diverse_rows = 4096  # diverse captioning: candidate rows (images x draws) per pass
         self.last_candidates = None   # diverse(): per image the K candidates (tokens, logprob, ended) of the last call, in draw order
+        # score(): row-steps (sequence rows x steps) per pass; act [T, N, 4H] + cs, hs [T + 1, N, H] are <= 8 H floats per row-step: 1 GiB
+        self._t_score = 0.0   # (diagnostics: PHASE_TIMES)
+        self.score_rows = max(1, (1 << 30) // (32 * int(engine.p.decoder_hidden)))
 
     def _b(self, name, shape, dtype=torch.float32):
         t = self.buf.get(name)
@@ -332,8 +347,16 @@ class CaptionGenerator(object):
                 self._graphs.clear()
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
+            # no cyclic garbage collection inside the capture: a collected object that owns device memory or a graph (a generator in a
+            # reference cycle, say) would free it in the middle of the capture, which the runtime answers with an abort
+            gc_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g):
+                    fn()
+            finally:
+                if gc_on:
+                    gc.enable()
             self._graphs[key] = g
         return g
 
@@ -493,7 +516,7 @@ class CaptionGenerator(object):
             self._capture(key, lambda: launches(False))   # (a capture executes nothing: the eager launches above are this call's)
         return cs1[1], hs1[1]
 
-    def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every):
+    def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every, rerank="likelihood"):
         """One pass of diverse(): the B*K candidate rows of B images decoded together, ranked per image on device (vc_diverse_rank),
         results in two flat buffers brought back by two copies into pinned memory."""
         lib, e, p = self.lib, self.e, self.p
@@ -560,10 +583,138 @@ class CaptionGenerator(object):
         ihost.copy_(ibuf, non_blocking=True)
         dhost.copy_(dbuf, non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        return diverse_from_host(ihost.numpy(), dhost.numpy(), io, B, K, max_len, n_best, candidates=True)
+        if rerank != "marginal":
+            return diverse_from_host(ihost.numpy(), dhost.numpy(), io, B, K, max_len, n_best, candidates=True)
+        # re-score every distinct caption under ALL K draws of the pass: their initial states are still in _diverse_init's buffers
+        res, cands = diverse_from_host(ihost.numpy(), dhost.numpy(), io, B, K, max_len, None, candidates=True)
+        caps = [[list(t) for t, _, _ in r] for r in res]
+        self._t_score = _phase("", 0.0)
+        _, marg = self._score_states(c0, h0, K, caps, bos)
+        out, o = [], 0
+        for b in range(B):
+            out.append(rerank_by_marginal(res[b], marg[o:o + len(res[b])].tolist(), eos, len_norm_f)[:n_best])
+            o += len(res[b])
+        return out, cands
+
+    # ------------------------------------------------------------------ scoring given captions
+    def _score_states(self, c0, h0, K, caps, bos):
+        """Teacher-forced log-likelihood of caps[b] (token lists without <BOS>) under the K draws of image b whose decoder states are rows
+        b*K + k of c0 / h0 [B*K, H]: (logprob float64 [C, K], marginal float64 [C]) over the C captions in image order.  Sequence rows are
+        caption-major, draw-minor; one upload of the indices, one copy of the results into pinned memory."""
+        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        E, Hd, V = p.embed_size, p.decoder_hidden, e.V
+        flat = [(b, t) for b, cl in enumerate(caps) for t in cl]
+        C = len(flat)
+        T = max([len(t) for _, t in flat] + [0])
+        if C == 0 or T == 0:
+            return np.zeros((C, K), np.float64), np.zeros((C,), np.float64)
+        N = C * K
+        i32 = torch.int32
+        # int32 upload: parent [N], row lengths [N], caption lengths [C], step inputs [T, N], labels [T, N]
+        host = np.zeros(2 * N + C + 2 * T * N, np.int32)
+        o_len, o_clen, o_in, o_lab = N, 2 * N, 2 * N + C, 2 * N + C + T * N
+        toks_in, labels = np.zeros((T, C), np.int32), np.full((T, C), -1, np.int32)
+        for c, (b, t) in enumerate(flat):
+            n = len(t)
+            host[c * K:(c + 1) * K] = b * K + np.arange(K)
+            host[o_clen + c] = n
+            if n:
+                labels[:n, c] = t
+                toks_in[0, c] = bos
+                toks_in[1:n, c] = t[:n - 1]
+        host[o_len:o_len + N] = np.repeat(host[o_clen:o_clen + C], K)
+        host[o_in:o_in + T * N] = np.repeat(toks_in, K, axis=1).ravel()
+        host[o_lab:o_lab + T * N] = np.repeat(labels, K, axis=1).ravel()
+        tag = "sc%d_%d_%d_" % (C, K, T)
+        idx = self._b(tag + "idx", (host.size,), i32)
+        idx.copy_(torch.from_numpy(host), non_blocking=False)
+        parent, lens, clen = idx[:N], idx[o_len:o_len + N], idx[o_clen:o_clen + C]
+        tin, lab = idx[o_in:o_in + T * N], idx[o_lab:o_lab + T * N]
+        X, act = self._b("sc_X", (T, N, E)), self._b("sc_act", (T, N, 4 * Hd))
+        cs, hs = self._b("sc_cs", (T + 1, N, Hd)), self._b("sc_hs", (T + 1, N, Hd))
+        lp, dbuf = self._b("sc_lp", (T * N,)), self._b(tag + "dbuf", (N + C,), torch.float64)
+        st = _stream()
+        t_ph = _phase("score: init chain", self._t_score)
+        lib.vc_beam_gather_f32(st, P(c0), P(h0), P(parent), N, Hd, P(cs[0]), P(hs[0]), None, None, V, 4 * Hd, None)
+        lib.vc_embedding_gather_f32(st, P(S.param("decoder/net/dec_embeddings")), P(tin), T * N, E, V, P(X))
+        for nb in (lib.vc_lstm_seq_workspace_bytes(T, N, E, Hd), lib.vc_gemm_workspace_bytes(T * N, 4 * Hd, E),
+                   lib.vc_logits_logprob_workspace_bytes(T * N, V, Hd)):
+            e._need_ws(nb)
+        lib.vc_lstm_seq_fwd_f32(st, T, N, E, Hd, P(X), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")), P(lens),
+                                P(act), P(cs), P(hs), P(e.ws), e.ws_bytes, e.lstm_flags)
+        t_ph = _phase("score: sequence", t_ph)
+        # (the f32 products on a bf16x3 engine too; the [T*N, V] logits are never written)
+        lib.vc_logits_logprob_f32(st, T * N, V, Hd, P(hs[1]), Hd, P(S.param("decoder/rnn_logits/kernel")), e.Vp,
+                                  P(S.param("decoder/rnn_logits/bias")), P(lab), P(lp), P(e.ws), e.ws_bytes)
+        t_ph = _phase("score: logits + log-probability", t_ph)
+        lib.vc_score_reduce_f64(st, P(lp), T, C, K, P(clen), P(dbuf[:N]), P(dbuf[N:]))
+        dhost = self._pinned(tag + "dhost", dbuf.numel(), torch.float64)
+        dhost.copy_(dbuf, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        out = dhost.numpy().copy()
+        self._t_score = _phase("score: reduce + copy-back", t_ph)
+        return out[:N].reshape(C, K), out[N:]
+
+    def score(self, features, captions, c_v=None, eps=None, bos=1, eos=2, draws=1):
+        """How likely are given captions for their images: per image, per caption {"logprob": float64 [K], "marginal": float, "tokens": n}.
+        captions[b]: token-id lists for image b, with or without the leading <BOS> (stripped), scored up to and including the last token
+        (pass the <EOS> to have it counted, as diverse() does for ended captions); n = tokens scored (empty caption: logprob 0, n 0).
+        logprob[k] = sum of the tokens' log-softmax at temperature 1 (f32 terms, f64 sum in token order) under diverse()'s draw k of the
+        image: z = prior_mean + std * eps[k], state as init_state(features[b:b+1], c_v[b:b+1], eps[k][:, None]); marginal =
+        log 1/K sum_k exp(logprob[k]), the model's likelihood estimate over the draws.  eps: [K, S, B, L] (Philox on device when None: those
+        draws depend on how the passes are cut).  --no_encoder models have no z: every draw gives the same number.
+        Passes: an image goes with all its captions and draws into one pass of <= score_rows row-steps (sequence rows x steps of its
+        longest caption); an image that exceeds it alone gets a pass of its own.  ValueError: a token id outside [0, V), more than
+        SCORE_MAX_TOKENS scored tokens (names image and caption), draws outside 1..DIVERSE_MAX_DRAWS, a wrong eps shape."""
+        K, p, V = int(draws), self.p, self.e.V
+        if not 1 <= K <= DIVERSE_MAX_DRAWS:
+            raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
+        B = int(features.shape[0])
+        if len(captions) != B:
+            raise ValueError("captions must hold one list of captions per image (%d images, %d lists)" % (B, len(captions)))
+        if eps is not None and tuple(np.shape(eps)) != (K, p.gen_z_samples, B, p.latent_size):
+            raise ValueError("eps must be [draws, gen_z_samples, images, latent_size] = %s" % ((K, p.gen_z_samples, B, p.latent_size),))
+        caps = []
+        for b, cl in enumerate(captions):
+            row = []
+            for j, t in enumerate(cl):
+                t = [int(w) for w in t]
+                if t and t[0] == bos:
+                    t = t[1:]
+                if len(t) > SCORE_MAX_TOKENS:
+                    raise ValueError("image %d caption %d: %d tokens to score, at most %d" % (b, j, len(t), SCORE_MAX_TOKENS))
+                if any(w < 0 or w >= V for w in t):
+                    raise ValueError("image %d caption %d: token id outside [0, %d)" % (b, j, V))
+                row.append(t)
+            caps.append(row)
+        if c_v is not None:
+            c_v = np.asarray(c_v)
+        eps = np.asarray(eps) if eps is not None else None
+        res, g0 = [], 0
+        while g0 < B:
+            g1, rows, steps = g0, 0, 0
+            while g1 < B:   # greedy cut: images g0 .. g1-1 while rows x steps fits (an image alone always goes)
+                r2 = rows + len(caps[g1]) * K
+                s2 = max([steps] + [len(t) for t in caps[g1]])
+                if g1 > g0 and r2 * s2 > self.score_rows:
+                    break
+                g1, rows, steps = g1 + 1, r2, s2
+            sl = slice(g0, g1)
+            if rows * steps == 0:
+                lp, marg = np.zeros((rows // K, K), np.float64), np.zeros((rows // K,), np.float64)
+            else:
+                self._t_score = _phase("", 0.0)
+                c0, h0 = self._diverse_init(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None, K)
+                lp, marg = self._score_states(c0, h0, K, caps[sl], bos)
+            o = 0
+            for b in range(g0, g1):
+                res.append([{"logprob": lp[o + j].copy(), "marginal": float(marg[o + j]), "tokens": len(t)} for j, t in enumerate(caps[b])])
+                o += len(caps[b])
+            g0 = g1
+        return res
 
     def diverse(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, method="greedy", n_best=None, max_len=None, len_norm_f=0.7,
-                uniforms=None, check_every=4):
+                uniforms=None, check_every=4, rerank="likelihood"):
         """Diverse captioning (the AG-CVAE paper's purpose of z): per image `draws` = K independent latent draws, each decoded with
         `greedy` (argmax) or `sample` (inverse CDF at params.temperature) up to and including its first <EOS> (at most max_len tokens),
         log-likelihood = sum of the emitted tokens' log-softmax at temperature 1 (f32 terms, f64 sum), score = logprob / (1 + n)**len_norm_f
@@ -574,12 +725,18 @@ class CaptionGenerator(object):
         consumes uniforms[k] as sample(..., uniforms=uniforms[k]) does; Philox when None).  Rounds replay as hipGraph chunks of
         check_every rounds with a 4-byte "all ended" read between chunks; VC_DECODE_GRAPH=0 keeps the eager loop (same outputs).  Images
         are decoded in passes of <= diverse_rows candidate rows, every image with all of its draws in one pass.
-        self.last_candidates: per image the K candidates (tokens, logprob, ended) in draw order."""
+        self.last_candidates: per image the K candidates (tokens, logprob, ended) in draw order.
+        rerank="marginal": every distinct caption of an image is re-scored under ALL K draws of its pass (score()'s marginal
+        log 1/K sum_k p(caption | z_k, image), nothing drawn again) and the entries are ordered by marginal / (1 + n)**len_norm_f:
+        <EOS>-ended first, then that score descending, exact ties in the likelihood order; entries become (tokens, score, count, marginal)
+        with `score` the new one.  n_best cuts after the re-ranking.  "likelihood" (default) is the order described above."""
         K = int(draws)
         if not 1 <= K <= DIVERSE_MAX_DRAWS:
             raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
         if method not in ("greedy", "sample"):
             raise ValueError("method must be 'greedy' or 'sample' (got %r)" % (method,))
+        if rerank not in ("likelihood", "marginal"):
+            raise ValueError("rerank must be 'likelihood' or 'marginal' (got %r)" % (rerank,))
         p = self.p
         max_len = int(max_len or p.gen_max_len)
         B = int(features.shape[0])
@@ -595,7 +752,7 @@ class CaptionGenerator(object):
             sl = slice(g0, min(B, g0 + G))
             r, c = self._diverse_pass(features[sl], c_v[sl] if c_v is not None else None, np.asarray(eps)[:, :, sl] if eps is not None else None,
                                       K, method, bos, eos, max_len, len_norm_f, n_best,
-                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every)
+                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every, rerank)
             res += r
             cands += c
         self.last_candidates = cands

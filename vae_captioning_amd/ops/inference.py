@@ -8,8 +8,11 @@ always decoded with `online_inference`, as in the reference.  `sample_gen == "di
 `diverse_inference`; `./val_{gen_name}.json` keeps the COCO shape with each image's top caption and
 `./val_{gen_name}_diverse.json` holds the full per-image lists (captions, scores, counts).  With `params.diverse_rerank ==
 "consensus"` (a `consensus.ConsensusIndex` attached to the decoder) the top caption is the consensus winner and the lists also hold
-the consensus scores."""
+the consensus scores; with `"marginal"` they hold each caption's likelihood over all of the image's draws.
+`params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
+(`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed."""
 import json
+import math
 import os
 
 import numpy as np
@@ -29,6 +32,28 @@ def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
     if allow_beam and params.sample_gen == "beam_search":
         return decoder.beam_search(sess, ids, images, placeholder, c_v, beam_size=params.beam_size)
     return decoder.online_inference(sess, ids, images, placeholder, c_v=c_v)[0]
+
+
+def human_captions(captions, lengths):
+    """One validation item's captions as score() takes them: caption c of image b is lab[b, c, :lens[b, c]] (the `w.. <EOS>` label row;
+    lab[b, :lens[b]] where the generator yields one caption per image); rows of length 0 (images with fewer captions) are skipped."""
+    lab = np.asarray(captions[1])
+    lens = np.asarray(lengths)
+    if lab.ndim == 2:
+        lab, lens = lab[:, None, :], lens.reshape(-1, 1)
+    return [[lab[b, c, :int(lens[b, c])].tolist() for c in range(lab.shape[1]) if int(lens[b, c]) > 0] for b in range(lab.shape[0])]
+
+
+def perplexity(score_records):
+    """exp(-sum marginal / sum tokens) over every scored caption (nan when nothing was scored)"""
+    caps = [c for r in score_records for c in r["captions"]]
+    n = sum(c["tokens"] for c in caps)
+    return math.exp(-sum(c["marginal"] for c in caps) / n) if n else float("nan")
+
+
+def store_scores(params, score_records):
+    _store("./val_{}_scores.json".format(params.gen_name), score_records)
+    print("Held-out perplexity of the human captions under %d prior draws: %.17g" % (params.score_draws, perplexity(score_records)))
 
 
 def _store(path, records):
@@ -55,9 +80,14 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
     if not params.fine_tune:
         print("Captioning from precomputed fc2 features; pass --fine_tune to run the fine-tuned VGG16 on the images.")
     val_cv = params.use_c_v or params.prior in ("GMM", "AG")
-    records = []
-    for images, _caps, _lens, ids, c_v in val_gen.next_val_batch(get_image_ids=True, use_obj_vectors=params.use_c_v):
+    records, scores = [], []
+    n_score = int(getattr(params, "score_draws", 0) or 0)
+    for images, caps, lens, ids, c_v in val_gen.next_val_batch(get_image_ids=True, use_obj_vectors=params.use_c_v):
         records += _decode(decoder, params, sess, image_f_inputs, ids, images, _cluster_rows(c_v, val_cv), allow_beam=True)
+        if n_score:
+            scores += decoder.score_captions(ids, images, human_captions(caps, lens), _cluster_rows(c_v, val_cv), draws=n_score)
+    if n_score:
+        store_scores(params, scores)
     if params.sample_gen == "diverse":
         _store("./val_{}_diverse.json".format(params.gen_name), records)
         records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]

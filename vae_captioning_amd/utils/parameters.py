@@ -26,6 +26,7 @@ _DEFAULTS = dict(
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
+    score_draws=0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -46,8 +47,8 @@ _FLAGS = [
     ("--features_pickle", "features_pickle", str, None), ("--cluster_pickle", "cluster_pickle", str, None),
     ("--ckpt_format", "ckpt_format", str, ["tf", "npz"]),
     ("--diverse_draws", "diverse_draws", int, None), ("--diverse_method", "diverse_method", str, ["greedy", "sample"]),
-    ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus"]), ("--consensus_k", "consensus_k", int, None),
-    ("--consensus_m", "consensus_m", int, None),
+    ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal"]), ("--consensus_k", "consensus_k", int, None),
+    ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -57,10 +58,12 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--ckpt_format": "tf = TensorFlow V2 checkpoint files (what tf.train.Saver writes), npz = numpy archive",
          "--diverse_draws": "--sample_gen diverse: latent draws per image (1..256; default 20)",
          "--diverse_method": "--sample_gen diverse: decoding of each draw (greedy or sample; default greedy)",
-         "--diverse_rerank": "--sample_gen diverse: order of each image's captions (likelihood, or consensus with the captions of its "
-                             "nearest training images; default likelihood)",
+         "--diverse_rerank": "--sample_gen diverse: order of each image's captions (likelihood, consensus with the captions of its "
+                             "nearest training images, or marginal: the likelihood over all of the image's draws; default likelihood)",
          "--consensus_k": "--diverse_rerank consensus: nearest training images per image (1..256; default 90)",
-         "--consensus_m": "--diverse_rerank consensus: best-matching pool captions averaged per candidate (>= 1; default 125)"}
+         "--consensus_m": "--diverse_rerank consensus: best-matching pool captions averaged per candidate (>= 1; default 125)",
+         "--score_draws": "--mode inference: also score the validation images' human captions under this many prior draws and write "
+                          "./val_{gen_name}_scores.json (0..256; default 0 = off)"}
 
 
 class Parameters(object):
@@ -96,6 +99,8 @@ class Parameters(object):
             ap.error("--consensus_k must be 1..256 (got %d)" % self.consensus_k)
         if self.consensus_m < 1:
             ap.error("--consensus_m must be >= 1 (got %d)" % self.consensus_m)
+        if not 0 <= self.score_draws <= 256:
+            ap.error("--score_draws must be 0..256 (got %d)" % self.score_draws)
         if self.synthetic:
             self.vocab_size = int(args["vocab"]) if args["vocab"] is not None else 10000
         self.hdf5_file = self.coco_dir + os.path.basename(self.hdf5_file)  # the image array lives next to the data set

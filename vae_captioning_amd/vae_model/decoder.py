@@ -98,19 +98,22 @@ class Decoder(object):
         cap_list: per image {"image_id", "caption": the best text, "captions": [texts], "scores": [...], "counts": [...]}.
         params.diverse_rerank == "consensus": every distinct caption is re-ranked by its consensus against the attached
         `consensus_index` (consensus.py) before n_best cuts the list; the records gain "consensus" (aligned with "captions") and
-        "caption" is the consensus winner."""
+        "caption" is the consensus winner.  params.diverse_rerank == "marginal": the distinct captions are ordered by their likelihood
+        over ALL draws of the image (generate.py: diverse(rerank="marginal")); "scores" are those scores and the records gain "marginal"
+        (aligned with "captions")."""
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
         draws = int(draws if draws is not None else self.params.diverse_draws)
         method = method if method is not None else self.params.diverse_method
         consensus = getattr(self.params, "diverse_rerank", "likelihood") == "consensus"
+        marginal = getattr(self.params, "diverse_rerank", "likelihood") == "marginal"
         if consensus and self.consensus_index is None:
             raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
                                "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
         feats = self._features(in_pictures)
         res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus else n_best,
-                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood")
         if consensus:
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
         cap_list = []
@@ -120,5 +123,19 @@ class Decoder(object):
                    "scores": [float(e[1]) for e in entries], "counts": [int(e[2]) for e in entries]}
             if consensus:
                 rec["consensus"] = [float(e[3]) for e in entries]
+            if marginal:
+                rec["marginal"] = [float(e[3]) for e in entries]
             cap_list.append(rec)
         return cap_list
+
+    def score_captions(self, picture_ids, in_pictures, captions, c_v=None, draws=None):
+        """Held-out likelihood of given captions (generate.py: score): captions[b] = token-id lists of image b (with or without <BOS>; the
+        <EOS> counts when present), scored under `draws` (params.score_draws) prior draws.  Returns per image {"image_id", "captions":
+        [{"tokens": n, "marginal": log 1/K sum_k p(caption | z_k, image), "logprob": mean over the draws of log p(caption | z_k, image)}]}."""
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        draws = int(draws if draws is not None else self.params.score_draws)
+        res = self._gen().score(self._features(in_pictures), captions, use_cv, None, bos, eos, draws=draws)
+        return [{"image_id": pid, "captions": [{"tokens": int(r["tokens"]), "marginal": float(r["marginal"]), "logprob": float(np.mean(r["logprob"]))}
+                                               for r in rs]} for pid, rs in zip(picture_ids, res)]
