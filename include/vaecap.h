@@ -455,6 +455,21 @@ int vc_beam_update(void* stream, int B, int beam, int Lmax, int eos, double len_
                    int32_t* p_len, const int32_t* sent_cur, int32_t* sent_next, double* c_score, double* c_logprob,
                    int32_t* c_len, int32_t* c_slot, int32_t* c_free, int32_t* c_sent, int32_t* parent, int32_t* tok);
 
+/* Group ("diverse") beam search bookkeeping after one decoder step (Diverse Beam Search, Vijayakumar et al. 2016, Hamming
+ * dissimilarity): every image has `groups` beam searches of width w, one wave per image running its groups IN ORDER; a word that c live
+ * beams of the round's earlier groups have just taken costs a candidate diversity * c of its heap key (rounded product, then rounded
+ * difference; c == 0 leaves the key alone).  Per live beam the first w of its kc candidates under (key descending, raw rank ascending)
+ * are walked like vc_beam_update walks a row.  The stored logprob stays the model's; <EOS> candidates are scored without the penalty.
+ * The state is vc_beam_update's for B*groups "virtual images" v = b*groups + g of beam w (vc_beam_init with B*groups images):
+ *   top_p / top_i [B*groups*w, kc], kc = min(groups*w, vocabulary) >= w; rows, heaps [B*groups, w]; pool c_sent [B*groups, w+1, Lmax];
+ *   pcount / ccount / c_free [B*groups]; parent / tok [B*groups*w].  groups*w <= 16; diversity finite and >= 0.
+ * groups == 1 is vc_beam_update(beam = w) move for move; diversity == 0 makes every group of an image the same search. */
+int vc_beam_update_groups(void* stream, int B, int groups, int w, int kc, int Lmax, int eos, double len_norm_f, double diversity,
+                          const float* top_p, const int32_t* top_i, int32_t* pcount, int32_t* ccount, double* p_score,
+                          double* p_logprob, int32_t* p_len, const int32_t* sent_cur, int32_t* sent_next, double* c_score,
+                          double* c_logprob, int32_t* c_len, int32_t* c_slot, int32_t* c_free, int32_t* c_sent, int32_t* parent,
+                          int32_t* tok);
+
 /* The state vc_beam_update starts from, in ONE launch (vae_model/decoder.py:238-247: partial = [Beam([bos], state, 0.0, 0.0)], complete
  * empty): pcount = 1, ccount = 0, p_score = p_logprob = 0, p_len = 1, every sent_cur token = bos, sent_next / c_* / c_sent = 0,
  * c_free = 2^(beam+1)-1, parent[r] = r, tok[r] = bos, and the images' LSTM state expanded to the beam rows:

@@ -252,6 +252,10 @@ def main(params):
                 sent = decoder.diverse_inference(None, ids, pics, None, c_v)
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (x%d)" % (t, n) for t, n in zip(r["captions"], r["counts"]))))
+            elif params.sample_gen == "diverse_beam":   # group beam search: the groups' captions merged, best first
+                sent = decoder.diverse_beam_search(None, ids, pics, None, c_v)
+                for r in sent:
+                    say("%s: %s" % (r["image_id"], " | ".join("%s (groups %s)" % (t, ",".join(map(str, g))) for t, g in zip(r["captions"], r["groups"]))))
             elif params.sample_gen == "beam_search":
                 sent = decoder.beam_search(None, ids, pics, None, c_v, beam_size=params.beam_size)
             else:
@@ -264,7 +268,7 @@ def main(params):
         if rank == 0:
             with open("./val_{}.json".format(params.gen_name), "w") as wj:
                 json.dump(captions_gen, wj)
-            if params.sample_gen == "diverse":   # the full per-image lists under the name ops/inference.py gives them
+            if params.sample_gen in ("diverse", "diverse_beam"):   # the full per-image lists under the name ops/inference.py gives them
                 with open("./val_{}_diverse.json".format(params.gen_name), "w") as wj:
                     json.dump(captions_gen, wj)
             if params.score_draws:

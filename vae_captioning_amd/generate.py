@@ -118,6 +118,25 @@ def rerank_by_marginal(entries, marginals, eos, len_norm_f):
     return sorted(new, key=lambda x: (not (len(x[0]) > 0 and x[0][-1] == eos), -x[1]))
 
 
+def merge_groups(groups):
+    """diverse_beam_search's per-image result (a list of G lists of (tokens, score)) as ONE ranked list of distinct captions:
+    [(tokens, score, [groups that produced it]), ...], equal token sequences merged under their best score, score descending (ties
+    keep the order of first appearance: group by group, each best first)."""
+    best, order = {}, []
+    for g, beams in enumerate(groups):
+        for toks, score in beams:
+            key = tuple(toks)
+            if key not in best:
+                best[key] = [list(toks), score, [g]]
+                order.append(key)
+            else:
+                ent = best[key]
+                ent[1] = max(ent[1], score)
+                if g not in ent[2]:
+                    ent[2].append(g)
+    return sorted((tuple(best[k]) for k in order), key=lambda x: -x[1])
+
+
 class CaptionGenerator(object):
     def __init__(self, engine):
         self.e = engine
@@ -759,15 +778,22 @@ class CaptionGenerator(object):
         return res
 
     # ------------------------------------------------------------------ beam search
-    def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused):
+    def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups=None):
         """The persistent device state of one slice of images (vae_model/decoder.py:238-247) and its round function.  A call decodes its
         images as `nparts` independent slices on `nparts` streams (beam_search): buffers are per (slice, beam width, length) and a
-        captured chunk of rounds bakes their addresses."""
+        captured chunk of rounds bakes their addresses.
+        groups = (G, diversity): group beam search (diverse_beam_search).  c, h then hold one row per "virtual image" b*G + g, a beam
+        search of width n of its own; a row has kc = min(G*n, V) candidates and the round's bookkeeping is vc_beam_update_groups."""
         lib, e = self.lib, self.e
         B, Hd, V = int(c.shape[0]), self.p.decoder_hidden, e.V
         M, dev = B * n, e.dev
         i32, f64 = torch.int32, torch.float64
         tag = "bm%d_%d_%dof%d_" % (n, L, k, nparts)
+        kc = n
+        if groups is not None:
+            G, lam = int(groups[0]), float(groups[1])
+            kc = min(G * n, V)
+            tag = "bmg%d_%r_" % (G, lam) + tag   # (per setting: a captured chunk of one setting is never replayed for another)
         pt = types.SimpleNamespace(B=B, M=M, k=k)
         # everything the host reads at the end lives in TWO flat buffers (int32 fields, float64 scores): two copies into pinned memory
         # bring a slice's results back, with no gathering launches in between
@@ -782,7 +808,7 @@ class CaptionGenerator(object):
         p_score, c_score, p_logprob, c_logprob = dbuf[0:M], dbuf[M:2 * M], dbuf[2 * M:3 * M], dbuf[3 * M:4 * M]
         c_free = self._b(tag + "c_free", (B,), i32)
         parent, tok = self._b(tag + "parent", (M,), i32), self._b(tag + "tok", (M,), i32)
-        tv, ti = self._b(tag + "tv", (M, n)), self._b(tag + "ti", (M, n), i32)
+        tv, ti = self._b(tag + "tv", (M, kc)), self._b(tag + "ti", (M, kc), i32)
         bufs = self._round_bufs(tag, M)
         # re-initialised per call: partial = [Beam([bos], state b, 0.0, 0.0)], and every row starts from its image's state (the [B, Hd]
         # state expanded to the M rows, parent = identity) -- one launch
@@ -798,13 +824,16 @@ class CaptionGenerator(object):
             lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent), M, Hd, P(cg), P(hg), P(xproj), P(tok), V, 4 * Hd, P(bufs["gact"]))
             if fused:   # softmax + top-k in one read of the logits (vc_softmax_topk_rows_f32: bit-identical to the two calls)
                 logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
-                lib.vc_softmax_topk_rows_f32(s_, P(logits), M, V, V, n, P(tv), P(ti))
+                lib.vc_softmax_topk_rows_f32(s_, P(logits), M, V, V, kc, P(tv), P(ti))
             else:
                 probs, _, _ = self.step(tok, cg, hg, bufs=bufs, timed=timed, projected=xproj is not None)
-                lib.vc_topk_rows_f32(s_, P(probs), M, V, V, n, P(tv), P(ti))
-            lib.vc_beam_update(s_, B, n, L, int(eos), float(len_norm_f), P(tv), P(ti), P(pcount), P(ccount), P(p_score), P(p_logprob),
-                               P(p_len), P(sent[it & 1]), P(sent[1 - (it & 1)]), P(c_score), P(c_logprob), P(c_len), P(c_slot),
-                               P(c_free), P(c_sent), P(parent), P(tok))
+                lib.vc_topk_rows_f32(s_, P(probs), M, V, V, kc, P(tv), P(ti))
+            state = (P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len), P(sent[it & 1]), P(sent[1 - (it & 1)]), P(c_score), P(c_logprob),
+                     P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
+            if groups is None:
+                lib.vc_beam_update(s_, B, n, L, int(eos), float(len_norm_f), P(tv), P(ti), *state)
+            else:   # the G groups of an image in order inside one wave, each penalised by the words the earlier ones have just taken
+                lib.vc_beam_update_groups(s_, B // G, G, n, kc, L, int(eos), float(len_norm_f), lam, P(tv), P(ti), *state)
 
         def chunk_fn():
             for r in range(K):
@@ -813,7 +842,8 @@ class CaptionGenerator(object):
 
         pt.one, pt.chunk_fn, pt.alive, pt.pcount = one, chunk_fn, alive, pcount
         # (the key names the engine's workspace: recomputed before the capture, since the eager rounds of a first call may grow it)
-        pt.key_fn = lambda: self._graph_key("beam", B, n, L, K, int(eos), float(len_norm_f),
+        kind = ("beam",) if groups is None else ("beam_groups", G, kc, lam)
+        pt.key_fn = lambda: self._graph_key(*kind, B, n, L, K, int(eos), float(len_norm_f),
                                             tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot,
                                                      c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M)] + list(bufs.values()))
         pt.key = pt.key_fn()
@@ -835,17 +865,46 @@ class CaptionGenerator(object):
         ones (state gather, LSTM step, top-k, the heap bookkeeping: together half the round's time at 640 rows, on a fraction of
         the CUs).  A batch of >= 512 rows is therefore decoded as TWO slices of images on two streams: while one slice is in its
         latency-bound kernels the other's logits product has the CUs.  VC_DECODE_SLICES=1 keeps one slice -- same beams."""
+        return self._beam_run(features, c_v, eps, bos, eos, int(beam_size), max_len, len_norm_f, check_every)
+
+    def diverse_beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, groups=5, group_size=2, diversity=0.5, max_len=None,
+                            len_norm_f=0.7, check_every=4):
+        """Group beam search (Diverse Beam Search, Vijayakumar et al. 2016, Hamming dissimilarity) for a batch of images: `groups`
+        beam searches of width `group_size` per image advance in lock step; within a round the groups run in order, and a word that
+        c live beams of the round's earlier groups have just taken costs a candidate diversity * c of its heap key (the stored
+        log-probability stays the model's; finished captions are scored without the penalty).  Returns per image a list of `groups`
+        lists of (sentence, score) in descending score order.  groups=1 is beam_search(beam_size=group_size); diversity=0 makes every
+        group that search.
+
+        The loop is beam_search's: rows [B, groups, group_size], groups * group_size candidates per row, and vc_beam_update_groups
+        for the bookkeeping (one wave per image, its groups in order) -- same graph replay, alive check and slices."""
+        G, w, lam = int(groups), int(group_size), float(diversity)
+        if G < 1 or w < 1 or G * w > 16:
+            raise ValueError("diverse_beam_search: groups * group_size must be 1..16, got %d x %d" % (G, w))
+        if not (lam >= 0.0 and lam < float("inf")):
+            raise ValueError("diverse_beam_search: diversity must be finite and >= 0, got %r" % (diversity,))
+        flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, groups=(G, lam))
+        return [flat[b * G:(b + 1) * G] for b in range(len(flat) // G)]
+
+    def _beam_run(self, features, c_v, eps, bos, eos, n, max_len, len_norm_f, check_every, groups=None):
+        """beam_search's loop over B * G "virtual images" of beam n (G = 1: beam_search itself; groups = (G, diversity): group beam
+        search, virtual image b*G + g = group g of image b).  Returns the virtual images' beams in order."""
         lib, e = self.lib, self.e
         max_len = max_len or self.p.gen_max_len
         t_ph = _phase("", 0.0)
         c, h = self.init_state(features, c_v, eps)
         t_ph = _phase("init_state", t_ph)
-        B, Hd, V, n = c.shape[0], self.p.decoder_hidden, e.V, int(beam_size)
+        B, Hd, V = c.shape[0], self.p.decoder_hidden, e.V
         tok0 = self._b("bm_tok0", (B,), torch.int32)
         tok0.fill_(bos)
         _, c, h = self.step(tok0, c, h, want="state", bufs=self._round_bufs("bm0_", B))  # :230-236 -- probabilities discarded, state kept
         L, rounds = max_len + 2, max_len - 1
-        fused = n <= 8
+        G = 1
+        if groups is not None:   # every group of an image starts from the image's state
+            G = int(groups[0])
+            c, h = c.repeat_interleave(G, 0), h.repeat_interleave(G, 0)
+            B *= G
+        fused = (n if groups is None else min(G * n, V)) <= 8   # (candidates per row: the fused softmax-top-k holds 8)
         # the words' input projections from a table (rows x rounds of lookups against ONE product over the vocabulary)
         xproj = self._project_vocab() if (B * n * rounds >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
         # Rounds run as hipGraph replays of K rounds each (nine launches per round otherwise): every buffer of a slice is persistent and
@@ -854,11 +913,11 @@ class CaptionGenerator(object):
         # them.  VC_DECODE_GRAPH=0 keeps the eager loop -- same kernels, same beams.
         K = int(check_every) if check_every and check_every % 2 == 0 else 4
         want = int(os.environ.get("VC_DECODE_SLICES", self.slices))
-        nparts = want if (want > 1 and B % want == 0 and B * n >= self.slice_rows * want and xproj is not None) else 1
+        nparts = want if (want > 1 and (B // G) % want == 0 and B * n >= self.slice_rows * want and xproj is not None) else 1
         nb = B // nparts
         if nparts > 1 and lib.vc_gemm_workspace_bytes(nb * n, V, Hd) != 0:
             nparts, nb = 1, B    # (a K-split logits product writes the engine's ONE workspace: slices on two streams would share it)
-        parts = [self._beam_part(k, nparts, c[k * nb:(k + 1) * nb], h[k * nb:(k + 1) * nb], n, L, rounds, K, bos, eos, len_norm_f, xproj, fused)
+        parts = [self._beam_part(k, nparts, c[k * nb:(k + 1) * nb], h[k * nb:(k + 1) * nb], n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups)
                  for k in range(nparts)]
         main = torch.cuda.current_stream()
         while len(self._side) < nparts - 1:

@@ -9,6 +9,8 @@ always decoded with `online_inference`, as in the reference.  `sample_gen == "di
 `./val_{gen_name}_diverse.json` holds the full per-image lists (captions, scores, counts).  With `params.diverse_rerank ==
 "consensus"` (a `consensus.ConsensusIndex` attached to the decoder) the top caption is the consensus winner and the lists also hold
 the consensus scores; with `"marginal"` they hold each caption's likelihood over all of the image's draws.
+`sample_gen == "diverse_beam"` (additive): group beam search (`decoder.diverse_beam_search`), written the same way: the merged ranked
+captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one in `./val_{gen_name}.json`.
 `params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
 (`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed."""
 import json
@@ -29,6 +31,8 @@ def _cluster_rows(c_v, wanted):
 def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
     if allow_beam and params.sample_gen == "diverse":
         return decoder.diverse_inference(sess, ids, images, placeholder, c_v)
+    if allow_beam and params.sample_gen == "diverse_beam":
+        return decoder.diverse_beam_search(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "beam_search":
         return decoder.beam_search(sess, ids, images, placeholder, c_v, beam_size=params.beam_size)
     return decoder.online_inference(sess, ids, images, placeholder, c_v=c_v)[0]
@@ -88,7 +92,7 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
             scores += decoder.score_captions(ids, images, human_captions(caps, lens), _cluster_rows(c_v, val_cv), draws=n_score)
     if n_score:
         store_scores(params, scores)
-    if params.sample_gen == "diverse":
+    if params.sample_gen in ("diverse", "diverse_beam"):
         _store("./val_{}_diverse.json".format(params.gen_name), records)
         records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]
     _store("./val_{}.json".format(params.gen_name), records)

@@ -26,7 +26,7 @@ _DEFAULTS = dict(
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
-    score_draws=0,
+    score_draws=0, beam_groups=5, beam_diversity=0.5,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -49,6 +49,7 @@ _FLAGS = [
     ("--diverse_draws", "diverse_draws", int, None), ("--diverse_method", "diverse_method", str, ["greedy", "sample"]),
     ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal"]), ("--consensus_k", "consensus_k", int, None),
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
+    ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -63,7 +64,11 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--consensus_k": "--diverse_rerank consensus: nearest training images per image (1..256; default 90)",
          "--consensus_m": "--diverse_rerank consensus: best-matching pool captions averaged per candidate (>= 1; default 125)",
          "--score_draws": "--mode inference: also score the validation images' human captions under this many prior draws and write "
-                          "./val_{gen_name}_scores.json (0..256; default 0 = off)"}
+                          "./val_{gen_name}_scores.json (0..256; default 0 = off)",
+         "--beam_size": "beams per image (default 10); --sample_gen diverse_beam: the total over the groups, a multiple of --beam_groups, <= 16",
+         "--beam_groups": "--sample_gen diverse_beam: groups per image, each a beam search of beam_size / beam_groups beams (default 5)",
+         "--beam_diversity": "--sample_gen diverse_beam: what a word costs a candidate per live beam of the round's earlier groups that "
+                             "has just taken it (>= 0; default 0.5)"}
 
 
 class Parameters(object):
@@ -101,6 +106,15 @@ class Parameters(object):
             ap.error("--consensus_m must be >= 1 (got %d)" % self.consensus_m)
         if not 0 <= self.score_draws <= 256:
             ap.error("--score_draws must be 0..256 (got %d)" % self.score_draws)
+        if self.sample_gen == "diverse_beam":
+            if self.beam_groups < 1:
+                ap.error("--beam_groups must be >= 1 (got %d)" % self.beam_groups)
+            if not 1 <= self.beam_size <= 16:
+                ap.error("--beam_size must be 1..16 with --sample_gen diverse_beam (got %d)" % self.beam_size)
+            if self.beam_size % self.beam_groups:
+                ap.error("--beam_size must be divisible by --beam_groups (got %d and %d)" % (self.beam_size, self.beam_groups))
+            if not (0.0 <= self.beam_diversity < float("inf")):
+                ap.error("--beam_diversity must be finite and >= 0 (got %r)" % self.beam_diversity)
         if self.synthetic:
             self.vocab_size = int(args["vocab"]) if args["vocab"] is not None else 10000
         self.hdf5_file = self.coco_dir + os.path.basename(self.hdf5_file)  # the image array lives next to the data set

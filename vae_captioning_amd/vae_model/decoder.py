@@ -128,6 +128,33 @@ class Decoder(object):
             cap_list.append(rec)
         return cap_list
 
+    def diverse_beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, beam_size=None, groups=None, diversity=None,
+                            len_norm_f=0.7):
+        """Group beam search (Diverse Beam Search; generate.py: diverse_beam_search): `groups` (params.beam_groups) beam searches of
+        beam_size / groups beams per image (params.beam_size in all), a word costing a candidate `diversity` (params.beam_diversity)
+        per live beam of the round's earlier groups that has just taken it.  Equal captions of different groups are merged under
+        their best score and ranked.  Returns cap_list in diverse_inference's record shape: per image {"image_id", "caption": the
+        best text, "captions": [texts], "scores": [...], "counts": [groups that produced the caption], "groups": [[group ids]]}."""
+        from ..generate import merge_groups
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        total = int(beam_size if beam_size is not None else self.params.beam_size)
+        G = int(groups if groups is not None else self.params.beam_groups)
+        lam = float(diversity if diversity is not None else self.params.beam_diversity)
+        if G < 1 or total < G or total % G or total > 16:
+            raise ValueError("diverse_beam_search: beam_size must be a multiple of groups and at most 16 (got %d and %d)" % (total, G))
+        res = self._gen().diverse_beam_search(self._features(in_pictures), use_cv, None, bos, eos, groups=G, group_size=total // G,
+                                              diversity=lam, max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+        cap_list = []
+        for pid, per_group in zip(picture_ids, res):
+            entries = merge_groups(per_group)
+            texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
+            cap_list.append({"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
+                             "scores": [float(e[1]) for e in entries], "counts": [len(e[2]) for e in entries],
+                             "groups": [[int(g) for g in e[2]] for e in entries]})
+        return cap_list
+
     def score_captions(self, picture_ids, in_pictures, captions, c_v=None, draws=None):
         """Held-out likelihood of given captions (generate.py: score): captions[b] = token-id lists of image b (with or without <BOS>; the
         <EOS> counts when present), scored under `draws` (params.score_draws) prior draws.  Returns per image {"image_id", "captions":
