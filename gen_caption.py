@@ -5,6 +5,7 @@
     python gen_caption.py --img_path cat.jpg --checkpoint ./checkpoints/last_run.ckpt \\
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
         [--gen_method greedy|beam_search|sample|diverse] [--beam_size 2] [--diverse_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
+        [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
 VGG16 fc2 features [1, 4096], imf_emb -> decoder (prior z) -> greedy / beam search, print the caption.
@@ -116,9 +117,15 @@ class Generator(object):
         fc2 = self._vgg.forward(torch.from_numpy(x).cuda())
         return fc2.cpu().numpy(), img
 
-    def generate_caption(self, img_path, beam_size=2, diverse_draws=None):
+    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
-        "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first."""
+        "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
+        the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
+        the params unless given."""
+        if top_k is not None:
+            self.params.top_k = int(top_k)
+        if top_p is not None:
+            self.params.top_p = float(top_p)
         from vae_captioning_amd.vae_model.decoder import Decoder
         if not img_path or not os.path.exists(img_path):
             raise ValueError("Image not found")
@@ -149,12 +156,19 @@ if __name__ == "__main__":
     parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size")
     parser.add_argument("--vgg_weights", default=None, help="vgg16_weights.npz for the feature extractor (additive flag)")
     parser.add_argument("--diverse_draws", type=int, default=None, help="--gen_method diverse: latent draws (default: the params' diverse_draws)")
+    parser.add_argument("--top_k", type=int, default=None, help="sampled decoding: draw from the k most likely words (0 = all; default: the params')")
+    parser.add_argument("--top_p", type=float, default=None, help="sampled decoding: draw from the nucleus holding this share of the probability "
+                                                                  "((0, 1], 1 = all; default: the params')")
     args = parser.parse_args()
+    if args.top_k is not None and args.top_k < 0:
+        parser.error("--top_k must be >= 0 (got %d)" % args.top_k)
+    if args.top_p is not None and not (0.0 < args.top_p <= 1.0):
+        parser.error("--top_p must be in (0, 1] (got %r)" % args.top_p)
     if args.gpu != "":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
                           gen_method=args.gen_method, vgg_weights=args.vgg_weights)
-    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws)
+    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

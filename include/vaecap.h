@@ -37,6 +37,7 @@ extern "C" {
  *      vc_topk_rows_wide_workspace_bytes / vc_ngram_vectors / vc_consensus_score.
  *      Added within 4 (additive, no layout change): the caption-scoring entries vc_logits_logprob_f32 /
  *      vc_logits_logprob_workspace_bytes / vc_score_reduce_f64.
+ *      Added within 4 (additive, no layout change): the truncated-sampling entry vc_decode_pick_trunc_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -499,6 +500,15 @@ int vc_eos_track_i32(void* stream, const int32_t* tok, int B, int eos, int32_t* 
  *                    partition and expressions: the same token); round NULL = 0, clamped to u_rounds - 1.  For rows with done[r] == 0 the
  *                    token is appended to seq [rows, Lmax] at len[r] (< Lmax), logprob[r] += its log-softmax at temperature 1 (f32 term,
  *                    f64 sum), len[r] += 1, and done[r] = (tok == eos).
+ *   decode_pick_trunc decode_pick's sampled round with the distribution truncated before the draw (u is required).  y = fl32(x / temperature as
+ *                    x * (1.0f / temperature)); order = y descending, equal y by lower index.  top_k > 0: only the first top_k words of
+ *                    the order (0 or >= V: all).  top_p < 1: inside that set, the shortest prefix of the order whose mass
+ *                    sum exp(y - max y) is >= top_p * the set's mass (at least one word; 1 = the whole set).  The draw is the inverse CDF
+ *                    over the kept words in index order with target = u * their mass: the lowest-index kept word whose running kept
+ *                    mass exceeds the target (else the last kept word).  Masses are summed as integers (multiples of 2^-32): the token
+ *                    does not depend on rows, on the row's place in the launch or on the call.  logprob is decode_pick's: the
+ *                    log-softmax at temperature 1 over the FULL vocabulary (the model's likelihood, not the sampler's).  kept (NULL or
+ *                    [rows]): the number of words kept.  top_k 0 / >= V with top_p 1 is decode_pick itself, bit for bit.
  *   decode_round_end pending[0] = rows with done == 0 (float); round[0] += 1 when round is not NULL.  One workgroup.
  *   diverse_rank     per image (one workgroup, K <= 256, rows == B*K): score = logprob / (1 + len)^len_norm_f; candidates with equal token
  *                    sequences merged (best score kept, ties: lower draw); ranked <EOS>-ended first, then score descending, then lower
@@ -508,6 +518,9 @@ int vc_diverse_latent_f32(void* stream, long rows, int K, int S, int L, const fl
                           uint64_t offset, const int32_t* step, float* z);
 int vc_decode_pick_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, const float* u, int u_rounds,
                        const int32_t* round, int eos, int32_t* tok, int32_t* done, int32_t* seq, int Lmax, int32_t* len, double* logprob);
+int vc_decode_pick_trunc_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, int top_k, float top_p,
+                             const float* u, int u_rounds, const int32_t* round, int eos, int32_t* tok, int32_t* done, int32_t* seq, int Lmax,
+                             int32_t* len, double* logprob, int32_t* kept);
 int vc_decode_round_end_i32(void* stream, const int32_t* done, long rows, float* pending, int32_t* round);
 int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32_t* seq, const int32_t* len, const int32_t* ended,
                     const double* logprob, double len_norm_f, int32_t* n_distinct, int32_t* rep, int32_t* count, double* score);

@@ -12,6 +12,7 @@ run $B
 run $B --restore
 run $B --mode inference --sample_gen beam_search --gen_name bs
 run $B --mode inference --sample_gen sample --temperature 0.7 --gen_name sm
+run $B --mode inference --sample_gen sample --temperature 1.2 --top_k 50 --top_p 0.9 --gen_name smt
 run $B --fine_tune --bs 2 --save_params
 run $B --fine_tune --bs 2 --mode inference --gen_name ft
 ls

@@ -7,6 +7,8 @@
 //                            argmax_rows_kernel) or the inverse-CDF draw with multinomial_rows_kernel's 256-chunk partition (same
 //                            expressions, same order: same token), plus the token's log-softmax at temperature 1 accumulated into the
 //                            row's candidate (sequence, length, float64 log-likelihood, <EOS> flag)
+//   vc_decode_pick_trunc_f32 the same round with the distribution truncated before the draw: the top_k best words and / or the smallest
+//                            set of best words holding a share top_p of the probability, found by a radix select (no sort of V words)
 //   vc_decode_round_end_i32  pending = rows without <EOS>, round += 1 (the device round counter keys the next round's uniforms)
 //   vc_diverse_rank          one workgroup per image: scores, 64-bit hashes confirmed by full compares, duplicates merged, ranked
 #include "common.h"
@@ -134,6 +136,225 @@ __global__ __launch_bounds__(256) void decode_pick_kernel(const float* __restric
     }
 }
 
+// ---- truncated pick (top-k / nucleus).  Order: descending y = fl32(x * inv_temp), equal y by lower index.  Everything the selection
+// decides on is an integer: the order-preserving 32-bit image of y (the key) and the word's mass exp(y - max y) rounded to a multiple of
+// 2^-32 (sums of integers are exact: no result depends on the order in which LDS atomics or partial sums arrive).
+__device__ __forceinline__ uint32_t pick_key(float x, float inv_temp) {
+    uint32_t b = __float_as_uint(__fmul_rn(x, inv_temp));
+    if ((b << 1) == 0u) b = 0u;   // -0 == +0
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+__device__ __forceinline__ unsigned long long key_mass(uint32_t k, float my) {
+    return __float2ull_rn(__expf(key_value(k) - my) * 4294967296.0f);   // <= 2^32 per word: 2^31 words stay below 2^63
+}
+__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int o) {
+    const uint32_t lo = __shfl_up((uint32_t)v, o, 64), hi = __shfl_up((uint32_t)(v >> 32), o, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// inclusive prefix sum over the 256 threads (thread order); total in every thread
+__device__ __forceinline__ unsigned long long block_scan_u64(unsigned long long v, unsigned long long* ws /* 4 */, unsigned long long& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long n = shfl_up_u64(v, o);
+        if (lane >= o) v += n;
+    }
+    __syncthreads();
+    if (lane == 63) ws[w] = v;
+    __syncthreads();
+    unsigned long long base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i < w) base += ws[i];
+        tot += ws[i];
+    }
+    total = tot;
+    return v + base;
+}
+
+constexpr int PICK_HIST_COPIES = 4;   // a bin's copies sit side by side (other LDS banks): lanes t, t + 4, ... share one, not all 64
+struct PickSel {
+    unsigned long long hist[256 * PICK_HIST_COPIES];
+    unsigned long long ws[4];
+    unsigned long long above;
+    int bin, found;
+};
+
+// MSB-first radix select, 8 bits per pass, over the words with key > lo: the key T at which the running quantity (MASS: the words' masses,
+// else their number), summed from the best word down, first reaches thr; above = the quantity of the keys > T.  false: the eligible
+// words together stay below thr.  Each pass: a 256-bin histogram of the words that share the prefix found so far, scanned from the top.
+template <bool MASS>
+__device__ bool radix_select(const float* p, int V, float inv_temp, float my, long long lo, double thr, PickSel& S, uint32_t& T,
+                             unsigned long long& above) {
+    const int t = threadIdx.x;
+    uint32_t prefix = 0;
+    unsigned long long ab = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+#pragma unroll
+        for (int i = 0; i < PICK_HIST_COPIES; ++i) S.hist[t + 256 * i] = 0;
+        if (t == 0) { S.found = 0; S.bin = 0; S.above = ab; }
+        __syncthreads();
+        for (int c = t; c < V; c += 256) {
+            const uint32_t k = pick_key(p[c], inv_temp);
+            const bool in = pass == 0 || (k >> (shift + 8)) == prefix;
+            if ((long long)k > lo && in) atomicAdd(&S.hist[((k >> shift) & 255u) * PICK_HIST_COPIES + (t & (PICK_HIST_COPIES - 1))], MASS ? key_mass(k, my) : 1ull);
+        }
+        __syncthreads();
+        unsigned long long v = 0;   // thread t holds the t-th bin from the top
+#pragma unroll
+        for (int i = 0; i < PICK_HIST_COPIES; ++i) v += S.hist[(255 - t) * PICK_HIST_COPIES + i];
+        unsigned long long tot;
+        const unsigned long long incl = block_scan_u64(v, S.ws, tot);
+        if ((double)(ab + incl) >= thr && !((double)(ab + incl - v) >= thr)) { S.bin = 255 - t; S.above = ab + incl - v; S.found = 1; }
+        __syncthreads();
+        const bool found = S.found != 0;
+        prefix = (prefix << 8) | (uint32_t)S.bin;
+        ab = S.above;
+        __syncthreads();
+        if (!found && pass == 0) return false;
+    }
+    T = prefix;
+    above = ab;
+    return true;
+}
+
+// how many of the equal words of mass m at the cut are needed for above + j * m >= thr (1 <= j <= cap)
+__device__ __forceinline__ long tie_count(double thr, unsigned long long above, unsigned long long m, long cap) {
+    long j = m ? (long)ceil((thr - (double)above) / (double)m) : 1;
+    j = max(1l, min(j, cap));
+    while (j > 1 && (double)(above + (unsigned long long)(j - 1) * m) >= thr) --j;
+    while (j < cap && (double)(above + (unsigned long long)j * m) < thr) ++j;
+    return j;
+}
+
+// One workgroup per row, the row staged in LDS (STAGE) or re-read.  top_k in (0, V) and / or top_p < 1 (the entry dispatches the rest).
+template <bool STAGE>
+__global__ __launch_bounds__(256) void decode_pick_trunc_kernel(const float* __restrict__ logits, long rows, int V, long ld, float inv_temp,
+                                                                int top_k, float top_p, const float* __restrict__ u, int u_rounds,
+                                                                const int32_t* __restrict__ round, int eos, int32_t* __restrict__ tok,
+                                                                int32_t* __restrict__ done, int32_t* __restrict__ seq, int Lmax,
+                                                                int32_t* __restrict__ len, double* __restrict__ logprob,
+                                                                int32_t* __restrict__ kept) {
+    extern __shared__ float srow[];
+    __shared__ PickSel S;
+    __shared__ float sh[4];
+    __shared__ int s_tok, s_last;
+    const long r = blockIdx.x;
+    const int t = threadIdx.x;
+    const float* p = logits + r * ld;
+    if (STAGE) {
+        for (int c = t; c < V; c += 256) srow[c] = p[c];
+        __syncthreads();
+        p = srow;
+    }
+    if (t == 0) { s_tok = -1; s_last = 0; }
+    const int per = (V + 255) / 256;
+    const int c0 = t * per, c1 = min(V, c0 + per);   // decode_pick_kernel's partition: contiguous chunks in index order
+    float bv = -INFINITY;
+    for (int c = t; c < V; c += 256) bv = fmaxf(bv, p[c]);
+    const float mx1 = block_max<256>(bv, sh);
+    float s1 = 0.f;
+    for (int c = c0; c < c1; ++c) s1 += __expf(p[c] - mx1);   // (decode_pick_kernel's sum: the same log-softmax bits)
+    s1 = block_sum<256>(s1, sh);
+    const float my = key_value(pick_key(mx1, inv_temp));   // max y (the scaling is monotone)
+
+    // ---- the cut: words with key > T are kept, and the first j (index order) of the words with key == T
+    uint32_t T = 0;
+    long j = 1, jcap = V;
+    long long lo = -1;
+    unsigned long long ab;
+    const bool by_k = top_k > 0 && top_k < V;
+    if (by_k) {
+        radix_select<false>(p, V, inv_temp, my, -1, (double)top_k, S, T, ab);
+        j = jcap = (long)top_k - (long)ab;
+        lo = (long long)T;
+    }
+    if (top_p < 1.0f) {
+        unsigned long long z = 0, zk;
+        for (int c = t; c < V; c += 256) {
+            const uint32_t k = pick_key(p[c], inv_temp);
+            if ((long long)k > lo) z += key_mass(k, my);
+        }
+        block_scan_u64(z, S.ws, zk);   // mass of the keys > lo
+        __syncthreads();
+        const unsigned long long above_k = zk, mk = by_k ? key_mass(T, my) : 0ull;
+        zk += (unsigned long long)j * mk * (by_k ? 1ull : 0ull);
+        const double thr = (double)top_p * (double)zk;
+        uint32_t Tp;
+        if (radix_select<true>(p, V, inv_temp, my, lo, thr, S, Tp, ab)) {
+            T = Tp;
+            jcap = V;
+            j = tie_count(thr, ab, key_mass(T, my), V);
+        } else {   // the cut falls among the top-k set's last equal words
+            j = tie_count(thr, above_k, mk, jcap);
+        }
+    }
+    // ---- kept words per chunk: their number, the rank of the chunk's first word of key T among the equal words, their mass
+    const unsigned long long mT = key_mass(T, my);
+    unsigned long long cnt = 0, mass_gt = 0;   // cnt: (words with key > T) << 32 | words with key == T
+    for (int c = c0; c < c1; ++c) {
+        const uint32_t k = pick_key(p[c], inv_temp);
+        if (k > T) { cnt += 1ull << 32; mass_gt += key_mass(k, my); }
+        else if (k == T) cnt += 1ull;
+    }
+    unsigned long long cnt_all, z_kept;
+    const unsigned long long cnt_incl = block_scan_u64(cnt, S.ws, cnt_all);
+    __syncthreads();
+    const long n_eq = (long)(cnt_all & 0xffffffffull), n_gt = (long)(cnt_all >> 32);
+    j = max(1l, min(min(j, jcap), n_eq));
+    const long eq0 = (long)((cnt_incl - cnt) & 0xffffffffull);   // equal words before this chunk
+    const long my_eq = max(0l, min((long)(cnt & 0xffffffffull), j - eq0));   // equal words of this chunk that are kept
+    const unsigned long long part = mass_gt + (unsigned long long)my_eq * mT;
+    const unsigned long long run_incl = block_scan_u64(part, S.ws, z_kept);
+    const int rd = round ? min(max(round[0], 0), u_rounds - 1) : 0;
+    const double target = (double)u[(long)rd * rows + r] * (double)z_kept;
+    if ((double)run_incl > target && !((double)(run_incl - part) > target)) {   // inverse CDF over the kept words in index order
+        unsigned long long run = run_incl - part;
+        long e = eq0;
+        int idx = -1;
+        for (int c = c0; c < c1; ++c) {
+            const uint32_t k = pick_key(p[c], inv_temp);
+            if (k > T || (k == T && e++ < j)) {
+                run += key_mass(k, my);
+                idx = c;
+                if ((double)run > target) break;
+            }
+        }
+        s_tok = idx;
+    }
+    __syncthreads();
+    if (s_tok < 0) {   // no running mass exceeds the target (u >= 1): the last kept word
+        long e = eq0;
+        int last = -1;
+        for (int c = c0; c < c1; ++c) {
+            const uint32_t k = pick_key(p[c], inv_temp);
+            if (k > T || (k == T && e++ < j)) last = c;
+        }
+        if (last >= 0) atomicMax(&s_last, last);
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int w = min(max(s_tok >= 0 ? s_tok : s_last, 0), V - 1);
+        tok[r] = w;
+        if (kept) kept[r] = (int32_t)(n_gt + j);
+        const int n = len[r];
+        if (!done[r] && n >= 0 && n < Lmax) {
+            const float lp = (p[w] - mx1) - logf(s1);   // log softmax at temperature 1 over the full vocabulary
+            seq[r * Lmax + n] = w;
+            len[r] = n + 1;
+            logprob[r] += (double)lp;
+            if (w == eos) done[r] = 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void fill_kept_kernel(int32_t* __restrict__ kept, long rows, int v) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < rows) kept[i] = v;
+}
+
 __global__ __launch_bounds__(256) void round_end_kernel(const int32_t* __restrict__ done, long rows, float* __restrict__ pending,
                                                         int32_t* __restrict__ round) {
     __shared__ float sh[4];
@@ -241,6 +462,34 @@ extern "C" int vc_decode_pick_f32(void* stream, const float* logits, long rows, 
     else
         hipLaunchKernelGGL(decode_pick_kernel<false>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, logits, rows, V, ld,
                            inv_temp, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_decode_pick_trunc_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, int top_k,
+                                        float top_p, const float* u, int u_rounds, const int32_t* round, int eos, int32_t* tok,
+                                        int32_t* done, int32_t* seq, int Lmax, int32_t* len, double* logprob, int32_t* kept) {
+    VC_CHECK_ARG(logits && tok && done && seq && len && logprob, "null pointer");
+    VC_CHECK_ARG(rows > 0 && V > 0 && ld >= V && Lmax > 0, "bad shape");
+    VC_CHECK_ARG(u && u_rounds > 0, "truncated sampling needs uniforms (u, u_rounds > 0): without a draw it is the argmax");
+    VC_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "temperature must be finite and > 0");
+    VC_CHECK_ARG(top_k >= 0, "top_k must be >= 0 (0 = off)");
+    VC_CHECK_ARG(top_p > 0.f && top_p <= 1.0f, "top_p must be in (0, 1] (1 = off)");
+    const hipStream_t st = (hipStream_t)stream;
+    if ((top_k == 0 || top_k >= V) && top_p == 1.0f) {   // nothing to cut: the plain draw, bit for bit
+        const int rc = vc_decode_pick_f32(stream, logits, rows, V, ld, temperature, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob);
+        if (rc) return rc;
+        if (kept) hipLaunchKernelGGL(fill_kept_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, kept, rows, V);
+        VC_LAUNCH_CHECK();
+        return 0;
+    }
+    const float inv_temp = 1.0f / temperature;
+    if (V <= PICK_LDS_MAX)
+        hipLaunchKernelGGL(decode_pick_trunc_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)V * sizeof(float), st, logits, rows, V, ld,
+                           inv_temp, top_k, top_p, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob, kept);
+    else
+        hipLaunchKernelGGL(decode_pick_trunc_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, logits, rows, V, ld, inv_temp, top_k,
+                           top_p, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob, kept);
     VC_LAUNCH_CHECK();
     return 0;
 }

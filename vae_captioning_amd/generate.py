@@ -137,6 +137,21 @@ def merge_groups(groups):
     return sorted((tuple(best[k]) for k in order), key=lambda x: -x[1])
 
 
+def check_truncation(top_k, top_p, method="sample"):
+    """(top_k, top_p) of truncated sampling as (int, float); ValueError for values outside top_k >= 0, 0 < top_p <= 1 and for a
+    truncation asked of a greedy decode (it has no draw to truncate).  (0, 1.0) = off."""
+    if isinstance(top_k, bool) or int(top_k) != top_k or int(top_k) < 0:
+        raise ValueError("top_k must be an integer >= 0 (0 = off; got %r)" % (top_k,))
+    top_p = float(top_p)
+    if not (0.0 < top_p <= 1.0):
+        raise ValueError("top_p must be in (0, 1] (1 = off; got %r)" % (top_p,))
+    if top_p < 1.0 and float(np.float32(top_p)) >= 1.0:
+        raise ValueError("top_p = %r is 1 in float32: pass 1.0 for no nucleus cut" % (top_p,))
+    if method != "sample" and (int(top_k) != 0 or top_p != 1.0):
+        raise ValueError("top_k / top_p truncate the draw of method='sample'; method=%r has none" % (method,))
+    return int(top_k), top_p
+
+
 class CaptionGenerator(object):
     def __init__(self, engine):
         self.e = engine
@@ -443,9 +458,12 @@ class CaptionGenerator(object):
                     break
         return self._trim(ids[:steps], eos)
 
-    def sample(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, uniforms=None, check_every=4):
+    def sample(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, uniforms=None, check_every=4, top_k=0, top_p=1.0):
         """decoder.py:145-201 with sample_gen='sample': tokens drawn from softmax(logits / temperature)
-        (tf.multinomial).  uniforms [max_len, B] in [0,1) may be injected; otherwise Philox."""
+        (tf.multinomial).  uniforms [max_len, B] in [0,1) may be injected; otherwise Philox.
+        top_k > 0 / top_p < 1: the draw is truncated to the top_k best words and / or the smallest set of best words holding a share
+        top_p of the probability (vc_decode_pick_trunc_f32; DESIGN.md "Truncated sampling"); the defaults leave it as it is."""
+        top_k, top_p = check_truncation(top_k, top_p)
         max_len = max_len or self.p.gen_max_len
         c, h = self.init_state(features, c_v, eps)
         B = c.shape[0]
@@ -454,6 +472,12 @@ class CaptionGenerator(object):
         u = torch.empty((B,), dtype=torch.float32, device=self.e.dev)
         ud = self._dev(uniforms, np.float32) if uniforms is not None else None
         steps = 0
+        trunc = top_k != 0 or top_p != 1.0
+        if trunc:   # the entry keeps a candidate per row (diverse()'s bookkeeping): scratch here, the ids are what sample() returns
+            i32 = torch.int32
+            t_done, t_len, t_seq = self._b("st_done", (B,), i32), self._b("st_len", (B,), i32), self._b("st_seq", (B, max_len), i32)
+            t_lp = self._b("st_lp", (B,), torch.float64)
+            t_done.zero_(); t_len.zero_(); t_lp.zero_()
         for it in range(max_len):
             logits, c, h = self.step(tok, c, h, want="logits")
             if ud is not None:
@@ -461,7 +485,11 @@ class CaptionGenerator(object):
             else:
                 self.lib.vc_philox_uniform_f32(_stream(), P(u), B, self.e.seed * 1000003 + 29, (16 + it) << 32, P(self.e.step))
             tok = ids[it]
-            self.lib.vc_multinomial_rows_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), P(tok))
+            if trunc:
+                self.lib.vc_decode_pick_trunc_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), top_k, top_p, P(u), 1,
+                                                  None, int(eos), P(tok), P(t_done), P(t_seq), max_len, P(t_len), P(t_lp), None)
+            else:
+                self.lib.vc_multinomial_rows_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), P(tok))
             steps = it + 1
             if check_every and steps % check_every == 0 and bool((ids[:steps] == eos).any(0).all().item()):
                 break
@@ -535,7 +563,8 @@ class CaptionGenerator(object):
             self._capture(key, lambda: launches(False))   # (a capture executes nothing: the eager launches above are this call's)
         return cs1[1], hs1[1]
 
-    def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every, rerank="likelihood"):
+    def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every, rerank="likelihood",
+                      top_k=0, top_p=1.0):
         """One pass of diverse(): the B*K candidate rows of B images decoded together, ranked per image on device (vc_diverse_rank),
         results in two flat buffers brought back by two copies into pinned memory."""
         lib, e, p = self.lib, self.e, self.p
@@ -562,6 +591,7 @@ class CaptionGenerator(object):
             else:
                 lib.vc_philox_uniform_f32(_stream(), P(ud), ud.numel(), e.seed * 1000003 + 29, 7 << 32, P(e.step))
         temp = float(p.temperature) if method == "sample" else 1.0
+        trunc = top_k != 0 or top_p != 1.0
 
         def reset():
             tok.fill_(bos); f["ended"].zero_(); f["len"].zero_(); logprob.zero_(); rnd.zero_()
@@ -569,15 +599,19 @@ class CaptionGenerator(object):
         def one(r, timed):
             src, dst = (Bb, A) if r % 2 == 0 else (A, Bb)
             logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
-            lib.vc_decode_pick_f32(_stream(), P(logits), M, V, V, temp, P(ud) if ud is not None else None, max_len, P(rnd), int(eos), P(tok),
-                                   P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob))
+            if trunc:
+                lib.vc_decode_pick_trunc_f32(_stream(), P(logits), M, V, V, temp, top_k, top_p, P(ud), max_len, P(rnd), int(eos), P(tok),
+                                             P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob), None)
+            else:
+                lib.vc_decode_pick_f32(_stream(), P(logits), M, V, V, temp, P(ud) if ud is not None else None, max_len, P(rnd), int(eos), P(tok),
+                                       P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob))
             lib.vc_decode_round_end_i32(_stream(), P(f["ended"]), M, P(pending), P(rnd))
 
         Kc = int(check_every) if check_every and check_every % 2 == 0 else 4   # rounds per captured chunk (even: the state ends where it started)
         self._pack_wh(M)
         Bb["c2"].copy_(c0); Bb["h2"].copy_(h0)    # state before round 0 lives in set B; round r reads set (B, A, B, ...) and writes the other
         baked = [tok, rnd, pending, ibuf, dbuf, ud, self._ones_for(M)] + list(A.values()) + list(Bb.values())
-        kargs = ("diverse", B, K, Kc, max_len, int(eos), method, temp)
+        kargs = ("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p)   # (a captured chunk bakes the truncation)
         key = self._graph_key(*kargs, tensors=baked)
         if key not in self._graphs:   # (the first call of a shape runs one round eagerly: it sizes the workspace a captured chunk bakes)
             reset()
@@ -733,7 +767,7 @@ class CaptionGenerator(object):
         return res
 
     def diverse(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, method="greedy", n_best=None, max_len=None, len_norm_f=0.7,
-                uniforms=None, check_every=4, rerank="likelihood"):
+                uniforms=None, check_every=4, rerank="likelihood", top_k=0, top_p=1.0):
         """Diverse captioning (the AG-CVAE paper's purpose of z): per image `draws` = K independent latent draws, each decoded with
         `greedy` (argmax) or `sample` (inverse CDF at params.temperature) up to and including its first <EOS> (at most max_len tokens),
         log-likelihood = sum of the emitted tokens' log-softmax at temperature 1 (f32 terms, f64 sum), score = logprob / (1 + n)**len_norm_f
@@ -748,7 +782,10 @@ class CaptionGenerator(object):
         rerank="marginal": every distinct caption of an image is re-scored under ALL K draws of its pass (score()'s marginal
         log 1/K sum_k p(caption | z_k, image), nothing drawn again) and the entries are ordered by marginal / (1 + n)**len_norm_f:
         <EOS>-ended first, then that score descending, exact ties in the likelihood order; entries become (tokens, score, count, marginal)
-        with `score` the new one.  n_best cuts after the re-ranking.  "likelihood" (default) is the order described above."""
+        with `score` the new one.  n_best cuts after the re-ranking.  "likelihood" (default) is the order described above.
+        top_k > 0 / top_p < 1 (method="sample" only): every draw's tokens come from the truncated distribution (the top_k best words and /
+        or the smallest set of best words holding a share top_p of the probability; DESIGN.md "Truncated sampling"); log-likelihoods stay
+        the model's, over the full vocabulary, so score() of a candidate under its own draw still returns its logprob."""
         K = int(draws)
         if not 1 <= K <= DIVERSE_MAX_DRAWS:
             raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
@@ -756,6 +793,7 @@ class CaptionGenerator(object):
             raise ValueError("method must be 'greedy' or 'sample' (got %r)" % (method,))
         if rerank not in ("likelihood", "marginal"):
             raise ValueError("rerank must be 'likelihood' or 'marginal' (got %r)" % (rerank,))
+        top_k, top_p = check_truncation(top_k, top_p, method)
         p = self.p
         max_len = int(max_len or p.gen_max_len)
         B = int(features.shape[0])
@@ -771,7 +809,7 @@ class CaptionGenerator(object):
             sl = slice(g0, min(B, g0 + G))
             r, c = self._diverse_pass(features[sl], c_v[sl] if c_v is not None else None, np.asarray(eps)[:, :, sl] if eps is not None else None,
                                       K, method, bos, eos, max_len, len_norm_f, n_best,
-                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every, rerank)
+                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every, rerank, top_k, top_p)
             res += r
             cands += c
         self.last_candidates = cands

@@ -26,7 +26,7 @@ _DEFAULTS = dict(
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
-    score_draws=0, beam_groups=5, beam_diversity=0.5,
+    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -50,6 +50,7 @@ _FLAGS = [
     ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal"]), ("--consensus_k", "consensus_k", int, None),
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
+    ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -68,7 +69,10 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--beam_size": "beams per image (default 10); --sample_gen diverse_beam: the total over the groups, a multiple of --beam_groups, <= 16",
          "--beam_groups": "--sample_gen diverse_beam: groups per image, each a beam search of beam_size / beam_groups beams (default 5)",
          "--beam_diversity": "--sample_gen diverse_beam: what a word costs a candidate per live beam of the round's earlier groups that "
-                             "has just taken it (>= 0; default 0.5)"}
+                             "has just taken it (>= 0; default 0.5)",
+         "--top_k": "--sample_gen sample / --diverse_method sample: draw each word from the k most likely only (>= 0; default 0 = all)",
+         "--top_p": "--sample_gen sample / --diverse_method sample: draw each word from the smallest set of most likely words that holds "
+                    "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)"}
 
 
 class Parameters(object):
@@ -115,6 +119,10 @@ class Parameters(object):
                 ap.error("--beam_size must be divisible by --beam_groups (got %d and %d)" % (self.beam_size, self.beam_groups))
             if not (0.0 <= self.beam_diversity < float("inf")):
                 ap.error("--beam_diversity must be finite and >= 0 (got %r)" % self.beam_diversity)
+        if self.top_k < 0:
+            ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
+        if not (0.0 < self.top_p <= 1.0):
+            ap.error("--top_p must be in (0, 1] (got %r)" % self.top_p)
         if self.synthetic:
             self.vocab_size = int(args["vocab"]) if args["vocab"] is not None else 10000
         self.hdf5_file = self.coco_dir + os.path.basename(self.hdf5_file)  # the image array lives next to the data set

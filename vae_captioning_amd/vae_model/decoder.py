@@ -68,7 +68,8 @@ class Decoder(object):
         bos, eos = d.word2idx["<BOS>"], d.word2idx[stop_word]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
         if self.params.sample_gen == "sample":  # tf.multinomial(logits / temperature): same distribution, own Philox stream
-            raw = self._gen().sample(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len)
+            raw = self._gen().sample(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len,
+                                     top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0))
         else:
             raw = self._gen().greedy(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len)
         cap_list = []
@@ -94,7 +95,8 @@ class Decoder(object):
     def diverse_inference(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, draws=None, method=None, n_best=None,
                           len_norm_f=0.7):
         """Diverse captioning (the purpose of z in the AG-CVAE paper): `draws` latent draws per image (params.diverse_draws), each decoded
-        with `method` (params.diverse_method: greedy or sample), identical captions merged and ranked (generate.py: diverse).  Returns
+        with `method` (params.diverse_method: greedy or sample; sample honours params.top_k / params.top_p), identical captions merged and
+        ranked (generate.py: diverse).  Returns
         cap_list: per image {"image_id", "caption": the best text, "captions": [texts], "scores": [...], "counts": [...]}.
         params.diverse_rerank == "consensus": every distinct caption is re-ranked by its consensus against the attached
         `consensus_index` (consensus.py) before n_best cuts the list; the records gain "consensus" (aligned with "captions") and
@@ -113,7 +115,8 @@ class Decoder(object):
                                "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
         feats = self._features(in_pictures)
         res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus else n_best,
-                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood")
+                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood",
+                                  top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0))
         if consensus:
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
         cap_list = []
