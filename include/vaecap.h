@@ -38,6 +38,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the caption-scoring entries vc_logits_logprob_f32 /
  *      vc_logits_logprob_workspace_bytes / vc_score_reduce_f64.
  *      Added within 4 (additive, no layout change): the truncated-sampling entry vc_decode_pick_trunc_f32.
+ *      Added within 4 (additive, no layout change): the caption-evaluation entry vc_ngram_overlap.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -557,6 +558,27 @@ int vc_consensus_score(void* stream, int B, int k, const int32_t* nbr, const int
                        const uint64_t* r_keys, const float* r_w, const float* r_norm, const int32_t* r_len, const int32_t* cand_img,
                        int max_cands, const int32_t* c_off, const int32_t* c_nnz, const uint64_t* c_keys, const float* c_w,
                        const float* c_norm, const int32_t* c_len, int m, double* score);
+
+/* ------------------------------------------------------------------------------------
+ * Evaluation of caption sets (evaluate.py: CaptionEvaluator; csrc/evaluate.hip): BLEU-style clipped n-gram counts.
+ *   ngram_overlap   Hypotheses (c_*, C rows) and references (r_*, n_ref rows) are ngram_vectors outputs (off, nnz, keys, w, words) built
+ *                   with an EMPTY df table (n_df = 0, idf_unseen = 1.0f): w is then the n-gram's count as an exact float.  The two tables
+ *                   may be the same one.  Hypothesis c is compared with the reference rows [lo[c], hi[c]) except row skip[c] (-1: none).
+ *                   The range is clamped on the device: lo' = min(max(lo, 0), n_ref), hi' = min(max(hi, lo'), n_ref), so lo > hi and
+ *                   ranges outside the table read nothing and give the results of an empty range; a skip outside the range drops
+ *                   nothing.  (lo, hi and skip are device arrays: the host checks the scalars and the pointers only.)
+ *                   With c_g the hypothesis's count of n-gram g and m_g the largest count of g over the range's rows, per order n = 1..4:
+ *                     total[c, n-1]    = sum_g c_g             (= max(0, L - n + 1))
+ *                     match[c, n-1]    = sum_g min(c_g, m_g)   (BLEU's clipped count)
+ *                     distinct[c, n-1] = the number of distinct n-grams g
+ *                     unseen[c, n-1]   = the number of those with m_g = 0
+ *                     ref_len[c]       = the words of the range's row that minimises (|L_r - L_c|, L_r): a tie goes to the shorter
+ *                   An empty range (also after the skip) gives match 0, unseen = distinct, ref_len 0.  All outputs are int32 sums and
+ *                   maxima: a row's results depend on the row and its range only.  One wave per hypothesis, four per workgroup, 16 KiB LDS. */
+int vc_ngram_overlap(void* stream, long C, const int32_t* c_off, const int32_t* c_nnz, const uint64_t* c_keys, const float* c_w,
+                     const int32_t* c_len, long n_ref, const int32_t* r_off, const int32_t* r_nnz, const uint64_t* r_keys, const float* r_w,
+                     const int32_t* r_len, const int32_t* lo, const int32_t* hi, const int32_t* skip, int32_t* total, int32_t* match,
+                     int32_t* distinct, int32_t* unseen, int32_t* ref_len);
 
 /* ------------------------------------------------------------------------------------
  * Scoring given captions (generate.py: CaptionGenerator.score; csrc/score.hip).  Forward only.

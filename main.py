@@ -74,25 +74,43 @@ def coco_batches(gen, params, epoch_rule=False, world=1):
             return
 
 
+def training_index_data(params, coco_train):
+    """(fc2 features, captions per image) of the training images at hand, or None.  MSCOCO: the training generator's images (train +
+    repartitioned val, never the held-out ones); --synthetic: 512 seeded images with 5 captions each."""
+    from vae_captioning_amd.consensus import index_data_from_generator
+    if coco_train is not None:
+        return index_data_from_generator(coco_train)
+    if params.synthetic:
+        b = synth.make_batch(np.random.default_rng(params.seed + 11), 512, 5, 12, params.vocab_size, feature_size=params.cnn_feature_size)
+        return b["features"], [[[int(t) for t in r] for r in b["cap_enc"][i * 5:(i + 1) * 5]] for i in range(512)]   # "w.. <EOS>", 11 words
+    return None
+
+
 def consensus_index(params, tr, cap_dict, coco_train):
-    """--diverse_rerank consensus: the index of training images (fc2 features + captions) that diverse captions are re-ranked against.
-    MSCOCO: the training generator's images (train + repartitioned val, never the held-out ones); --synthetic: 512 seeded images with
-    5 captions each."""
-    from vae_captioning_amd.consensus import ConsensusIndex, index_data_from_generator
+    """--diverse_rerank consensus: the index of training images (fc2 features + captions, training_index_data) that diverse captions are
+    re-ranked against."""
+    from vae_captioning_amd.consensus import ConsensusIndex
     if params.fine_tune:
         raise SystemExit("--diverse_rerank consensus needs precomputed fc2 features for its index of training images; "
                          "an index from a fine-tuned VGG16 is not supported (drop --fine_tune)")
-    if coco_train is not None:
-        feats, caps = index_data_from_generator(coco_train)
-    elif params.synthetic:
-        b = synth.make_batch(np.random.default_rng(params.seed + 11), 512, 5, 12, params.vocab_size, feature_size=params.cnn_feature_size)
-        feats = b["features"]
-        caps = [[[int(t) for t in r] for r in b["cap_enc"][i * 5:(i + 1) * 5]] for i in range(512)]   # "w.. <EOS>", 11 words
-    else:
+    data = training_index_data(params, coco_train)
+    if data is None:
         raise SystemExit("--diverse_rerank consensus needs the MSCOCO training images (--coco_dir) or --synthetic")
+    feats, caps = data
     bos, eos = cap_dict.word2idx["<BOS>"], cap_dict.word2idx["<EOS>"]
     print("consensus index: %d images, k = %d, m = %d" % (len(caps), params.consensus_k, params.consensus_m))
     return ConsensusIndex(tr.cap, feats, caps, bos, eos, k=params.consensus_k, m=params.consensus_m, vocab_size=cap_dict.vocab_size)
+
+
+def training_captions(params, coco_train):
+    """--eval_captions: the flat training captions `novel` is measured against -- the captions of the training generator's images (a
+    walk of its caption table: no features are read, so --fine_tune works too) or of --synthetic's seeded index; None when neither is
+    at hand (`novel` is then null)."""
+    if coco_train is not None:
+        from vae_captioning_amd.consensus import captions_from_generator
+        return [c for caps in captions_from_generator(coco_train) for c in caps]
+    data = training_index_data(params, coco_train)
+    return None if data is None else [c for caps in data[1] for c in caps]
 
 
 def main(params):
@@ -234,6 +252,8 @@ def main(params):
         decoder = Decoder(None, None, None, params, cap_dict)
         if params.sample_gen == "diverse" and params.diverse_rerank == "consensus":
             decoder.consensus_index = consensus_index(params, tr, cap_dict, coco_train)
+        if params.eval_captions and rank == 0:
+            decoder.train_captions = training_captions(params, coco_train)
         if coco_val is not None:  # ops/inference.py:4-56 on the validation / test image sets
             from vae_captioning_amd.ops.inference import inference
             if rank == 0:
@@ -242,7 +262,7 @@ def main(params):
                 dist.destroy_process_group()
             return
         rng = np.random.default_rng(params.seed + 5)
-        captions_gen, scores = [], []
+        captions_gen, scores, references, decoded = [], [], [], []
         for it in range(2):
             b = synth.make_batch(rng, params.batch_size, 1, 20, params.vocab_size, use_ci=spec.uses_ci(params), images=params.fine_tune)
             ids = ["synthetic_%06d" % (it * params.batch_size + i) for i in range(params.batch_size)]
@@ -261,6 +281,10 @@ def main(params):
             else:
                 sent, _ = decoder.online_inference(None, ids, pics, None, c_v=c_v)
             captions_gen += sent
+            if params.eval_captions:   # the batch's own captions (one per image, by construction) are its "human" references
+                from vae_captioning_amd.ops.inference import decoded_ids, human_captions
+                references += human_captions((b["cap_dec"], b["cap_enc"]), b["lengths"])
+                decoded += decoded_ids(decoder, len(ids))
             if params.score_draws:   # held-out likelihood of the batch's own ("human") captions under the prior
                 from vae_captioning_amd.ops.inference import human_captions
                 scores += decoder.score_captions(ids, pics, human_captions((b["cap_dec"], b["cap_enc"]), b["lengths"]), c_v)
@@ -274,6 +298,9 @@ def main(params):
             if params.score_draws:
                 from vae_captioning_amd.ops.inference import store_scores
                 store_scores(params, scores)
+            if params.eval_captions:
+                from vae_captioning_amd.ops.inference import evaluate_decoded
+                evaluate_decoded(params, decoder, references, decoded)
     if world > 1:
         dist.destroy_process_group()
 

@@ -149,6 +149,41 @@ def host_index(captions, bos, eos, vocab_size=None):
                                  idf_unseen=np.float32(np.log(float(D))))
 
 
+def upload(dev, a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def ngram_vectors(lib, dev, W, L, bos, eos, df_keys, idf, n_df, idf_unseen, head=None):
+    """n-gram vectors of word rows (vc_ngram_vectors), CSR by capacity(L), weighted by the device df / idf table given (n_df = 0: every
+    n-gram gets idf_unseen).  The host inputs go up in one copy; head: an int32 array sent along (v.head is its device copy)."""
+    n = int(W.shape[0])
+    cap = capacity(L)
+    off = np.zeros(n + 1, np.int64)
+    off[1:] = np.cumsum(cap)
+    if off[-1] >= 2 ** 31:
+        raise ValueError("%d n-gram slots: more than an int32 CSR offset holds" % off[-1])
+    head = np.zeros(0, np.int32) if head is None else np.asarray(head, np.int32)
+    h, o1, o2 = head.size, head.size + n + 1, head.size + 2 * n + 1
+    up = upload(dev, np.concatenate([head, off.astype(np.int32), np.asarray(L, np.int32), W.astype(np.int32).reshape(-1)]))
+    total = max(1, int(off[-1]))
+    v = types.SimpleNamespace(n=n, head=up[:h], off=up[h:o1], keys=torch.empty(total, dtype=torch.int64, device=dev),
+                              w=torch.empty(total, dtype=torch.float32, device=dev),
+                              nnz=torch.empty(max(1, n), dtype=torch.int32, device=dev),
+                              norm=torch.empty((max(1, n), 4), dtype=torch.float32, device=dev),
+                              words=torch.empty(max(1, n), dtype=torch.int32, device=dev))
+    if n:
+        lib.vc_ngram_vectors(_stream(), P(up[o2:]), n, int(W.shape[1]), P(up[o1:o2]), int(bos), int(eos), P(df_keys), P(idf), int(n_df),
+                             float(idf_unseen), P(v.off), P(v.keys), P(v.w), P(v.nnz), P(v.norm), P(v.words))
+    return v
+
+
+def library_and_device(lib_or_engine):
+    """(library, device) of the C-ABI library (abi.load(): the current device) or of a CaptionEngine"""
+    if hasattr(lib_or_engine, "lib") and hasattr(lib_or_engine, "dev"):
+        return lib_or_engine.lib, lib_or_engine.dev
+    return lib_or_engine, torch.device("cuda", torch.cuda.current_device())
+
+
 def rerank_entries(entries, consensus, n_best=None):
     """(tokens, score, count) entries in likelihood order + their consensus scores -> (tokens, score, count, consensus) by consensus,
     highest first; exact ties keep the likelihood order.  n_best: keep the first n_best (None: all)."""
@@ -159,21 +194,36 @@ def rerank_entries(entries, consensus, n_best=None):
     return out if n_best is None else out[:int(n_best)]
 
 
+def _training_names(gen):
+    """base file names of the training images of a Batch_Generator: `_iterable` without the held-out `unused_cap_in` images"""
+    held = set(gen.unused_cap_in or ())
+    return [name.split("/")[-1] for name in gen._iterable if name not in held]
+
+
+def captions_from_generator(gen):
+    """per training image of a Batch_Generator its token lists, looked up through `_lookup` so that repartitioned validation images
+    come from val_captions; no features are read.  Host only."""
+    return [[list(c) for c in gen._lookup(gen.captions or {}, gen.val_captions, base)] for base in _training_names(gen)]
+
+
 def index_data_from_generator(gen):
     """(features [D, F] float32, captions: per image its token lists) of the training images of a Batch_Generator: `_iterable`
     walked through `_lookup`, so repartitioned validation images come from val_feature_dict / val_captions.  The held-out
     `unused_cap_in` images are never included.  Host only."""
     if not gen.feature_dict:
         raise ValueError("the consensus index needs precomputed fc2 features (a Batch_Generator with a feature_dict)")
-    held = set(gen.unused_cap_in or ())
-    feats, caps = [], []
+    feats = [np.asarray(gen._lookup(gen.feature_dict, gen.val_feature_dict, base), np.float32).reshape(-1) for base in _training_names(gen)]
+    return np.stack(feats), captions_from_generator(gen)
+
+
+def references_from_generator(gen):
+    """{image id: EVERY human caption (token list) of the image} for the images a Batch_Generator iterates over, keyed by the ids
+    next_val_batch(get_image_ids=True) yields.  (The batches themselves carry ONE randomly drawn caption per image.)  Host only."""
+    out = {}
     for name in gen._iterable:
-        if name in held:
-            continue
         base = name.split("/")[-1]
-        feats.append(np.asarray(gen._lookup(gen.feature_dict, gen.val_feature_dict, base), np.float32).reshape(-1))
-        caps.append([list(c) for c in gen._lookup(gen.captions or {}, gen.val_captions, base)])
-    return np.stack(feats), caps
+        out[gen._imid([name])[0]] = [list(c) for c in gen._lookup(gen.captions or {}, gen.val_captions, base)]
+    return out
 
 
 class ConsensusIndex(object):
@@ -181,10 +231,7 @@ class ConsensusIndex(object):
     and device).  features [D, F] (host array or device tensor); captions: per image a list of token lists."""
 
     def __init__(self, lib_or_engine, features, captions, bos, eos, k=90, m=125, vocab_size=None):
-        if hasattr(lib_or_engine, "lib") and hasattr(lib_or_engine, "dev"):
-            self.lib, self.dev = lib_or_engine.lib, lib_or_engine.dev
-        else:
-            self.lib, self.dev = lib_or_engine, torch.device("cuda", torch.cuda.current_device())
+        self.lib, self.dev = library_and_device(lib_or_engine)
         check_limits(k, m)
         self.k, self.m, self.bos, self.eos = int(k), int(m), int(bos), int(eos)
         if len(features) != len(captions):
@@ -213,7 +260,7 @@ class ConsensusIndex(object):
 
     # ------------------------------------------------------------------ plumbing
     def _up(self, a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        return upload(self.dev, a)
 
     def _dev_f32(self, a):
         if isinstance(a, torch.Tensor):
@@ -221,27 +268,8 @@ class ConsensusIndex(object):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.dev)
 
     def _vectors(self, W, L, head=None):
-        """n-gram vectors of word rows (vc_ngram_vectors), CSR by capacity(L).  The host inputs go up in one copy; head: an int32
-        array sent along (v.head is its device copy)."""
-        n = int(W.shape[0])
-        cap = capacity(L)
-        off = np.zeros(n + 1, np.int64)
-        off[1:] = np.cumsum(cap)
-        if off[-1] >= 2 ** 31:
-            raise ValueError("%d n-gram slots: more than an int32 CSR offset holds" % off[-1])
-        head = np.zeros(0, np.int32) if head is None else np.asarray(head, np.int32)
-        h, o1, o2 = head.size, head.size + n + 1, head.size + 2 * n + 1
-        up = self._up(np.concatenate([head, off.astype(np.int32), np.asarray(L, np.int32), W.astype(np.int32).reshape(-1)]))
-        total = max(1, int(off[-1]))
-        v = types.SimpleNamespace(n=n, head=up[:h], off=up[h:o1], keys=torch.empty(total, dtype=torch.int64, device=self.dev),
-                                  w=torch.empty(total, dtype=torch.float32, device=self.dev),
-                                  nnz=torch.empty(max(1, n), dtype=torch.int32, device=self.dev),
-                                  norm=torch.empty((max(1, n), 4), dtype=torch.float32, device=self.dev),
-                                  words=torch.empty(max(1, n), dtype=torch.int32, device=self.dev))
-        if n:
-            self.lib.vc_ngram_vectors(_stream(), P(up[o2:]), n, int(W.shape[1]), P(up[o1:o2]), self.bos, self.eos, P(self.df_keys),
-                                      P(self.idf), self.n_df, self.idf_unseen, P(v.off), P(v.keys), P(v.w), P(v.nnz), P(v.norm), P(v.words))
-        return v
+        """n-gram vectors of word rows under the index's df / idf table (ngram_vectors above)"""
+        return ngram_vectors(self.lib, self.dev, W, L, self.bos, self.eos, self.df_keys, self.idf, self.n_df, self.idf_unseen, head)
 
     def _exclude(self, exclude, B):
         if exclude is None:

@@ -1,0 +1,215 @@
+"""Evaluation of caption sets on the GPU: the numbers the AG-CVAE paper reports for a set of captions per image -- accuracy of the top
+caption (BLEU-1..4, CIDEr-D), "oracle" accuracy of the best caption of the set, and the diversity of the set (share of distinct
+captions, share of novel sentences, Div-1, Div-2, mBLEU-4).
+
+`CaptionEvaluator(lib_or_engine, references, bos, eos)` holds the n-gram vectors of every image's human captions on the device;
+`evaluate(candidates)` takes per image a ranked list of token-id lists (best first, possibly empty) and returns a dict of float64
+values (METRICS) plus per-image arrays under "per_image".
+
+Words are token ids without <BOS>, <EOS> and PAD (0), as in consensus.py, whose limits hold here: at most 64 words per caption, ids
+<= 65535, at most 256 captions and 2048 references per image.
+
+Every integer comes from the device, every float from float64 arithmetic on those integers on the host:
+
+* BLEU-style counts: csrc/evaluate.hip's vc_ngram_overlap on count vectors (vc_ngram_vectors with an empty df table), called three
+  times on one hypothesis table -- against the image's references (BLEU), against the image's EARLIER captions (an n-gram unseen there
+  is a new distinct n-gram of the image: Div-n), against the image's OTHER captions (mBLEU).  One copy-back of the integer arrays.
+* CIDEr-D: vc_consensus_score on idf-weighted vectors with k = 1, nbr[b] = b, the references' offsets as img_cap and m = 2048, i.e.
+  the mean over ALL references of the image of the one-reference CIDEr-D.  The idf is coco-caption's convention: document frequencies
+  over the evaluated images' references (consensus.host_index), unseen n-grams log D.
+
+BLEU here is the plain corpus-level definition (corpus_bleu): it does NOT imitate coco-caption's smoothing constants (its 1e-9 "tiny" /
+1e-15 "small" terms), and the tokens are vocabulary ids after the vocabulary cut, not PTB tokens -- the numbers compare runs of this
+project with each other, not with a leaderboard ("Evaluation").
+
+Single-caption modes (greedy, sample, beam_search) hand in lists of one: the set metrics are then those of lists of one -- `distinct`
+1.0, `mbleu_4` 0.0 (no hypotheses), `oracle_cider_d` = `mean_cider_d` = `cider_d`."""
+import math
+
+import numpy as np
+import torch
+
+from .abi import ptr as P
+from .consensus import MAX_POOL, host_index, library_and_device, ngram_vectors, upload, word_rows
+from .engine import _stream
+from .generate import DIVERSE_MAX_DRAWS
+
+METRICS = ("bleu_1", "bleu_2", "bleu_3", "bleu_4", "cider_d", "oracle_cider_d", "mean_cider_d", "distinct", "div_1", "div_2", "mbleu_4",
+           "novel")
+MAX_REFS = MAX_POOL       # references per image (vc_consensus_score stages an image's pool in LDS)
+OUT_COLS = 17             # total, match, distinct, unseen [., 4] + ref_len per hypothesis
+
+
+def corpus_bleu(match, total, hyp_len, ref_len):
+    """Corpus-level BLEU-1..4 from integer sums over the hypotheses: match[n-1] / total[n-1] the clipped and the total n-gram counts,
+    hyp_len = C and ref_len = R the summed hypothesis and closest-reference lengths.  p_n = match_n / total_n, BLEU_n = BP * exp(mean
+    over i <= n of log p_i), BP = 1 if C >= R else exp(1 - R / C); 0.0 when any p_i is 0 (or has no n-gram) or C is 0.  Plain float64,
+    no smoothing constants.  -> [BLEU_1 .. BLEU_4]"""
+    C, R = int(hyp_len), int(ref_len)
+    out, logsum, dead = [], 0.0, C == 0
+    bp = 1.0 if C >= R or C == 0 else math.exp(1.0 - R / C)
+    for n in range(4):
+        m, t = int(match[n]), int(total[n])
+        dead = dead or m == 0 or t == 0
+        if not dead:
+            logsum += math.log(m / t)
+        out.append(0.0 if dead else bp * math.exp(logsum / (n + 1)))
+    return out
+
+
+def count_vectors(lib, dev, W, L, bos, eos, head=None):
+    """n-gram COUNT vectors of word rows: vc_ngram_vectors with an empty df table and idf_unseen = 1, so w is the exact count"""
+    return ngram_vectors(lib, dev, W, L, bos, eos, None, None, 0, 1.0, head)
+
+
+def check_ranges(lo, hi, skip, n_hyp, n_ref):
+    """lo / hi / skip [n_hyp] of vc_ngram_overlap, checked on the host (the library itself clamps a bad range to an empty one)"""
+    lo, hi, skip = (np.asarray(a, np.int64).reshape(-1) for a in (lo, hi, skip))
+    if not (lo.size == hi.size == skip.size == n_hyp):
+        raise ValueError("lo, hi and skip must hold one entry per hypothesis row (%d)" % n_hyp)
+    if n_hyp and ((lo < 0) | (lo > hi) | (hi > n_ref)).any():
+        r = int(np.flatnonzero((lo < 0) | (lo > hi) | (hi > n_ref))[0])
+        raise ValueError("row %d: range [%d, %d) is not inside the %d reference rows" % (r, lo[r], hi[r], n_ref))
+    if n_hyp and (skip < -1).any():
+        raise ValueError("skip must be a reference row or -1")
+    return lo.astype(np.int32), hi.astype(np.int32), skip.astype(np.int32)
+
+
+def _launch(lib, hyp, ref, rng, out):
+    """rng: int32 device [3, C] (lo, hi, skip); out: int32 device [OUT_COLS * C]"""
+    C = hyp.n
+    o = [P(out) + 4 * C * 4 * i for i in range(5)]
+    lib.vc_ngram_overlap(_stream(), C, P(hyp.off), P(hyp.nnz), P(hyp.keys), P(hyp.w), P(hyp.words), ref.n, P(ref.off), P(ref.nnz),
+                         P(ref.keys), P(ref.w), P(ref.words), P(rng), P(rng) + 4 * C, P(rng) + 8 * C, o[0], o[1], o[2], o[3], o[4])
+
+
+def _split(a, C):
+    """host int32 [OUT_COLS * C] -> dict of the five outputs"""
+    q = a[:16 * C].reshape(4, C, 4)
+    return dict(total=q[0], match=q[1], distinct=q[2], unseen=q[3], ref_len=a[16 * C:17 * C])
+
+
+def ngram_overlap(lib_or_engine, hyp, ref, lo, hi, skip=None):
+    """One vc_ngram_overlap call on two count_vectors tables (they may be the same one): hypothesis row c against reference rows
+    [lo[c], hi[c]) without row skip[c] (-1 / None: none).  -> dict of int32 arrays total, match, distinct, unseen [C, 4], ref_len [C]."""
+    lib, dev = library_and_device(lib_or_engine)
+    C = hyp.n
+    lo, hi, skip = check_ranges(lo, hi, np.full(C, -1) if skip is None else skip, C, ref.n)
+    if C == 0:
+        return _split(np.zeros(0, np.int32), 0)
+    rng = upload(dev, np.stack([lo, hi, skip]))
+    out = torch.empty(OUT_COLS * C, dtype=torch.int32, device=dev)
+    _launch(lib, hyp, ref, rng, out)
+    return _split(out.cpu().numpy(), C)
+
+
+def _mean(x):
+    x = np.asarray(x, np.float64)
+    return float(x.mean()) if x.size else 0.0
+
+
+class CaptionEvaluator(object):
+    """references: per image a list of token-id lists (1..2048); train_captions: an optional flat list of token-id lists for `novel`.
+    lib_or_engine: the C-ABI library (abi.load()) or a CaptionEngine (its library and device)."""
+
+    def __init__(self, lib_or_engine, references, bos, eos, vocab_size=None, train_captions=None):
+        self.lib, self.dev = library_and_device(lib_or_engine)
+        self.bos, self.eos = int(bos), int(eos)
+        self.B = len(references)
+        if self.B == 0:
+            raise ValueError("the evaluator needs the references of at least one image")
+        per = np.fromiter((len(r) for r in references), np.int64, self.B)
+        if per.min() < 1:
+            raise ValueError("image %d has no reference caption" % int(np.argmin(per)))
+        if per.max() > MAX_REFS:
+            raise ValueError("at most %d references per image (image %d has %d)" % (MAX_REFS, int(np.argmax(per)), per.max()))
+        h = host_index(references, bos, eos, vocab_size)
+        self.ref_off = h.img_cap                                   # int64 [B + 1]
+        self.n_refs = int(h.L.size)
+        self.n_df = int(h.df_keys.size)
+        self.df_keys = upload(self.dev, h.df_keys.view(np.int64) if self.n_df else np.zeros(1, np.int64))
+        self.idf = upload(self.dev, h.idf if self.n_df else np.zeros(1, np.float32))
+        self.idf_unseen = float(h.idf_unseen)
+        self.ref_counts = count_vectors(self.lib, self.dev, h.W, h.L, bos, eos)
+        self.ref_idf = self._idf_vectors(h.W, h.L, head=np.concatenate([h.img_cap, np.arange(self.B)]))   # head: img_cap, nbr [B, 1]
+        self.train = None
+        if train_captions is not None:
+            Wt, Lt = word_rows(list(train_captions), bos, eos, owner=lambda i: "training caption %d" % i)
+            Wt = Wt.astype(np.int32)
+            self.train = {Wt[i, :Lt[i]].tobytes() for i in range(Wt.shape[0])}
+
+    def _idf_vectors(self, W, L, head=None):
+        return ngram_vectors(self.lib, self.dev, W, L, self.bos, self.eos, self.df_keys, self.idf, self.n_df, self.idf_unseen, head)
+
+    def _cider(self, W, L, cand_img, max_cands):
+        """CIDEr-D of every candidate: the mean over its image's references (vc_consensus_score, k = 1, m = 2048) -> device float64"""
+        cv, rv, B = self._idf_vectors(W, L, head=cand_img), self.ref_idf, self.B
+        out = torch.empty(max(1, cv.n), dtype=torch.float64, device=self.dev)
+        self.lib.vc_consensus_score(_stream(), B, 1, P(rv.head[B + 1:]), P(rv.head[:B + 1]), P(rv.off), P(rv.nnz), P(rv.keys), P(rv.w),
+                                    P(rv.norm), P(rv.words), P(cv.head), int(max_cands), P(cv.off), P(cv.nnz), P(cv.keys), P(cv.w),
+                                    P(cv.norm), P(cv.words), MAX_REFS, P(out))
+        return out
+
+    def evaluate(self, candidates):
+        B = self.B
+        if len(candidates) != B:
+            raise ValueError("%d images of candidates for %d images of references" % (len(candidates), B))
+        per = np.fromiter((len(c) for c in candidates), np.int64, B)
+        if per.max() > DIVERSE_MAX_DRAWS:
+            raise ValueError("at most %d captions per image (image %d has %d)" % (DIVERSE_MAX_DRAWS, int(np.argmax(per)), per.max()))
+        cand_img = np.zeros(B + 1, np.int64)
+        cand_img[1:] = np.cumsum(per)
+        C = int(cand_img[-1])
+        image_of = np.repeat(np.arange(B), per)
+        flat = [c for cs in candidates for c in cs]
+        W, L = word_rows(flat, self.bos, self.eos, owner=lambda i: "caption %d of image %d" % (i - cand_img[image_of[i]], image_of[i]))
+        W = W.astype(np.int32)
+        rows = np.arange(C)
+        start, end = cand_img[image_of], cand_img[image_of + 1]
+        if C:
+            # ---- device: one hypothesis table, three overlap calls, the CIDEr-D path; one copy-back of the integers
+            hyp = count_vectors(self.lib, self.dev, W, L, self.bos, self.eos)
+            none = np.full(C, -1)
+            rng = upload(self.dev, np.stack([self.ref_off[image_of], self.ref_off[image_of + 1], none,      # the image's references
+                                             start, rows, none,                                             # its earlier captions
+                                             start, end, rows]).astype(np.int32).reshape(3, 3 * C))         # its other captions
+            out = torch.empty((3, OUT_COLS * C), dtype=torch.int32, device=self.dev)
+            for i, ref in enumerate((self.ref_counts, hyp, hyp)):
+                _launch(self.lib, hyp, ref, rng[i], out[i])
+            cider_dev = self._cider(W, L, cand_img, int(per.max()))
+            ints = out.cpu().numpy()
+            cider = cider_dev.cpu().numpy()[:C]
+            to_ref, to_prev, to_rest = (_split(ints[i], C) for i in range(3))
+        else:
+            cider = np.zeros(0, np.float64)
+            to_ref = to_prev = to_rest = _split(np.zeros(0, np.int32), 0)
+        # ---- host: float64 from exact integers
+        have = per > 0
+        top = cand_img[:-1][have]
+        bleu = corpus_bleu(to_ref["match"][top].sum(axis=0, dtype=np.int64), to_ref["total"][top].sum(axis=0, dtype=np.int64),
+                           L[top].sum(), to_ref["ref_len"][top].sum(dtype=np.int64))
+        best = np.array([cider[cand_img[b]:cand_img[b + 1]].max() if per[b] else np.nan for b in range(B)], np.float64)
+        top_cider = np.full(B, np.nan)
+        top_cider[have] = cider[top]
+        # distinct word sequences per image: rows are 0-padded, so equal rows are equal captions
+        uniq = np.unique(np.column_stack([image_of, W]), axis=0)[:, 0] if C else np.zeros(0, np.int64)
+        n_distinct = np.bincount(uniq, minlength=B)
+        share = np.full(B, np.nan)
+        share[have] = n_distinct[have] / per[have]
+        words = np.bincount(image_of, weights=L, minlength=B)
+        div = np.full((2, B), np.nan)
+        for n in range(2):
+            new = np.bincount(image_of, weights=to_prev["unseen"][:, n], minlength=B) if C else np.zeros(B)
+            div[n][words > 0] = new[words > 0] / words[words > 0]
+        multi = per[image_of] >= 2
+        mbleu = corpus_bleu(to_rest["match"][multi].sum(axis=0, dtype=np.int64), to_rest["total"][multi].sum(axis=0, dtype=np.int64),
+                            L[multi].sum(), to_rest["ref_len"][multi].sum(dtype=np.int64))
+        novel = None
+        if self.train is not None:
+            novel = (sum(W[i, :L[i]].tobytes() not in self.train for i in range(C)) / C) if C else 0.0
+        res = dict(bleu_1=bleu[0], bleu_2=bleu[1], bleu_3=bleu[2], bleu_4=bleu[3], cider_d=_mean(top_cider[have]),
+                   oracle_cider_d=_mean(best[have]), mean_cider_d=_mean(cider), distinct=_mean(share[have]), div_1=_mean(div[0][words > 0]),
+                   div_2=_mean(div[1][words > 0]), mbleu_4=mbleu[3], novel=novel)
+        res["per_image"] = dict(captions=per, cider_d=top_cider, oracle_cider_d=best, distinct=share, div_1=div[0], div_2=div[1],
+                                caption_cider_d=[cider[cand_img[b]:cand_img[b + 1]].copy() for b in range(B)])
+        return res

@@ -12,7 +12,12 @@ the consensus scores; with `"marginal"` they hold each caption's likelihood over
 `sample_gen == "diverse_beam"` (additive): group beam search (`decoder.diverse_beam_search`), written the same way: the merged ranked
 captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one in `./val_{gen_name}.json`.
 `params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
-(`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed."""
+(`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed.
+`params.eval_captions` (additive): what was decoded for the validation images (`decoder.last_token_ids`: the whole ranked list of an
+image in the diverse modes, a list of one otherwise) is evaluated against ALL human captions of each image (taken from the generator's
+caption table by image id, `validation_references`: the batches carry one random caption per image) (`decoder.caption_evaluator`,
+evaluate.py: BLEU, CIDEr-D, oracle and diversity metrics) once after the loop -> `./val_{gen_name}_metrics.json`, one printed line
+per metric.  The caption files are written exactly as without the flag."""
 import json
 import math
 import os
@@ -60,6 +65,57 @@ def store_scores(params, score_records):
     print("Held-out perplexity of the human captions under %d prior draws: %.17g" % (params.score_draws, perplexity(score_records)))
 
 
+EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
+              "beam_diversity", "top_k", "top_p")
+
+
+def store_metrics(params, metrics, images, captions):
+    """./val_{gen_name}_metrics.json: the evaluator's dict without its per-image arrays, the number of images and of captions evaluated,
+    sample_gen and the decoding flags in force; one printed line per metric."""
+    from ..evaluate import METRICS
+    out = {k: metrics[k] for k in METRICS}
+    out.update(images=int(images), captions=int(captions), sample_gen=params.sample_gen)
+    out.update({k: getattr(params, k) for k in EVAL_FLAGS if hasattr(params, k)})
+    path = "./val_{}_metrics.json".format(params.gen_name)
+    if os.path.exists(path):
+        os.remove(path)
+    with open(path, "w") as fh:
+        json.dump(out, fh)
+    for k in METRICS:
+        print("%s: %s" % (k, "n/a (no training captions at hand)" if out[k] is None else "%.6f" % out[k]))
+    print("wrote the metrics of %d captions of %d images to %s" % (captions, images, path))
+    return out
+
+
+def validation_references(val_gen):
+    """--eval_captions: {image id: every human caption of the image} of a Batch_Generator (consensus.references_from_generator).  Its
+    validation batches carry ONE randomly drawn caption per image, which is no reference set: BLEU's clipping and closest length and
+    CIDEr-D's idf need all of an image's captions, and the numbers must not depend on the generator's random state.  None for a
+    generator that holds no captions by file name (then the batches' own captions are all there is)."""
+    if not (hasattr(val_gen, "_iterable") and hasattr(val_gen, "_imid") and getattr(val_gen, "captions", None) is not None):
+        return None
+    from ..consensus import references_from_generator
+    return references_from_generator(val_gen)
+
+
+def decoded_ids(decoder, n):
+    """what the generation call just made left in decoder.last_token_ids: per image its ranked token-id lists"""
+    ids = getattr(decoder, "last_token_ids", None)
+    if ids is None or len(ids) != n:
+        raise RuntimeError("--eval_captions: the decoder left no token ids of the %d images it has just decoded in last_token_ids" % n)
+    return ids
+
+
+def evaluate_decoded(params, decoder, references, decoded):
+    """--eval_captions: evaluate once what was decoded (per image its ranked token-id lists) against the images' human captions and
+    store the metrics.  Images without a human caption cannot be scored and are left out."""
+    keep = [i for i, r in enumerate(references) if r]
+    if len(keep) < len(references):
+        print("%d images without a human caption are not evaluated" % (len(references) - len(keep)))
+    references, decoded = [references[i] for i in keep], [decoded[i] for i in keep]
+    return store_metrics(params, decoder.caption_evaluator(references).evaluate(decoded), len(decoded), sum(map(len, decoded)))
+
+
 def _store(path, records):
     if os.path.exists(path):
         os.remove(path)
@@ -86,8 +142,16 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
     val_cv = params.use_c_v or params.prior in ("GMM", "AG")
     records, scores = [], []
     n_score = int(getattr(params, "score_draws", 0) or 0)
+    evaluate = bool(getattr(params, "eval_captions", False))
+    references, decoded = [], []
+    all_refs = validation_references(val_gen) if evaluate else None
     for images, caps, lens, ids, c_v in val_gen.next_val_batch(get_image_ids=True, use_obj_vectors=params.use_c_v):
+        if evaluate:
+            decoder.last_token_ids = None
         records += _decode(decoder, params, sess, image_f_inputs, ids, images, _cluster_rows(c_v, val_cv), allow_beam=True)
+        if evaluate:
+            references += [all_refs[i] for i in ids] if all_refs is not None else human_captions(caps, lens)
+            decoded += decoded_ids(decoder, len(ids))
         if n_score:
             scores += decoder.score_captions(ids, images, human_captions(caps, lens), _cluster_rows(c_v, val_cv), draws=n_score)
     if n_score:
@@ -96,6 +160,8 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
         _store("./val_{}_diverse.json".format(params.gen_name), records)
         records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]
     _store("./val_{}.json".format(params.gen_name), records)
+    if evaluate:
+        evaluate_decoded(params, decoder, references, decoded)
     if test_gen is None:
         return
     records = []

@@ -26,7 +26,7 @@ _DEFAULTS = dict(
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
-    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0,
+    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -50,7 +50,7 @@ _FLAGS = [
     ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal"]), ("--consensus_k", "consensus_k", int, None),
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
-    ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None),
+    ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -72,7 +72,9 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                              "has just taken it (>= 0; default 0.5)",
          "--top_k": "--sample_gen sample / --diverse_method sample: draw each word from the k most likely only (>= 0; default 0 = all)",
          "--top_p": "--sample_gen sample / --diverse_method sample: draw each word from the smallest set of most likely words that holds "
-                    "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)"}
+                    "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)",
+         "--eval_captions": "--mode inference: also evaluate the validation captions against the images' human captions on the GPU (BLEU, "
+                            "CIDEr-D, oracle CIDEr-D, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json"}
 
 
 class Parameters(object):
@@ -123,6 +125,8 @@ class Parameters(object):
             ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
         if not (0.0 < self.top_p <= 1.0):
             ap.error("--top_p must be in (0, 1] (got %r)" % self.top_p)
+        if self.eval_captions and self.mode != "inference":
+            ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.synthetic:
             self.vocab_size = int(args["vocab"]) if args["vocab"] is not None else 10000
         self.hdf5_file = self.coco_dir + os.path.basename(self.hdf5_file)  # the image array lives next to the data set

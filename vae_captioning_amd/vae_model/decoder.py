@@ -23,6 +23,9 @@ class Decoder(object):
         self.c_i_ph = None
         self.cap_clusters = None
         self.consensus_index = None  # consensus.ConsensusIndex: --diverse_rerank consensus re-ranks diverse captions against it
+        self.last_token_ids = None   # per image of the last generation call its ranked token-id lists (what --eval_captions evaluates);
+                                     # every generation method clears it first, so a call that fails leaves None, never older ids
+        self.train_captions = None   # flat token-id lists of the training captions: `novel` of caption_evaluator (None: not reported)
 
     def px_z_fi(self, observed, gen_mode=False):
         """Training graph: returns (model, x_logits, shpe, (initial_state, final_state, sample)) like
@@ -64,6 +67,7 @@ class Decoder(object):
 
     def online_inference(self, sess, picture_ids, in_pictures, image_f_inputs, stop_word="<EOS>", c_v=None):
         """decoder.py:145-201.  Returns (cap_list, cap_raw)."""
+        self.last_token_ids = None
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx[stop_word]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
@@ -76,11 +80,13 @@ class Decoder(object):
         for pid, toks in zip(picture_ids, raw):
             words = [d.idx2word[t] for t in toks if t not in (bos, eos)]
             cap_list.append({"image_id": pid, "caption": " ".join(words)})
+        self.last_token_ids = [[list(toks)] for toks in raw]
         return cap_list, raw
 
     def beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, beam_size=2, ret_beams=False,
                     len_norm_f=0.7):
         """decoder.py:203-320.  Returns cap_list."""
+        self.last_token_ids = None
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
@@ -90,6 +96,7 @@ class Decoder(object):
         for pid, beams in zip(picture_ids, res):
             texts = [" ".join(d.idx2word[t] for t in s if t not in (bos, eos)) for s, _ in beams]
             cap_list.append({"image_id": pid, "caption": texts if ret_beams else texts[0]})
+        self.last_token_ids = [[list(s) for s, _ in (beams if ret_beams else beams[:1])] for beams in res]
         return cap_list
 
     def diverse_inference(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, draws=None, method=None, n_best=None,
@@ -103,6 +110,7 @@ class Decoder(object):
         "caption" is the consensus winner.  params.diverse_rerank == "marginal": the distinct captions are ordered by their likelihood
         over ALL draws of the image (generate.py: diverse(rerank="marginal")); "scores" are those scores and the records gain "marginal"
         (aligned with "captions")."""
+        self.last_token_ids = None
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
@@ -129,6 +137,7 @@ class Decoder(object):
             if marginal:
                 rec["marginal"] = [float(e[3]) for e in entries]
             cap_list.append(rec)
+        self.last_token_ids = [[list(e[0]) for e in entries] for entries in res]
         return cap_list
 
     def diverse_beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, beam_size=None, groups=None, diversity=None,
@@ -139,6 +148,7 @@ class Decoder(object):
         their best score and ranked.  Returns cap_list in diverse_inference's record shape: per image {"image_id", "caption": the
         best text, "captions": [texts], "scores": [...], "counts": [groups that produced the caption], "groups": [[group ids]]}."""
         from ..generate import merge_groups
+        self.last_token_ids = None
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
@@ -149,13 +159,15 @@ class Decoder(object):
             raise ValueError("diverse_beam_search: beam_size must be a multiple of groups and at most 16 (got %d and %d)" % (total, G))
         res = self._gen().diverse_beam_search(self._features(in_pictures), use_cv, None, bos, eos, groups=G, group_size=total // G,
                                               diversity=lam, max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
-        cap_list = []
+        cap_list, token_ids = [], []
         for pid, per_group in zip(picture_ids, res):
             entries = merge_groups(per_group)
+            token_ids.append([list(e[0]) for e in entries])
             texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
             cap_list.append({"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
                              "scores": [float(e[1]) for e in entries], "counts": [len(e[2]) for e in entries],
                              "groups": [[int(g) for g in e[2]] for e in entries]})
+        self.last_token_ids = token_ids
         return cap_list
 
     def score_captions(self, picture_ids, in_pictures, captions, c_v=None, draws=None):
@@ -169,3 +181,11 @@ class Decoder(object):
         res = self._gen().score(self._features(in_pictures), captions, use_cv, None, bos, eos, draws=draws)
         return [{"image_id": pid, "captions": [{"tokens": int(r["tokens"]), "marginal": float(r["marginal"]), "logprob": float(np.mean(r["logprob"]))}
                                                for r in rs]} for pid, rs in zip(picture_ids, res)]
+
+    def caption_evaluator(self, references):
+        """evaluate.CaptionEvaluator of the images whose human captions are `references` (per image a list of token-id lists), on this
+        decoder's engine and dictionary; `novel` is reported against self.train_captions when those are set."""
+        from ..evaluate import CaptionEvaluator
+        d = self.data_dict
+        return CaptionEvaluator(session.get(self.params).cap, references, d.word2idx["<BOS>"], d.word2idx["<EOS>"],
+                                vocab_size=d.vocab_size, train_captions=self.train_captions)
