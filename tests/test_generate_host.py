@@ -7,13 +7,19 @@ order, both sentence parities."""
 import numpy as np
 import pytest
 
-from vae_captioning_amd.generate import beams_from_host
+from vae_captioning_amd.generate import FieldLayout, beam_fields, beams_from_host
 from vae_captioning_amd.utils.top_n import Beam, TopN
+
+
+def _sizes(B, n, L):
+    """the int32 result buffer of a beam-search slice, spelt out here independently of generate.beam_fields"""
+    M = B * n
+    return [("pcount", B), ("ccount", B), ("p_len", M), ("c_len", M), ("c_slot", M), ("sent0", M * L), ("sent1", M * L), ("c_sent", B * (n + 1) * L)]
 
 
 def _buffers(rng, B, n, L, complete):
     M = B * n
-    sizes = [("pcount", B), ("ccount", B), ("p_len", M), ("c_len", M), ("c_slot", M), ("sent0", M * L), ("sent1", M * L), ("c_sent", B * (n + 1) * L)]
+    sizes = _sizes(B, n, L)
     io, o = {}, 0
     for name, sz in sizes:
         io[name] = o
@@ -57,3 +63,27 @@ def test_result_buffers_become_the_lists_the_reference_returns(B, n, L, last, co
     ref = _reference(ints, dbls, io, B, n, L, last)
     assert got == ref
     assert all(isinstance(t, int) for img in got for s, _ in img for t in s) and all(isinstance(sc, float) for img in got for _, sc in img)
+
+
+@pytest.mark.parametrize("fields", [[], [("a", 3)], [("a", 2), ("none", 0), ("b", 5), ("c", 1)], [("none", 0), ("a", 4), ("tail", 0)]],
+                         ids=["empty", "one", "zero-sized-inside", "zero-sized-ends"])
+def test_field_layout_packs_the_fields_back_to_back(fields):
+    lay = FieldLayout(fields)
+    sizes = [n for _, n in fields]
+    assert lay.total == sum(sizes)
+    assert [lay.off[name] for name, _ in fields] == [sum(sizes[:j]) for j in range(len(sizes))]   # the running sum: no padding
+    buf = np.zeros(lay.total, np.int32)
+    views = lay.views(buf)
+    assert list(views) == [name for name, _ in fields] and [v.size for v in views.values()] == sizes
+    for j, v in enumerate(views.values()):   # views of buf itself, disjoint: every element is written exactly once ...
+        v += j + 1
+    assert buf.tolist() == [j + 1 for j, n in enumerate(sizes) for _ in range(n)]   # ... and together they cover the buffer, in order
+
+
+@pytest.mark.parametrize("B,n,L", [(1, 1, 3), (3, 4, 7)])
+def test_beam_fields_are_the_buffer_the_host_end_reads(B, n, L):
+    assert beam_fields(B, n, L) == _sizes(B, n, L)
+    lay = FieldLayout(beam_fields(B, n, L))
+    rng = np.random.default_rng(B + n)
+    ints, dbls, io = _buffers(rng, B, n, L, "mixed")
+    assert lay.off == io and lay.total == ints.size

@@ -17,7 +17,7 @@ from vae_captioning_amd.generate import CaptionGenerator
 from vae_captioning_amd.utils.parameters import Parameters
 
 from .test_diverse_host import rank_rule
-from .test_gpu_generate import setup
+from .test_gpu_generate import count_replays, replayed_kinds, setup, whole_chunks
 
 pytestmark = pytest.mark.gpu
 BOS, EOS = 1, 2
@@ -322,3 +322,45 @@ def test_main_synthetic_inference_with_diverse_captions(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     recs = json.load(open(tmp_path / "val_dv.json"))
     assert len(recs) == 8 and all(sum(x["counts"]) == 4 for x in recs)
+
+
+def _diverse_args(p, feats, method, max_len, K=3):
+    rng = np.random.default_rng(41)
+    eps = _eps(rng, p, K, feats.shape[0])
+    U = rng.random((K, max_len, feats.shape[0])).astype(np.float32) if method == "sample" else None
+    return dict(eps=eps, bos=BOS, eos=EOS, draws=K, method=method, max_len=max_len, uniforms=U)
+
+
+@pytest.mark.parametrize("max_len,check_every", [(10, 4), (10, 2), (3, 4)], ids=["chunks-of-4", "chunks-of-2", "shorter-than-a-chunk"])
+@pytest.mark.parametrize("method", ["greedy", "sample"])
+@pytest.mark.parametrize("seed", [23, 19], ids=["to-max-len", "early-exit"])   # (seed 19: every greedy candidate ends within three tokens)
+def test_second_call_replays_the_init_graph_and_every_whole_chunk(lib, seed, method, max_len, check_every, monkeypatch):
+    """As tests/test_gpu_generate.py pins it for greedy(): the second diverse() call of a shape captures nothing and replays
+    _diverse_init's graph, then one chunk graph per whole chunk of `check_every` rounds up to the early exit."""
+    p, eng, gen, P64, feats, cv, _, cm = setup(lib, seed, prior="GMM")
+    kw = _diverse_args(p, feats, method, max_len)
+    replayed = count_replays(monkeypatch)
+    first = gen.diverse(feats, None, check_every=check_every, **kw)
+    graphs = dict(gen._graphs)
+    assert sorted(k[0] for k in graphs) == ["diverse", "dvinit"]
+    replayed.clear()
+    assert gen.diverse(feats, None, check_every=check_every, **kw) == first
+    assert gen._graphs == graphs, "an identical second call captures nothing new"
+    cands = [c for img in gen.last_candidates for c in img]
+    n = whole_chunks([len(t) for t, _, _ in cands], [en for _, _, en in cands], max_len, check_every)
+    print("diverse %s max_len %d check_every %d: longest %d, %d chunk replays expected, replayed %s"
+          % (method, max_len, check_every, max(len(t) for t, _, _ in cands), n, replayed_kinds(gen, replayed)))
+    assert n <= max_len // check_every and (n >= 1 or max_len < check_every)
+    assert replayed_kinds(gen, replayed) == ["dvinit"] + ["diverse"] * n
+
+
+@pytest.mark.parametrize("method", ["greedy", "sample"])
+def test_with_graphs_off_nothing_is_captured_or_replayed(lib, method, monkeypatch):
+    p, eng, gen, P64, feats, cv, _, cm = setup(lib, 23, prior="GMM")
+    kw = _diverse_args(p, feats, method, 10)
+    on = [(gen.diverse(feats, None, check_every=4, **kw), gen.last_candidates) for _ in range(2)]
+    monkeypatch.setenv("VC_DECODE_GRAPH", "0")
+    replayed = count_replays(monkeypatch)
+    g = CaptionGenerator(eng)
+    assert [(g.diverse(feats, None, check_every=4, **kw), g.last_candidates) for _ in range(2)] == on
+    assert replayed == [] and len(g._graphs) == 0

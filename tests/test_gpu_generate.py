@@ -423,3 +423,60 @@ def test_beam_chunk_captured_after_the_first_round_grew_the_workspace_is_replaye
     eps2 = rng.standard_normal(eps.shape).astype(np.float32)
     third = run(gen, feats2, eps2)
     assert third == run(CaptionGenerator(eng), feats2, eps2) and third != first
+
+
+def count_replays(monkeypatch):
+    """Every hipGraph replayed from here on, in order.  (Patched on the class: see tests/test_gpu_score.py on reference cycles.)"""
+    import torch
+    replayed = []
+    replay = torch.cuda.CUDAGraph.replay
+    monkeypatch.setattr(torch.cuda.CUDAGraph, "replay", lambda g: (replayed.append(g), replay(g))[1])
+    return replayed
+
+
+def whole_chunks(lengths, ended, max_len, K):
+    """Chunks of K rounds that a decode of at most max_len rounds replays, from what it returned: the host stops after the first chunk at
+    whose end every row has emitted <EOS> (rows that never did are max_len long); rounds past the last whole chunk run eagerly."""
+    rounds = min(max_len, -(-max(lengths) // K) * K) if all(ended) else max_len
+    assert max(lengths) <= rounds
+    return rounds // K
+
+
+def replayed_kinds(gen, replayed):
+    kind = {id(g): k[0] for k, g in gen._graphs.items()}
+    return [kind.get(id(g)) for g in replayed]
+
+
+@pytest.mark.parametrize("max_len,check_every", [(10, 4), (10, 2), (3, 4)], ids=["chunks-of-4", "chunks-of-2", "shorter-than-a-chunk"])
+@pytest.mark.parametrize("seed", [13, 19], ids=["to-max-len", "early-exit"])   # (seed 19: every image emits <EOS> in its first two tokens)
+def test_greedy_second_call_replays_the_init_graph_and_every_whole_chunk(lib, seed, max_len, check_every, monkeypatch):
+    """The graph path is TAKEN (the outputs cannot tell: the eager loop gives the same ids): the second call of a shape captures nothing
+    and replays init_state's graph, then one chunk graph per whole chunk of `check_every` rounds up to the early exit -- at max_len 10
+    and chunks of 4 two of them with the ragged last two rounds eager, none at all when max_len is shorter than a chunk."""
+    p, eng, gen, P64, feats, cv, eps, cm = setup(lib, seed, prior="GMM")
+    replayed = count_replays(monkeypatch)
+    first = gen.greedy(feats, None, eps, BOS, EOS, max_len=max_len, check_every=check_every)
+    graphs = dict(gen._graphs)
+    assert sorted(k[0] for k in graphs) == ["greedy", "init"]
+    replayed.clear()
+    assert gen.greedy(feats, None, eps, BOS, EOS, max_len=max_len, check_every=check_every) == first
+    assert gen._graphs == graphs, "an identical second call captures nothing new"
+    n = whole_chunks([len(t) for t in first], [t[-1] == EOS for t in first], max_len, check_every)
+    print("greedy max_len %d check_every %d: lengths %s, %d chunk replays expected, replayed %s"
+          % (max_len, check_every, [len(t) for t in first], n, replayed_kinds(gen, replayed)))
+    assert n <= max_len // check_every and (n >= 1 or max_len < check_every)
+    assert replayed_kinds(gen, replayed) == ["init"] + ["greedy"] * n
+    if max_len < check_every:   # every round ran eagerly
+        for b in range(feats.shape[0]):
+            assert first[b] == od.greedy(P64, p, feats[b].astype(np.float64), cv[b].astype(np.float64), eps[:, b:b + 1].astype(np.float64),
+                                         BOS, EOS, c_means=cm, max_len=max_len)
+
+
+def test_greedy_with_graphs_off_captures_and_replays_nothing(lib, monkeypatch):
+    p, eng, gen, P64, feats, cv, eps, cm = setup(lib, 13, prior="GMM")
+    on = [gen.greedy(feats, None, eps, BOS, EOS, max_len=10, check_every=4) for _ in range(2)]
+    monkeypatch.setenv("VC_DECODE_GRAPH", "0")
+    replayed = count_replays(monkeypatch)
+    g = CaptionGenerator(eng)
+    assert [g.greedy(feats, None, eps, BOS, EOS, max_len=10, check_every=4) for _ in range(2)] == on
+    assert replayed == [] and len(g._graphs) == 0

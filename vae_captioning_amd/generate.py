@@ -69,6 +69,26 @@ def beams_from_host(ints, dbls, io, B, n, L, last):
     return res
 
 
+class FieldLayout(object):
+    """Named fields packed back to back in ONE flat buffer (no padding): fields = [(name, size), ...] in buffer order, off[name] = where
+    a field starts, total = the buffer's length, views(buf) = {name: its slice of buf}.  The device fills the fields, one copy brings
+    the buffer back, the host reads by offset."""
+    def __init__(self, fields):
+        self.fields, self.off, self.total = list(fields), {}, 0
+        for name, n in self.fields:
+            self.off[name], self.total = self.total, self.total + n
+
+    def views(self, buf):
+        return {name: buf[self.off[name]:self.off[name] + n] for name, n in self.fields}
+
+
+def beam_fields(B, n, L):
+    """(name, size) of the int32 result buffer of a beam-search slice of B images x n beams, sentences of <= L tokens, in buffer order
+    (what beams_from_host reads).  The float64 buffer holds p_score, c_score, p_logprob, c_logprob, [B, n] each."""
+    M = B * n
+    return [("pcount", B), ("ccount", B), ("p_len", M), ("c_len", M), ("c_slot", M), ("sent0", M * L), ("sent1", M * L), ("c_sent", B * (n + 1) * L)]
+
+
 DIVERSE_MAX_DRAWS = 256   # vc_diverse_rank: one workgroup of 256 lanes per image, one lane per draw
 
 
@@ -186,10 +206,10 @@ class CaptionGenerator(object):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.e.dev)
 
     def _load(self, dst, a):
-        """host array or tensor -> the persistent device buffer dst (same shape)"""
+        """host array or tensor -> the persistent device buffer dst (same shape), which it returns"""
         if not isinstance(a, torch.Tensor):
             a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-        dst.copy_(a.reshape(dst.shape), non_blocking=True)
+        return dst.copy_(a.reshape(dst.shape), non_blocking=True)
 
     def prior_mean(self, c_v):
         """decoder.py:42-71: zeros, or for the AG prior the mean of the image's cluster means
@@ -209,6 +229,46 @@ class CaptionGenerator(object):
         return out
 
     # ------------------------------------------------------------------ init chain
+    def _image_rows(self, tag, n, features, c_v, z_rows):
+        """What both init chains do on their B image rows, n LSTM steps long: features, cluster vectors and AG prior means (host-computed) go
+        into the persistent buffers feats, cv, pmd (None where the model has none), the workspace is sized (z_rows: rows of the z_rnn
+        product), and two launch lists are made: embed(tg), X[0] = imf_emb(features), X[1] = cv_emb(c_v); lstm(st), the n steps over X from
+        a zero state, to cs[n] / hs[n].  Returns them all (a captured chain bakes the buffers' addresses)."""
+        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        B, E, Hd, F = int(features.shape[0]), p.embed_size, p.decoder_hidden, p.cnn_feature_size
+        feats = self._load(self._b(tag + "feats", (B, F)), features)
+        cv = self._load(self._b(tag + "cv", (B, K_CL)), c_v) if e.feed_cv else None
+        pm = self.prior_mean(np.asarray(c_v) if c_v is not None else None) if e.enc else None
+        pmd = self._load(self._b(tag + "pm", (B, p.latent_size)), pm) if pm is not None else None
+        X, act = self._b(tag + "X", (n, B, E)), self._b(tag + "act0", (n, B, 4 * Hd))
+        cs, hs, lens = self._b(tag + "cs0", (n + 1, B, Hd)), self._b(tag + "hs0", (n + 1, B, Hd)), self._ones_for(B, n)
+        e._need_ws(lib.vc_lstm_seq_workspace_bytes(n, B, E, Hd))
+        for sh in ((B, E, F), (B, E, K_CL), (z_rows, E, p.gen_z_samples * p.latent_size)):
+            e._need_ws(lib.vc_gemm_workspace_bytes(*sh))
+
+        def embed(tg):
+            e.gemm(0, 0, B, E, F, feats, F, S.param("imf_emb/kernel"), E, X[0], E, S.param("imf_emb/bias"), tag=tg)
+            if e.feed_cv:
+                e.gemm(0, 0, B, E, K_CL, cv, K_CL, S.param("cv_emb/kernel"), E, X[1], E, S.param("cv_emb/bias"), tag=tg)
+
+        def lstm(st):
+            lib.vc_fill_f32(st, P(cs[0]), B * Hd, 0.0)
+            lib.vc_fill_f32(st, P(hs[0]), B * Hd, 0.0)
+            lib.vc_lstm_seq_fwd_f32(st, n, B, E, Hd, P(X), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")),
+                                    P(lens), P(act), P(cs), P(hs), P(e.ws), e.ws_bytes, e.lstm_flags)
+
+        return types.SimpleNamespace(feats=feats, cv=cv, pmd=pmd, X=X, act=act, cs=cs, hs=hs, lens=lens, embed=embed, lstm=lstm)
+
+    def _replay_or_capture(self, key, launches):
+        """Replay the hipGraph of a launch list or, on the first call of its key, run it eagerly and capture it for the next (a capture
+        executes nothing: the eager launches are this call's).  launches(timed): timed = False inside the capture (no timer events)."""
+        graph = self._graphs.get(key)
+        if graph is not None:
+            graph.replay()
+        else:
+            launches(True)
+            self._capture(key, lambda: launches(False))
+
     def init_state(self, features, c_v=None, eps=None):
         """State after image -> (c_v) -> z (decoder.py:96-114), batched over B images.
         eps: [S, B, L] N(0,1) draws (generated on device when None).
@@ -217,40 +277,21 @@ class CaptionGenerator(object):
         they are ~50 us of kernels behind ~250 us of launch calls.  VC_DECODE_GRAPH=0 keeps the eager launches."""
         e, p, lib, S = self.e, self.p, self.lib, self.e.store
         B = int(features.shape[0])
-        E, Hd, L, Sm, F = p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples, p.cnn_feature_size
+        E, L, Sm = p.embed_size, p.latent_size, p.gen_z_samples
         n_init = e.n_init_d
         tag = "in%d_" % B
-        feats = self._b(tag + "feats", (B, F))
-        self._load(feats, features)
-        X = self._b(tag + "X", (n_init, B, E))
-        cv = epsd = mean = std = z = None
-        have_pm = False
-        if e.feed_cv:
-            cv = self._b(tag + "cv", (B, K_CL))
-            self._load(cv, c_v)
+        im = self._image_rows(tag, n_init, features, c_v, B)
+        pmd, have_pm = im.pmd, im.pmd is not None
+        epsd = mean = std = z = None
         if e.enc:
             z, epsd = self._b(tag + "z", (B, Sm, L)), self._b(tag + "eps", (B, Sm, L))
             if eps is not None:
                 self._load(epsd, np.transpose(np.asarray(eps, np.float32), (1, 0, 2)))
             mean, std = self._b(tag + "zmean", (B * Sm, L)), self._b(tag + "zstd", (B * Sm, L))
-            pm = self.prior_mean(np.asarray(c_v) if c_v is not None else None)
-            have_pm = pm is not None
-            if have_pm:
-                pmd = self._b(tag + "pm", (B, L))
-                self._load(pmd, pm)
-        act, cs, hs = self._b(tag + "act0", (n_init, B, 4 * Hd)), self._b(tag + "cs0", (n_init + 1, B, Hd)), self._b(tag + "hs0", (n_init + 1, B, Hd))
-        lens = self.buf.get(tag + "lens%d" % n_init)
-        if lens is None:
-            lens = self.buf[tag + "lens%d" % n_init] = torch.full((B,), n_init, dtype=torch.int32, device=e.dev)
-        e._need_ws(lib.vc_lstm_seq_workspace_bytes(n_init, B, E, Hd))
-        for sh in ((B, E, F), (B, E, K_CL), (B, E, Sm * L)):
-            e._need_ws(lib.vc_gemm_workspace_bytes(*sh))
 
         def launches(timed):
             st, tg = _stream(), ("gemm" if timed else None)
-            e.gemm(0, 0, B, E, F, feats, F, S.param("imf_emb/kernel"), E, X[0], E, S.param("imf_emb/bias"), tag=tg)
-            if e.feed_cv:
-                e.gemm(0, 0, B, E, K_CL, cv, K_CL, S.param("cv_emb/kernel"), E, X[1], E, S.param("cv_emb/bias"), tag=tg)
+            im.embed(tg)
             if e.enc:
                 if eps is None:
                     lib.vc_philox_normal_f32(st, P(epsd), epsd.numel(), e.seed * 1000003 + 17, 5 << 32, P(e.step))
@@ -260,21 +301,13 @@ class CaptionGenerator(object):
                     lib.vc_fill_f32(st, P(mean), mean.numel(), 0.0)
                 lib.vc_fill_f32(st, P(std), std.numel(), float(p.std))
                 lib.vc_latent_sample_f32(st, 1, B * Sm, L, P(mean), P(std), P(epsd), P(z))  # decoder.py:72-74
-                e.gemm(0, 0, B, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, X[n_init - 1], E, S.param("decoder/net/z_rnn/bias"), tag=tg)
-            lib.vc_fill_f32(st, P(cs[0]), B * Hd, 0.0)
-            lib.vc_fill_f32(st, P(hs[0]), B * Hd, 0.0)
-            lib.vc_lstm_seq_fwd_f32(st, n_init, B, E, Hd, P(X), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")),
-                                    P(lens), P(act), P(cs), P(hs), P(e.ws), e.ws_bytes, e.lstm_flags)
+                e.gemm(0, 0, B, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, im.X[n_init - 1], E, S.param("decoder/net/z_rnn/bias"), tag=tg)
+            im.lstm(st)
 
         key = self._graph_key("init", B, eps is None, have_pm, float(p.std), e.lstm_flags, e.seed,
-                              tensors=[feats, X, cv, epsd, mean, std, z, act, cs, hs, lens] + ([pmd] if have_pm else []))
-        graph = self._graphs.get(key)
-        if graph is not None:
-            graph.replay()
-        else:
-            launches(True)
-            self._capture(key, lambda: launches(False))   # (a capture executes nothing: the eager launches above are this call's)
-        return cs[n_init], hs[n_init]
+                              tensors=[im.feats, im.X, im.cv, epsd, mean, std, z, im.act, im.cs, im.hs, im.lens] + ([pmd] if have_pm else []))
+        self._replay_or_capture(key, launches)
+        return im.cs[n_init], im.hs[n_init]
 
     # ------------------------------------------------------------------ one decoder step
     def _round_bufs(self, tag, M):
@@ -284,11 +317,11 @@ class CaptionGenerator(object):
         return {"x": self._b(tag + "x", (M, E)), "gact": self._b(tag + "gact", (M, 4 * Hd)), "c2": self._b(tag + "c2", (M, Hd)),
                 "h2": self._b(tag + "h2", (M, Hd)), "logits": self._b(tag + "logits", (M, V))}
 
-    def _ones_for(self, M):
-        """[M] int32 ones: the "every row is active" lengths of a single decoder step (persistent: captured chunks bake the address)"""
-        t = self._ones.get(M)
+    def _ones_for(self, M, n=1):
+        """[M] int32 of n: the "every row runs n steps" lengths of an LSTM launch, 1 for a decoder step (persistent: captured graphs bake it)"""
+        t = self._ones.get((M, n))
         if t is None:
-            t = self._ones[M] = torch.ones((M,), dtype=torch.int32, device=self.e.dev)
+            t = self._ones[(M, n)] = torch.full((M,), n, dtype=torch.int32, device=self.e.dev)
         return t
 
     def _pack_wh(self, M):
@@ -355,6 +388,17 @@ class CaptionGenerator(object):
             t = self.buf[name] = torch.zeros(int(n), dtype=dtype).pin_memory()
         return t
 
+    def _to_host(self, tag, ibuf, dbuf, wait=True):
+        """A pass's flat result buffers (int32 fields or None, float64 companion) as numpy views of pinned memory: two non-blocking copies
+        and ONE stream synchronise (wait=False: left to a later call -- the slices of a beam search share one), no gathering launches."""
+        hosts = [None, None]
+        for j, (name, buf) in enumerate((("ihost", ibuf), ("dhost", dbuf))):
+            if buf is not None:
+                hosts[j] = self._pinned(tag + name, buf.numel(), buf.dtype).copy_(buf, non_blocking=True).numpy()
+        if wait:
+            torch.cuda.current_stream().synchronize()
+        return hosts
+
     def _pinned_alive(self, n):
         t = self.buf.get("bm_host_alive")
         if t is None or t.numel() < n:
@@ -394,6 +438,47 @@ class CaptionGenerator(object):
             self._graphs[key] = g
         return g
 
+    @staticmethod
+    def _chunk_rounds(check_every):
+        """rounds per captured chunk: check_every when it is even (the ping-ponged state then ends where it started), else 4"""
+        return int(check_every) if check_every and check_every % 2 == 0 else 4
+
+    def _round_state(self, tag, M, c0, h0):
+        """What step() needs for rounds over M rows that ping-pong the decoder state between two _round_bufs sets: the state before round 0
+        (c0, h0) lives in set B; round r reads set (B, A, B, ...) and writes the other.  Re-packs Wh (the weights may have been trained
+        since the last call).  Returns (sets, tensors): sets(r) = round r's (source, destination); tensors = what a captured round bakes."""
+        A, Bb = self._round_bufs(tag + "A_", M), self._round_bufs(tag + "B_", M)
+        Bb["c2"].copy_(c0); Bb["h2"].copy_(h0)
+        self._pack_wh(M)
+        return (lambda r: (Bb, A) if r % 2 == 0 else (A, Bb)), [self._ones_for(M)] + list(A.values()) + list(Bb.values())
+
+    def _run_chunks(self, kind_key, baked, one, reset, K, max_len, check_every, pending, after=lambda steps, k: None):
+        """The round loop of greedy() and diverse(): up to max_len rounds one(r, timed), r = the round's index in its chunk, as replays of
+        ONE hipGraph of K rounds while a whole chunk fits and eagerly for the ragged rest (VC_DECODE_GRAPH=0: throughout).  after(steps, k)
+        follows every chunk of k rounds; then, with check_every, the 4-byte read of `pending`: 0 once every row has ended.  The first call
+        of a key (kind_key + the addresses of `baked`, the packed Wh and the workspace) runs round 0 eagerly, since that may grow the
+        workspace: reset(), which restores what round 0 starts from, undoes it and the key is taken again.  Returns the rounds run."""
+        key = self._graph_key(*kind_key, tensors=baked)
+        reset()
+        if key not in self._graphs:
+            one(0, True)
+            reset()
+            key = self._graph_key(*kind_key, tensors=baked)
+        graph = self._capture(key, lambda: [one(r, False) for r in range(K)])
+        steps = 0
+        while steps < max_len:
+            k = min(K, max_len - steps)
+            if graph is not None and k == K:
+                graph.replay()
+            else:
+                for r in range(k):
+                    one(r, True)
+            after(steps, k)
+            steps += k
+            if steps < max_len and check_every and pending.item() == 0:
+                break
+        return steps
+
     # ------------------------------------------------------------------ greedy (online_inference)
     def _trim(self, ids, eos):
         """[steps, B] token ids -> per image the tokens up to and including its first <EOS>."""
@@ -414,48 +499,25 @@ class CaptionGenerator(object):
         max_len = max_len or self.p.gen_max_len
         c0, h0 = self.init_state(features, c_v, eps)
         B, V = c0.shape[0], e.V
-        dev = e.dev
-        K = int(check_every) if check_every and check_every % 2 == 0 else 4   # steps per captured chunk (even: the state ends where it started)
-        ids = torch.zeros((max_len, B), dtype=torch.int32, device=dev)
+        K = self._chunk_rounds(check_every)
+        ids = torch.zeros((max_len, B), dtype=torch.int32, device=e.dev)
         chunk = self._b("g_chunk", (K + 1, B), torch.int32)    # row 0: the token fed to the chunk's first step; rows 1..K: its outputs
         done, pending = self._b("g_done", (B,), torch.int32), self._b("g_pending", (1,))
-        A, Bb = self._round_bufs("gA_", B), self._round_bufs("gB_", B)
-        chunk.zero_(); done.zero_()
-        chunk[0].fill_(bos)
-        Bb["c2"].copy_(c0); Bb["h2"].copy_(h0)    # state before step 0 lives in set B; step r reads set (B, A, B, ...) and writes the other
+        sets, state = self._round_state("g", B, c0, h0)
+        chunk.zero_(); chunk[0].fill_(bos)
 
         def one(r, timed):
-            src, dst = (Bb, A) if r % 2 == 0 else (A, Bb)
+            src, dst = sets(r)
             logits, _, _ = self.step(chunk[r], src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)  # argmax(softmax**(1/t)/sum) == argmax(logits)
             lib.vc_argmax_rows_f32(_stream(), P(logits), B, V, V, P(chunk[r + 1]))
             lib.vc_eos_track_i32(_stream(), P(chunk[r + 1]), B, int(eos), P(done), P(pending))
 
-        # the first call of a shape runs one step eagerly (it sizes the workspace, whose address a captured chunk bakes; the chunk
-        # then repeats that step on unchanged inputs); every call re-packs Wh (the weights may have been trained since the last one)
-        self._pack_wh(B)
-        baked = [chunk, done, pending, self._ones_for(B)] + list(A.values()) + list(Bb.values())
-        key = self._graph_key("greedy", B, K, int(eos), tensors=baked)
-        if key not in self._graphs:
-            one(0, True)
-            done.zero_()
-            key = self._graph_key("greedy", B, K, int(eos), tensors=baked)   # (the first step may have sized the workspace)
-        graph = self._capture(key, lambda: [one(r, False) for r in range(K)])
-        steps = 0
-        while steps < max_len:
-            k = min(K, max_len - steps)
-            if graph is not None and k == K:
-                graph.replay()
-            else:
-                for r in range(k):
-                    one(r, True)
+        def keep(steps, k):   # the chunk's k tokens; its last one feeds the next chunk (a ragged chunk is the last: nothing follows it)
             ids[steps:steps + k].copy_(chunk[1:k + 1])
-            steps += k
-            if steps < max_len:
+            if steps + k < max_len:
                 chunk[0].copy_(chunk[k])
-                if k % 2:   # (an odd remainder can only be the last chunk; kept for completeness)
-                    Bb["c2"].copy_(A["c2"]); Bb["h2"].copy_(A["h2"])
-                if check_every and pending.item() == 0:
-                    break
+
+        steps = self._run_chunks(("greedy", B, K, int(eos)), [chunk, done, pending] + state, one, done.zero_, K, max_len, check_every, pending, keep)
         return self._trim(ids[:steps], eos)
 
     def sample(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, uniforms=None, check_every=4, top_k=0, top_p=1.0):
@@ -504,46 +566,27 @@ class CaptionGenerator(object):
         e, p, lib, S = self.e, self.p, self.lib, self.e.store
         B = int(features.shape[0])
         M = B * K
-        E, Hd, L, Sm, F = p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples, p.cnn_feature_size
+        E, Hd, L, Sm = p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples
         n_pre = e.n_init_d - int(e.enc)   # steps that depend on the image only
         tag = "dvi%d_%d_" % (B, K)
-        feats = self._b(tag + "feats", (B, F))
-        self._load(feats, features)
-        X = self._b(tag + "X", (n_pre, B, E))
-        cv = epsd = z = Xz = pmd = act1 = None
-        if e.feed_cv:
-            cv = self._b(tag + "cv", (B, K_CL))
-            self._load(cv, c_v)
+        im = self._image_rows(tag, n_pre, features, c_v, M)
+        pmd, cs0, hs0 = im.pmd, im.cs, im.hs
+        epsd = z = Xz = act1 = None
         if e.enc:
             z, Xz = self._b(tag + "z", (M, Sm, L)), self._b(tag + "Xz", (1, M, E))
             if eps is not None:
                 epsd = self._b(tag + "eps", (M, Sm, L))
                 self._load(epsd, np.transpose(np.asarray(eps, np.float32), (2, 0, 1, 3)))   # [K, S, B, L] -> rows b*K + k
-            pm = self.prior_mean(np.asarray(c_v) if c_v is not None else None)
-            if pm is not None:
-                pmd = self._b(tag + "pm", (B, L))
-                self._load(pmd, pm)
             act1 = self._b(tag + "act1", (1, M, 4 * Hd))
-        act0, cs0, hs0 = self._b(tag + "act0", (n_pre, B, 4 * Hd)), self._b(tag + "cs0", (n_pre + 1, B, Hd)), self._b(tag + "hs0", (n_pre + 1, B, Hd))
         cs1, hs1 = self._b(tag + "cs1", (2, M, Hd)), self._b(tag + "hs1", (2, M, Hd))
-        lens = self.buf.get(tag + "lens")
-        if lens is None:
-            lens = self.buf[tag + "lens"] = torch.full((B,), n_pre, dtype=torch.int32, device=e.dev)
         ones = self._ones_for(M)
-        e._need_ws(lib.vc_lstm_seq_workspace_bytes(n_pre, B, E, Hd))
         e._need_ws(lib.vc_lstm_seq_workspace_bytes(1, M, E, Hd))
-        for sh in ((B, E, F), (B, E, K_CL), (M, E, Sm * L)):
-            e._need_ws(lib.vc_gemm_workspace_bytes(*sh))
         W, bias = S.param(spec.DEC_CELL + "kernel"), S.param(spec.DEC_CELL + "bias")
 
         def launches(timed):
             st, tg = _stream(), ("gemm" if timed else None)
-            e.gemm(0, 0, B, E, F, feats, F, S.param("imf_emb/kernel"), E, X[0], E, S.param("imf_emb/bias"), tag=tg)
-            if e.feed_cv:
-                e.gemm(0, 0, B, E, K_CL, cv, K_CL, S.param("cv_emb/kernel"), E, X[1], E, S.param("cv_emb/bias"), tag=tg)
-            lib.vc_fill_f32(st, P(cs0[0]), B * Hd, 0.0)
-            lib.vc_fill_f32(st, P(hs0[0]), B * Hd, 0.0)
-            lib.vc_lstm_seq_fwd_f32(st, n_pre, B, E, Hd, P(X), P(W), P(bias), P(lens), P(act0), P(cs0), P(hs0), P(e.ws), e.ws_bytes, e.lstm_flags)
+            im.embed(tg)
+            im.lstm(st)
             dst = (cs1[0], hs1[0]) if e.enc else (cs1[1], hs1[1])
             lib.vc_tile_rows_f32(st, P(cs0[n_pre]), B, K, Hd, P(dst[0]))
             lib.vc_tile_rows_f32(st, P(hs0[n_pre]), B, K, Hd, P(dst[1]))
@@ -554,13 +597,8 @@ class CaptionGenerator(object):
                 lib.vc_lstm_seq_fwd_f32(st, 1, M, E, Hd, P(Xz), P(W), P(bias), P(ones), P(act1), P(cs1), P(hs1), P(e.ws), e.ws_bytes, e.lstm_flags)
 
         key = self._graph_key("dvinit", B, K, eps is None, pmd is not None, float(p.std), e.lstm_flags, e.seed,
-                              tensors=[feats, X, cv, epsd, z, Xz, pmd, act0, act1, cs0, hs0, cs1, hs1, lens, ones])
-        graph = self._graphs.get(key)
-        if graph is not None:
-            graph.replay()
-        else:
-            launches(True)
-            self._capture(key, lambda: launches(False))   # (a capture executes nothing: the eager launches above are this call's)
+                              tensors=[im.feats, im.X, im.cv, epsd, z, Xz, pmd, im.act, act1, cs0, hs0, cs1, hs1, im.lens, ones])
+        self._replay_or_capture(key, launches)
         return cs1[1], hs1[1]
 
     def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every, rerank="likelihood",
@@ -573,16 +611,10 @@ class CaptionGenerator(object):
         B = M // K
         i32 = torch.int32
         tag = "dv%d_%d_%d_" % (B, K, max_len)
-        fields = diverse_fields(B, K, max_len)
-        ibuf, dbuf = self._b(tag + "ibuf", (sum(n for _, n in fields),), i32), self._b(tag + "dbuf", (2 * M,), torch.float64)
-        io, o = {}, 0
-        for name, n in fields:
-            io[name] = o
-            o += n
-        f = {name: ibuf[io[name]:io[name] + n] for name, n in fields}
-        score, logprob = dbuf[:M], dbuf[M:]
+        lay, dlay = FieldLayout(diverse_fields(B, K, max_len)), FieldLayout([("score", M), ("logprob", M)])
+        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), torch.float64)
+        f, (score, logprob) = lay.views(ibuf), dlay.views(dbuf).values()
         tok, rnd, pending = self._b(tag + "tok", (M,), i32), self._b(tag + "round", (1,), i32), self._b(tag + "pending", (1,))
-        A, Bb = self._round_bufs(tag + "A_", M), self._round_bufs(tag + "B_", M)
         ud = None
         if method == "sample":
             ud = self._b(tag + "u", (max_len, M))
@@ -596,8 +628,10 @@ class CaptionGenerator(object):
         def reset():
             tok.fill_(bos); f["ended"].zero_(); f["len"].zero_(); logprob.zero_(); rnd.zero_()
 
+        sets, state = self._round_state(tag, M, c0, h0)
+
         def one(r, timed):
-            src, dst = (Bb, A) if r % 2 == 0 else (A, Bb)
+            src, dst = sets(r)
             logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
             if trunc:
                 lib.vc_decode_pick_trunc_f32(_stream(), P(logits), M, V, V, temp, top_k, top_p, P(ud), max_len, P(rnd), int(eos), P(tok),
@@ -607,39 +641,15 @@ class CaptionGenerator(object):
                                        P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob))
             lib.vc_decode_round_end_i32(_stream(), P(f["ended"]), M, P(pending), P(rnd))
 
-        Kc = int(check_every) if check_every and check_every % 2 == 0 else 4   # rounds per captured chunk (even: the state ends where it started)
-        self._pack_wh(M)
-        Bb["c2"].copy_(c0); Bb["h2"].copy_(h0)    # state before round 0 lives in set B; round r reads set (B, A, B, ...) and writes the other
-        baked = [tok, rnd, pending, ibuf, dbuf, ud, self._ones_for(M)] + list(A.values()) + list(Bb.values())
-        kargs = ("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p)   # (a captured chunk bakes the truncation)
-        key = self._graph_key(*kargs, tensors=baked)
-        if key not in self._graphs:   # (the first call of a shape runs one round eagerly: it sizes the workspace a captured chunk bakes)
-            reset()
-            one(0, True)
-            key = self._graph_key(*kargs, tensors=baked)
-        reset()
-        graph = self._capture(key, lambda: [one(r, False) for r in range(Kc)])
-        steps = 0
-        while steps < max_len:
-            k = min(Kc, max_len - steps)
-            if graph is not None and k == Kc:
-                graph.replay()
-            else:
-                for r in range(k):
-                    one(r, True)
-            steps += k
-            if steps < max_len and check_every and pending.item() == 0:
-                break
+        Kc = self._chunk_rounds(check_every)
+        self._run_chunks(("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p),   # (a captured chunk bakes the truncation)
+                         [tok, rnd, pending, ibuf, dbuf, ud] + state, one, reset, Kc, max_len, check_every, pending)
         lib.vc_diverse_rank(_stream(), M, B, K, max_len, P(f["seq"]), P(f["len"]), P(f["ended"]), P(logprob), float(len_norm_f),
                             P(f["n_distinct"]), P(f["rep"]), P(f["count"]), P(score))
-        ihost, dhost = self._pinned(tag + "ihost", ibuf.numel(), i32), self._pinned(tag + "dhost", dbuf.numel(), torch.float64)
-        ihost.copy_(ibuf, non_blocking=True)
-        dhost.copy_(dbuf, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
+        res, cands = diverse_from_host(*self._to_host(tag, ibuf, dbuf), lay.off, B, K, max_len, n_best if rerank != "marginal" else None, candidates=True)
         if rerank != "marginal":
-            return diverse_from_host(ihost.numpy(), dhost.numpy(), io, B, K, max_len, n_best, candidates=True)
+            return res, cands
         # re-score every distinct caption under ALL K draws of the pass: their initial states are still in _diverse_init's buffers
-        res, cands = diverse_from_host(ihost.numpy(), dhost.numpy(), io, B, K, max_len, None, candidates=True)
         caps = [[list(t) for t, _, _ in r] for r in res]
         self._t_score = _phase("", 0.0)
         _, marg = self._score_states(c0, h0, K, caps, bos)
@@ -663,29 +673,30 @@ class CaptionGenerator(object):
             return np.zeros((C, K), np.float64), np.zeros((C,), np.float64)
         N = C * K
         i32 = torch.int32
-        # int32 upload: parent [N], row lengths [N], caption lengths [C], step inputs [T, N], labels [T, N]
-        host = np.zeros(2 * N + C + 2 * T * N, np.int32)
-        o_len, o_clen, o_in, o_lab = N, 2 * N, 2 * N + C, 2 * N + C + T * N
+        # int32 upload: parent row, row lengths, caption lengths, step inputs [T, N], labels [T, N]
+        lay = FieldLayout([("parent", N), ("len", N), ("clen", C), ("tok_in", T * N), ("label", T * N)])
+        host = np.zeros(lay.total, np.int32)
+        h_parent, h_len, h_clen, h_in, h_lab = lay.views(host).values()
         toks_in, labels = np.zeros((T, C), np.int32), np.full((T, C), -1, np.int32)
         for c, (b, t) in enumerate(flat):
             n = len(t)
-            host[c * K:(c + 1) * K] = b * K + np.arange(K)
-            host[o_clen + c] = n
+            h_parent[c * K:(c + 1) * K] = b * K + np.arange(K)
+            h_clen[c] = n
             if n:
                 labels[:n, c] = t
                 toks_in[0, c] = bos
                 toks_in[1:n, c] = t[:n - 1]
-        host[o_len:o_len + N] = np.repeat(host[o_clen:o_clen + C], K)
-        host[o_in:o_in + T * N] = np.repeat(toks_in, K, axis=1).ravel()
-        host[o_lab:o_lab + T * N] = np.repeat(labels, K, axis=1).ravel()
+        h_len[:] = np.repeat(h_clen, K)
+        h_in[:] = np.repeat(toks_in, K, axis=1).ravel()
+        h_lab[:] = np.repeat(labels, K, axis=1).ravel()
         tag = "sc%d_%d_%d_" % (C, K, T)
         idx = self._b(tag + "idx", (host.size,), i32)
         idx.copy_(torch.from_numpy(host), non_blocking=False)
-        parent, lens, clen = idx[:N], idx[o_len:o_len + N], idx[o_clen:o_clen + C]
-        tin, lab = idx[o_in:o_in + T * N], idx[o_lab:o_lab + T * N]
+        parent, lens, clen, tin, lab = lay.views(idx).values()
         X, act = self._b("sc_X", (T, N, E)), self._b("sc_act", (T, N, 4 * Hd))
         cs, hs = self._b("sc_cs", (T + 1, N, Hd)), self._b("sc_hs", (T + 1, N, Hd))
-        lp, dbuf = self._b("sc_lp", (T * N,)), self._b(tag + "dbuf", (N + C,), torch.float64)
+        dlay = FieldLayout([("logprob", N), ("marginal", C)])
+        lp, dbuf = self._b("sc_lp", (T * N,)), self._b(tag + "dbuf", (dlay.total,), torch.float64)
         st = _stream()
         t_ph = _phase("score: init chain", self._t_score)
         lib.vc_beam_gather_f32(st, P(c0), P(h0), P(parent), N, Hd, P(cs[0]), P(hs[0]), None, None, V, 4 * Hd, None)
@@ -700,13 +711,19 @@ class CaptionGenerator(object):
         lib.vc_logits_logprob_f32(st, T * N, V, Hd, P(hs[1]), Hd, P(S.param("decoder/rnn_logits/kernel")), e.Vp,
                                   P(S.param("decoder/rnn_logits/bias")), P(lab), P(lp), P(e.ws), e.ws_bytes)
         t_ph = _phase("score: logits + log-probability", t_ph)
-        lib.vc_score_reduce_f64(st, P(lp), T, C, K, P(clen), P(dbuf[:N]), P(dbuf[N:]))
-        dhost = self._pinned(tag + "dhost", dbuf.numel(), torch.float64)
-        dhost.copy_(dbuf, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        out = dhost.numpy().copy()
+        logprob, marginal = dlay.views(dbuf).values()
+        lib.vc_score_reduce_f64(st, P(lp), T, C, K, P(clen), P(logprob), P(marginal))
+        logprob, marginal = dlay.views(self._to_host(tag, None, dbuf)[1].copy()).values()
         self._t_score = _phase("score: reduce + copy-back", t_ph)
-        return out[:N].reshape(C, K), out[N:]
+        return logprob.reshape(C, K), marginal
+
+    def _check_draws(self, K, eps, B):
+        """ValueError unless K latent draws per image are 1..DIVERSE_MAX_DRAWS and eps, when given, is [K, S, B, L] (score(), diverse())"""
+        want = (K, self.p.gen_z_samples, B, self.p.latent_size)
+        if not 1 <= K <= DIVERSE_MAX_DRAWS:
+            raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
+        if eps is not None and tuple(np.shape(eps)) != want:
+            raise ValueError("eps must be [draws, gen_z_samples, images, latent_size] = %s" % (want,))
 
     def score(self, features, captions, c_v=None, eps=None, bos=1, eos=2, draws=1):
         """How likely are given captions for their images: per image, per caption {"logprob": float64 [K], "marginal": float, "tokens": n}.
@@ -719,14 +736,10 @@ class CaptionGenerator(object):
         Passes: an image goes with all its captions and draws into one pass of <= score_rows row-steps (sequence rows x steps of its
         longest caption); an image that exceeds it alone gets a pass of its own.  ValueError: a token id outside [0, V), more than
         SCORE_MAX_TOKENS scored tokens (names image and caption), draws outside 1..DIVERSE_MAX_DRAWS, a wrong eps shape."""
-        K, p, V = int(draws), self.p, self.e.V
-        if not 1 <= K <= DIVERSE_MAX_DRAWS:
-            raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
-        B = int(features.shape[0])
+        K, V, B = int(draws), self.e.V, int(features.shape[0])
+        self._check_draws(K, eps, B)
         if len(captions) != B:
             raise ValueError("captions must hold one list of captions per image (%d images, %d lists)" % (B, len(captions)))
-        if eps is not None and tuple(np.shape(eps)) != (K, p.gen_z_samples, B, p.latent_size):
-            raise ValueError("eps must be [draws, gen_z_samples, images, latent_size] = %s" % ((K, p.gen_z_samples, B, p.latent_size),))
         caps = []
         for b, cl in enumerate(captions):
             row = []
@@ -786,19 +799,14 @@ class CaptionGenerator(object):
         top_k > 0 / top_p < 1 (method="sample" only): every draw's tokens come from the truncated distribution (the top_k best words and /
         or the smallest set of best words holding a share top_p of the probability; DESIGN.md "Truncated sampling"); log-likelihoods stay
         the model's, over the full vocabulary, so score() of a candidate under its own draw still returns its logprob."""
-        K = int(draws)
-        if not 1 <= K <= DIVERSE_MAX_DRAWS:
-            raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
+        K, B = int(draws), int(features.shape[0])
+        self._check_draws(K, eps, B)
         if method not in ("greedy", "sample"):
             raise ValueError("method must be 'greedy' or 'sample' (got %r)" % (method,))
         if rerank not in ("likelihood", "marginal"):
             raise ValueError("rerank must be 'likelihood' or 'marginal' (got %r)" % (rerank,))
         top_k, top_p = check_truncation(top_k, top_p, method)
-        p = self.p
-        max_len = int(max_len or p.gen_max_len)
-        B = int(features.shape[0])
-        if eps is not None and tuple(np.shape(eps)) != (K, p.gen_z_samples, B, p.latent_size):
-            raise ValueError("eps must be [draws, gen_z_samples, images, latent_size] = %s" % ((K, p.gen_z_samples, B, p.latent_size),))
+        max_len = int(max_len or self.p.gen_max_len)
         if uniforms is not None and tuple(np.shape(uniforms)) != (K, max_len, B):
             raise ValueError("uniforms must be [draws, max_len, images] = %s" % ((K, max_len, B),))
         if c_v is not None:
@@ -824,7 +832,7 @@ class CaptionGenerator(object):
         search of width n of its own; a row has kc = min(G*n, V) candidates and the round's bookkeeping is vc_beam_update_groups."""
         lib, e = self.lib, self.e
         B, Hd, V = int(c.shape[0]), self.p.decoder_hidden, e.V
-        M, dev = B * n, e.dev
+        M = B * n
         i32, f64 = torch.int32, torch.float64
         tag = "bm%d_%d_%dof%d_" % (n, L, k, nparts)
         kc = n
@@ -832,18 +840,15 @@ class CaptionGenerator(object):
             G, lam = int(groups[0]), float(groups[1])
             kc = min(G * n, V)
             tag = "bmg%d_%r_" % (G, lam) + tag   # (per setting: a captured chunk of one setting is never replayed for another)
-        pt = types.SimpleNamespace(B=B, M=M, k=k)
+        pt = types.SimpleNamespace(B=B, k=k)
         # everything the host reads at the end lives in TWO flat buffers (int32 fields, float64 scores): two copies into pinned memory
         # bring a slice's results back, with no gathering launches in between
-        sizes = [("pcount", B), ("ccount", B), ("p_len", M), ("c_len", M), ("c_slot", M), ("sent0", M * L), ("sent1", M * L), ("c_sent", B * (n + 1) * L)]
-        ibuf, dbuf = self._b(tag + "ibuf", (sum(sz for _, sz in sizes),), i32), self._b(tag + "dbuf", (4 * M,), f64)
-        iv, o = {}, 0
-        for name, sz in sizes:
-            iv[name] = (o, ibuf[o:o + sz])
-            o += sz
-        pcount, ccount, p_len, c_len, c_slot = (iv[k_][1] for k_ in ("pcount", "ccount", "p_len", "c_len", "c_slot"))
-        sent, c_sent = [iv["sent0"][1].view(M, L), iv["sent1"][1].view(M, L)], iv["c_sent"][1].view(B * (n + 1), L)
-        p_score, c_score, p_logprob, c_logprob = dbuf[0:M], dbuf[M:2 * M], dbuf[2 * M:3 * M], dbuf[3 * M:4 * M]
+        lay, dlay = FieldLayout(beam_fields(B, n, L)), FieldLayout([(k_, M) for k_ in ("p_score", "c_score", "p_logprob", "c_logprob")])
+        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), f64)
+        iv = lay.views(ibuf)
+        pcount, ccount, p_len, c_len, c_slot = (iv[k_] for k_ in ("pcount", "ccount", "p_len", "c_len", "c_slot"))
+        sent, c_sent = [iv["sent0"].view(M, L), iv["sent1"].view(M, L)], iv["c_sent"].view(B * (n + 1), L)
+        p_score, c_score, p_logprob, c_logprob = dlay.views(dbuf).values()
         c_free = self._b(tag + "c_free", (B,), i32)
         parent, tok = self._b(tag + "parent", (M,), i32), self._b(tag + "tok", (M,), i32)
         tv, ti = self._b(tag + "tv", (M, kc)), self._b(tag + "ti", (M, kc), i32)
@@ -884,10 +889,8 @@ class CaptionGenerator(object):
         pt.key_fn = lambda: self._graph_key(*kind, B, n, L, K, int(eos), float(len_norm_f),
                                             tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot,
                                                      c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M)] + list(bufs.values()))
-        pt.key = pt.key_fn()
-        pt.graph = self._graphs.get(pt.key) if fused else None
-        pt.ibuf, pt.dbuf, pt.ioff = ibuf, dbuf, {k_: v[0] for k_, v in iv.items()}
-        pt.ihost, pt.dhost = self._pinned(tag + "ihost", ibuf.numel(), i32), self._pinned(tag + "dhost", 2 * M, f64)
+        pt.graph = self._graphs.get(pt.key_fn()) if fused else None
+        pt.tag, pt.ibuf, pt.scores, pt.ioff = tag, ibuf, dbuf[:dlay.off["p_logprob"]], lay.off   # (the host reads the scores only)
         pt.it, pt.last, pt.done, pt.pending = 0, 0, rounds <= 0, []
         return pt
 
@@ -949,7 +952,7 @@ class CaptionGenerator(object):
         # the sentence buffers alternate with the round's parity, so a chunk that starts at an even round is the same graph every time.
         # The FIRST call of a shape runs eagerly and captures the chunks at its end (a capture executes nothing); later calls replay
         # them.  VC_DECODE_GRAPH=0 keeps the eager loop -- same kernels, same beams.
-        K = int(check_every) if check_every and check_every % 2 == 0 else 4
+        K = self._chunk_rounds(check_every)
         want = int(os.environ.get("VC_DECODE_SLICES", self.slices))
         nparts = want if (want > 1 and (B // G) % want == 0 and B * n >= self.slice_rows * want and xproj is not None) else 1
         nb = B // nparts
@@ -1006,18 +1009,14 @@ class CaptionGenerator(object):
             main.wait_stream(s)
         t_ph = _phase("rounds", t_ph)
         # results: two asynchronous copies per slice into pinned memory, one wait
-        for pt in parts:
-            pt.ihost.copy_(pt.ibuf, non_blocking=True)
-            pt.dhost.copy_(pt.dbuf[:2 * pt.M], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
+        hosts = [self._to_host(pt.tag, pt.ibuf, pt.scores, wait=pt is parts[-1]) for pt in parts]
         t_ph = _phase("results: copies to pinned memory", t_ph)
         res = []
-        for pt in parts:
-            res += beams_from_host(pt.ihost.numpy(), pt.dhost.numpy(), pt.ioff, pt.B, n, L, pt.last)
+        for pt, (ints, dbls) in zip(parts, hosts):
+            res += beams_from_host(ints, dbls, pt.ioff, pt.B, n, L, pt.last)
         t_ph = _phase("results to host lists", t_ph)
         if fused and rounds > K:
             for pt in parts:
                 if pt.graph is None:
-                    pt.key = pt.key_fn()
-                    self._capture(pt.key, pt.chunk_fn)   # (the results are on the host: the capture touches no state)
+                    self._capture(pt.key_fn(), pt.chunk_fn)   # (the results are on the host: the capture touches no state)
         return res
