@@ -39,6 +39,8 @@ extern "C" {
  *      vc_logits_logprob_workspace_bytes / vc_score_reduce_f64.
  *      Added within 4 (additive, no layout change): the truncated-sampling entry vc_decode_pick_trunc_f32.
  *      Added within 4 (additive, no layout change): the caption-evaluation entry vc_ngram_overlap.
+ *      Added within 4 (additive, no layout change): the posterior-bound entries vc_posterior_latent_f32 / vc_gauss_kl_rows_f64 /
+ *      vc_bound_reduce_f64.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -598,6 +600,32 @@ size_t vc_logits_logprob_workspace_bytes(long rows, int V, int H);
 int vc_logits_logprob_f32(void* stream, long rows, int V, int H, const float* hs, long pitch, const float* W, long ldw, const float* bias,
                           const int32_t* labels, float* lp, float* ws, size_t ws_bytes);
 int vc_score_reduce_f64(void* stream, const float* lp, int T, int C, int K, const int32_t* len, double* logprob, double* marginal);
+
+/* ------------------------------------------------------------------------------------
+ * Posterior at inference: ELBO and importance-weighted bound of given captions (generate.py: CaptionGenerator.bound; csrc/bound.hip;
+ * DESIGN.md "Bounds").  Rows are caption-major, draw-minor: r = c*K + k.  sigma_p = prior_std; pm [n_img, L] with img [rows / K] = the
+ * pm row of every caption, or both NULL (a zero prior mean).  Every float64 sum is per-lane partials in a fixed stride order, then a fixed
+ * shuffle tree: no atomics, and what a row gets depends on the row only (not on its index, nor on the other rows of the call).
+ *   posterior_latent  z[r, s, l] = mean[r / K, l] + std_[r / K, l] * eps[r, s, l] (f32, vc_latent_sample_f32's expression) for mean, std_
+ *                     [rows / K, L]; eps [rows, S, L], or NULL: N(0,1) draws from Philox, bit-identical to
+ *                     vc_philox_normal_f32(out, rows*S*L, seed, offset, step) -- a draw is defined by its flat element index, so a row
+ *                     whose S*L is no multiple of 4 may start inside a Philox quad.  logw[r] (float64) = sum_{s,l} [ -0.5 ((z - pm_l) /
+ *                     sigma_p)^2 - log sigma_p + 0.5 eps^2 + log std_l ] = log p(z) - log q(z), the 2 pi terms cancelled, from the f32 z,
+ *                     eps, std_, pm: one pass, z written and its term accumulated from the same registers.
+ *   gauss_kl_rows     kl[c] = S * sum_l [ log(sigma_p / std_l) + (std_l^2 + (mean_l - pm_l)^2) / (2 sigma_p^2) - 0.5 ] (float64).
+ *   bound_reduce      lp [T, C*K], len [C] as vc_score_reduce_f64; logw [C*K].  logprob [C, K] = vc_score_reduce_f64's sums (same bits;
+ *                     len[c] == 0: zeros); with a_k = logprob[c, k] + logw[c, k]: out [C, 5] = elbo = mean_k a_k, iwae = log sum_k
+ *                     exp(a_k - max a) + max a - log K, rec = mean_k logprob, kl_mc = -mean_k logw, ess = (sum_k v_k)^2 / sum_k v_k^2
+ *                     with v_k = exp(a_k - max a).  One wave per caption, K <= 256.
+ * K outside 1..256, S or L < 1, a negative size or a NULL output is VC_EINVAL.
+ * ---------------------------------------------------------------------------------- */
+int vc_posterior_latent_f32(void* stream, long rows, int K, int S, int L, const float* mean, const float* std_, const float* pm,
+                            const int32_t* img, float prior_std, const float* eps, uint64_t seed, uint64_t offset, const int32_t* step,
+                            float* z, double* logw);
+int vc_gauss_kl_rows_f64(void* stream, long C, int S, int L, const float* mean, const float* std_, const float* pm, const int32_t* img,
+                         float prior_std, double* kl);
+int vc_bound_reduce_f64(void* stream, const float* lp, int T, int C, int K, const int32_t* len, const double* logw, double* logprob,
+                        double* out);
 
 /* ------------------------------------------------------------------------------------
  * Host-side helper (the only entry point that takes HOST pointers): CRC-32C (Castagnoli) of a byte

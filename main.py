@@ -262,7 +262,7 @@ def main(params):
                 dist.destroy_process_group()
             return
         rng = np.random.default_rng(params.seed + 5)
-        captions_gen, scores, references, decoded = [], [], [], []
+        captions_gen, scores, bounds, references, decoded = [], [], [], [], []
         for it in range(2):
             b = synth.make_batch(rng, params.batch_size, 1, 20, params.vocab_size, use_ci=spec.uses_ci(params), images=params.fine_tune)
             ids = ["synthetic_%06d" % (it * params.batch_size + i) for i in range(params.batch_size)]
@@ -288,6 +288,9 @@ def main(params):
             if params.score_draws:   # held-out likelihood of the batch's own ("human") captions under the prior
                 from vae_captioning_amd.ops.inference import human_captions
                 scores += decoder.score_captions(ids, pics, human_captions((b["cap_dec"], b["cap_enc"]), b["lengths"]), c_v)
+            if params.bound_draws:   # the same captions bounded with draws from the model's own posterior
+                from vae_captioning_amd.ops.inference import human_captions
+                bounds += decoder.bound_captions(ids, pics, human_captions((b["cap_dec"], b["cap_enc"]), b["lengths"]), c_v)
         say("Generated {} captions".format(len(captions_gen)))
         if rank == 0:
             with open("./val_{}.json".format(params.gen_name), "w") as wj:
@@ -298,6 +301,9 @@ def main(params):
             if params.score_draws:
                 from vae_captioning_amd.ops.inference import store_scores
                 store_scores(params, scores)
+            if params.bound_draws:
+                from vae_captioning_amd.ops.inference import store_bounds
+                store_bounds(params, bounds, decoder.bound_stats)
             if params.eval_captions:
                 from vae_captioning_amd.ops.inference import evaluate_decoded
                 evaluate_decoded(params, decoder, references, decoded)

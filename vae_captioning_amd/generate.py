@@ -191,6 +191,7 @@ class CaptionGenerator(object):
         # score(): row-steps (sequence rows x steps) per pass; act [T, N, 4H] + cs, hs [T + 1, N, H] are <= 8 H floats per row-step: 1 GiB
         self._t_score = 0.0   # (diagnostics: PHASE_TIMES)
         self.score_rows = max(1, (1 << 30) // (32 * int(engine.p.decoder_hidden)))
+        self.bound_rows = self.score_rows   # bound(): the same budget (its teacher forcing is score()'s; the encoder pass has 1 / K of the rows)
 
     def _b(self, name, shape, dtype=torch.float32):
         t = self.buf.get(name)
@@ -229,16 +230,18 @@ class CaptionGenerator(object):
         return out
 
     # ------------------------------------------------------------------ init chain
-    def _image_rows(self, tag, n, features, c_v, z_rows):
+    def _image_rows(self, tag, n, features, c_v, z_rows, encoder=False):
         """What both init chains do on their B image rows, n LSTM steps long: features, cluster vectors and AG prior means (host-computed) go
         into the persistent buffers feats, cv, pmd (None where the model has none), the workspace is sized (z_rows: rows of the z_rnn
         product), and two launch lists are made: embed(tg), X[0] = imf_emb(features), X[1] = cv_emb(c_v); lstm(st), the n steps over X from
-        a zero state, to cs[n] / hs[n].  Returns them all (a captured chain bakes the buffers' addresses)."""
+        a zero state, to cs[n] / hs[n].  Returns them all (a captured chain bakes the buffers' addresses).
+        encoder=True: the same chain through the ENCODER cell (encoder.py:38-50: the image-only steps of q_net; no prior mean)."""
         e, p, lib, S = self.e, self.p, self.lib, self.e.store
-        B, E, Hd, F = int(features.shape[0]), p.embed_size, p.decoder_hidden, p.cnn_feature_size
+        B, E, Hd, F = int(features.shape[0]), p.embed_size, (p.encoder_hidden if encoder else p.decoder_hidden), p.cnn_feature_size
+        cell = spec.ENC_CELL if encoder else spec.DEC_CELL
         feats = self._load(self._b(tag + "feats", (B, F)), features)
         cv = self._load(self._b(tag + "cv", (B, K_CL)), c_v) if e.feed_cv else None
-        pm = self.prior_mean(np.asarray(c_v) if c_v is not None else None) if e.enc else None
+        pm = self.prior_mean(np.asarray(c_v) if c_v is not None else None) if e.enc and not encoder else None
         pmd = self._load(self._b(tag + "pm", (B, p.latent_size)), pm) if pm is not None else None
         X, act = self._b(tag + "X", (n, B, E)), self._b(tag + "act0", (n, B, 4 * Hd))
         cs, hs, lens = self._b(tag + "cs0", (n + 1, B, Hd)), self._b(tag + "hs0", (n + 1, B, Hd)), self._ones_for(B, n)
@@ -254,7 +257,7 @@ class CaptionGenerator(object):
         def lstm(st):
             lib.vc_fill_f32(st, P(cs[0]), B * Hd, 0.0)
             lib.vc_fill_f32(st, P(hs[0]), B * Hd, 0.0)
-            lib.vc_lstm_seq_fwd_f32(st, n, B, E, Hd, P(X), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")),
+            lib.vc_lstm_seq_fwd_f32(st, n, B, E, Hd, P(X), P(S.param(cell + "kernel")), P(S.param(cell + "bias")),
                                     P(lens), P(act), P(cs), P(hs), P(e.ws), e.ws_bytes, e.lstm_flags)
 
         return types.SimpleNamespace(feats=feats, cv=cv, pmd=pmd, X=X, act=act, cs=cs, hs=hs, lens=lens, embed=embed, lstm=lstm)
@@ -664,13 +667,30 @@ class CaptionGenerator(object):
         """Teacher-forced log-likelihood of caps[b] (token lists without <BOS>) under the K draws of image b whose decoder states are rows
         b*K + k of c0 / h0 [B*K, H]: (logprob float64 [C, K], marginal float64 [C]) over the C captions in image order.  Sequence rows are
         caption-major, draw-minor; one upload of the indices, one copy of the results into pinned memory."""
+        C = sum(len(cl) for cl in caps)
+        tf = self._teacher_force(c0, h0, K, caps, bos)
+        if tf is None:
+            return np.zeros((C, K), np.float64), np.zeros((C,), np.float64)
+        dlay = FieldLayout([("logprob", C * K), ("marginal", C)])
+        dbuf = self._b(tf.tag + "dbuf", (dlay.total,), torch.float64)
+        logprob, marginal = dlay.views(dbuf).values()
+        self.lib.vc_score_reduce_f64(_stream(), P(tf.lp), tf.T, C, K, P(tf.clen), P(logprob), P(marginal))
+        logprob, marginal = dlay.views(self._to_host(tf.tag, None, dbuf)[1].copy()).values()
+        self._t_score = _phase("score: reduce + copy-back", tf.t_ph)
+        return logprob.reshape(C, K), marginal
+
+    def _teacher_force(self, c0, h0, K, caps, bos, own_rows=False):
+        """The device half of _score_states: every caption of caps[b] teacher-forced from <BOS> under K draws, the tokens' log-softmax terms
+        left in lp [T, C*K] (time-major, f32; rows caption-major, draw-minor).  Row c*K + k starts from row b*K + k of c0 / h0 [B*K, H], the
+        state of draw k of the caption's IMAGE, or with own_rows from row c*K + k of c0 / h0 [C*K, H], a state of its own (bound(): the
+        posterior draws belong to the caption).  Returns lp, T, clen [C] (device) and the buffers' tag; None when there is nothing to score."""
         e, p, lib, S = self.e, self.p, self.lib, self.e.store
         E, Hd, V = p.embed_size, p.decoder_hidden, e.V
         flat = [(b, t) for b, cl in enumerate(caps) for t in cl]
         C = len(flat)
         T = max([len(t) for _, t in flat] + [0])
         if C == 0 or T == 0:
-            return np.zeros((C, K), np.float64), np.zeros((C,), np.float64)
+            return None
         N = C * K
         i32 = torch.int32
         # int32 upload: parent row, row lengths, caption lengths, step inputs [T, N], labels [T, N]
@@ -680,7 +700,7 @@ class CaptionGenerator(object):
         toks_in, labels = np.zeros((T, C), np.int32), np.full((T, C), -1, np.int32)
         for c, (b, t) in enumerate(flat):
             n = len(t)
-            h_parent[c * K:(c + 1) * K] = b * K + np.arange(K)
+            h_parent[c * K:(c + 1) * K] = (c if own_rows else b) * K + np.arange(K)
             h_clen[c] = n
             if n:
                 labels[:n, c] = t
@@ -695,8 +715,7 @@ class CaptionGenerator(object):
         parent, lens, clen, tin, lab = lay.views(idx).values()
         X, act = self._b("sc_X", (T, N, E)), self._b("sc_act", (T, N, 4 * Hd))
         cs, hs = self._b("sc_cs", (T + 1, N, Hd)), self._b("sc_hs", (T + 1, N, Hd))
-        dlay = FieldLayout([("logprob", N), ("marginal", C)])
-        lp, dbuf = self._b("sc_lp", (T * N,)), self._b(tag + "dbuf", (dlay.total,), torch.float64)
+        lp = self._b("sc_lp", (T * N,))
         st = _stream()
         t_ph = _phase("score: init chain", self._t_score)
         lib.vc_beam_gather_f32(st, P(c0), P(h0), P(parent), N, Hd, P(cs[0]), P(hs[0]), None, None, V, 4 * Hd, None)
@@ -711,19 +730,16 @@ class CaptionGenerator(object):
         lib.vc_logits_logprob_f32(st, T * N, V, Hd, P(hs[1]), Hd, P(S.param("decoder/rnn_logits/kernel")), e.Vp,
                                   P(S.param("decoder/rnn_logits/bias")), P(lab), P(lp), P(e.ws), e.ws_bytes)
         t_ph = _phase("score: logits + log-probability", t_ph)
-        logprob, marginal = dlay.views(dbuf).values()
-        lib.vc_score_reduce_f64(st, P(lp), T, C, K, P(clen), P(logprob), P(marginal))
-        logprob, marginal = dlay.views(self._to_host(tag, None, dbuf)[1].copy()).values()
-        self._t_score = _phase("score: reduce + copy-back", t_ph)
-        return logprob.reshape(C, K), marginal
+        return types.SimpleNamespace(lp=lp, T=T, clen=clen, tag=tag, t_ph=t_ph)
 
-    def _check_draws(self, K, eps, B):
-        """ValueError unless K latent draws per image are 1..DIVERSE_MAX_DRAWS and eps, when given, is [K, S, B, L] (score(), diverse())"""
+    def _check_draws(self, K, eps, B, per="images"):
+        """ValueError unless K latent draws are 1..DIVERSE_MAX_DRAWS and eps, when given, is [K, S, B, L] (score(), diverse(): B images;
+        bound(): B captions)"""
         want = (K, self.p.gen_z_samples, B, self.p.latent_size)
         if not 1 <= K <= DIVERSE_MAX_DRAWS:
             raise ValueError("draws must be 1..%d (got %d)" % (DIVERSE_MAX_DRAWS, K))
         if eps is not None and tuple(np.shape(eps)) != want:
-            raise ValueError("eps must be [draws, gen_z_samples, images, latent_size] = %s" % (want,))
+            raise ValueError("eps must be [draws, gen_z_samples, %s, latent_size] = %s" % (per, want))
 
     def score(self, features, captions, c_v=None, eps=None, bos=1, eos=2, draws=1):
         """How likely are given captions for their images: per image, per caption {"logprob": float64 [K], "marginal": float, "tokens": n}.
@@ -736,8 +752,32 @@ class CaptionGenerator(object):
         Passes: an image goes with all its captions and draws into one pass of <= score_rows row-steps (sequence rows x steps of its
         longest caption); an image that exceeds it alone gets a pass of its own.  ValueError: a token id outside [0, V), more than
         SCORE_MAX_TOKENS scored tokens (names image and caption), draws outside 1..DIVERSE_MAX_DRAWS, a wrong eps shape."""
-        K, V, B = int(draws), self.e.V, int(features.shape[0])
+        K, B = int(draws), int(features.shape[0])
         self._check_draws(K, eps, B)
+        caps = self._caption_lists(captions, B, bos)
+        if c_v is not None:
+            c_v = np.asarray(c_v)
+        eps = np.asarray(eps) if eps is not None else None
+        res = []
+        for g0, g1, rows, steps in self._passes(caps, K, self.score_rows):
+            sl = slice(g0, g1)
+            if rows * steps == 0:
+                lp, marg = np.zeros((rows // K, K), np.float64), np.zeros((rows // K,), np.float64)
+            else:
+                self._t_score = _phase("", 0.0)
+                c0, h0 = self._diverse_init(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None, K)
+                lp, marg = self._score_states(c0, h0, K, caps[sl], bos)
+            o = 0
+            for b in range(g0, g1):
+                res.append([{"logprob": lp[o + j].copy(), "marginal": float(marg[o + j]), "tokens": len(t)} for j, t in enumerate(caps[b])])
+                o += len(caps[b])
+        return res
+
+    def _caption_lists(self, captions, B, bos, empty_ok=True):
+        """captions as score() / encode() / bound() take them (per image a list of token-id lists) -> the same lists as ints without the
+        leading <BOS>.  ValueError: not one list per image, more than SCORE_MAX_TOKENS tokens, a token id outside [0, V), and, unless
+        empty_ok, a caption without a token (the message names image and caption)."""
+        V = self.e.V
         if len(captions) != B:
             raise ValueError("captions must hold one list of captions per image (%d images, %d lists)" % (B, len(captions)))
         caps = []
@@ -751,32 +791,219 @@ class CaptionGenerator(object):
                     raise ValueError("image %d caption %d: %d tokens to score, at most %d" % (b, j, len(t), SCORE_MAX_TOKENS))
                 if any(w < 0 or w >= V for w in t):
                     raise ValueError("image %d caption %d: token id outside [0, %d)" % (b, j, V))
+                if not t and not empty_ok:
+                    raise ValueError("image %d caption %d: an empty caption has no posterior" % (b, j))
                 row.append(t)
             caps.append(row)
-        if c_v is not None:
-            c_v = np.asarray(c_v)
-        eps = np.asarray(eps) if eps is not None else None
-        res, g0 = [], 0
+        return caps
+
+    @staticmethod
+    def _passes(caps, K, limit):
+        """The passes of score() / bound() over the images of caps: (g0, g1, rows, steps) per pass, images g0 .. g1-1 with rows = their
+        captions x K sequence rows and steps = their longest caption.  Greedy cut: images are added while rows x steps <= limit; an
+        image that exceeds it alone gets a pass of its own."""
+        B, g0 = len(caps), 0
         while g0 < B:
             g1, rows, steps = g0, 0, 0
-            while g1 < B:   # greedy cut: images g0 .. g1-1 while rows x steps fits (an image alone always goes)
+            while g1 < B:
                 r2 = rows + len(caps[g1]) * K
                 s2 = max([steps] + [len(t) for t in caps[g1]])
-                if g1 > g0 and r2 * s2 > self.score_rows:
+                if g1 > g0 and r2 * s2 > limit:
                     break
                 g1, rows, steps = g1 + 1, r2, s2
-            sl = slice(g0, g1)
-            if rows * steps == 0:
-                lp, marg = np.zeros((rows // K, K), np.float64), np.zeros((rows // K,), np.float64)
-            else:
-                self._t_score = _phase("", 0.0)
-                c0, h0 = self._diverse_init(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None, K)
-                lp, marg = self._score_states(c0, h0, K, caps[sl], bos)
-            o = 0
-            for b in range(g0, g1):
-                res.append([{"logprob": lp[o + j].copy(), "marginal": float(marg[o + j]), "tokens": len(t)} for j, t in enumerate(caps[b])])
-                o += len(caps[b])
+            yield g0, g1, rows, steps
             g0 = g1
+
+    # ------------------------------------------------------------------ the posterior at inference: encode(), bound()
+    def _posterior_inputs(self, features, captions, c_v, gmm_idx, bos):
+        """The checks encode() and bound() share (their ValueError cases) -> (caps without <BOS>, c_v as an array or None, gmm_idx as a
+        flat int32 array over the captions or None)."""
+        e, p = self.e, self.p
+        if not e.enc:
+            raise ValueError("a --no_encoder model has no posterior q(z | caption, image)")
+        B = int(features.shape[0])
+        caps = self._caption_lists(captions, B, bos, empty_ok=False)
+        C = sum(len(cl) for cl in caps)
+        if e.use_ci:
+            if c_v is None or tuple(np.shape(c_v)) != (B, K_CL):
+                raise ValueError("a %s model%s needs the images' cluster vectors c_v [%d, %d]" % (p.prior, " with use_c_v" if p.use_c_v else "", B, K_CL))
+            c_v = np.ascontiguousarray(c_v, dtype=np.float32)
+        else:
+            c_v = None
+        if p.prior in ("AG", "GMM"):
+            for b in range(B):
+                if caps[b] and not c_v[b].any():
+                    raise ValueError("image %d: an all-zero cluster vector gives its captions no %s posterior (the std would be 0)" % (b, p.prior))
+        if p.prior == "GMM":
+            if gmm_idx is None:
+                raise ValueError("a GMM model needs gmm_idx: the mixture component (0..%d) of every caption, flat in image order" % (K_CL - 1))
+            g = np.asarray(gmm_idx).reshape(-1)
+            if g.size != C or (C and (g.dtype.kind not in "iu" or g.min() < 0 or g.max() >= K_CL)):
+                raise ValueError("gmm_idx must hold one integer in 0..%d per caption (%d captions)" % (K_CL - 1, C))
+            gmm_idx = g.astype(np.int32)
+        else:
+            gmm_idx = None
+        return caps, c_v, gmm_idx
+
+    def _encode_pass(self, features, c_v, caps, gmm_idx):
+        """q(z | caption, image) of the C captions of one pass (caps[b]: the non-empty token lists of image b): mean, std [C, L] in
+        persistent device buffers, computed as CaptionEngine.fw_encode_stats does for a training row (encoder.py:24-110, no dropout).
+        The image-only steps of the encoder run on the B image rows; their state is gathered to the caption rows (parent = the caption's
+        image), where ONE length-masked LSTM call runs the token steps; then the heads.  Returns (mean, std, img, h_img): img [C] int32,
+        the image of every caption, on the device and on the host."""
+        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        B, E, He, L, V = int(features.shape[0]), p.embed_size, p.encoder_hidden, p.latent_size, e.V
+        flat = [(b, t) for b, cl in enumerate(caps) for t in cl]
+        C, T, n_e = len(flat), max(len(t) for _, t in flat), e.n_init_e
+        im = self._image_rows("bde_", n_e, features, c_v, 1, encoder=True)
+        gmm, ag = p.prior == "GMM", p.prior == "AG"
+        lay = FieldLayout([("img", C), ("len", C), ("gmm", C), ("tok", T * C)])
+        host = np.zeros(lay.total, np.int32)
+        h_img, h_len, h_gmm, h_tok = lay.views(host).values()
+        toks = h_tok.reshape(T, C)
+        for c, (b, t) in enumerate(flat):
+            h_img[c], h_len[c] = b, len(t)
+            toks[:len(t), c] = t
+        if gmm:
+            h_gmm[:] = gmm_idx
+        idx = self._b("bdq_idx", (host.size,), torch.int32)
+        idx.copy_(torch.from_numpy(host), non_blocking=False)
+        img, lens, gidx, tok = lay.views(idx).values()
+        X, act = self._b("bdq_X", (T, C, E)), self._b("bdq_act", (T, C, 4 * He))
+        cs, hs = self._b("bdq_cs", (T + 1, C, He)), self._b("bdq_hs", (T + 1, C, He))
+        mean, std = self._b("bdq_mean", (C, L)), self._b("bdq_std", (C, L))
+        st = _stream()
+        im.embed("gemm")
+        im.lstm(st)
+        lib.vc_beam_gather_f32(st, P(im.cs[n_e]), P(im.hs[n_e]), P(img), C, He, P(cs[0]), P(hs[0]), None, None, V, 4 * He, None)
+        lib.vc_embedding_gather_f32(st, P(S.param("encoder/enc_embeddings")), P(tok), T * C, E, V, P(X))
+        nh = L if p.prior == "Normal" else 2 * K_CL * L
+        for nb in (lib.vc_lstm_seq_workspace_bytes(T, C, E, He), lib.vc_gemm_workspace_bytes(C, nh, He)):
+            e._need_ws(nb)
+        lib.vc_lstm_seq_fwd_f32(st, T, C, E, He, P(X), P(S.param(spec.ENC_CELL + "kernel")), P(S.param(spec.ENC_CELL + "bias")), P(lens),
+                                P(act), P(cs), P(hs), P(e.ws), e.ws_bytes, e.lstm_flags)
+        hT = hs[T]   # (rows shorter than T carry their last state forward)
+        if p.prior == "Normal":
+            logstd = self._b("bdq_logstd", (C, L))
+            e.gemm(0, 0, C, L, He, hT, He, S.param("encoder/dense/kernel"), L, mean, L, S.param("encoder/dense/bias"))
+            e.gemm(0, 0, C, L, He, hT, He, S.param("encoder/dense_1/kernel"), L, logstd, L, S.param("encoder/dense_1/bias"))
+            lib.vc_exp_f32(st, P(logstd), C * L, P(std))
+        else:
+            heads = self._b("bdq_heads", (C, nh))
+            e.gemm(0, 0, C, nh, He, hT, He, S.param("encoder/heads/kernel"), nh, heads, nh, S.param("encoder/heads/bias"))
+            cvr = self._load(self._b("bdq_cvrows", (C, K_CL)), c_v[h_img]) if ag else None   # the c_v-weighted mix takes a row per caption
+            lib.vc_heads_mix_fwd_f32(st, C, K_CL, L, P(heads), P(cvr), P(gidx) if gmm else None, P(mean), P(std))
+        return mean, std, img, h_img
+
+    def encode(self, features, captions, c_v=None, gmm_idx=None, bos=1):
+        """The posterior q(z | caption, image) of given captions: per image, per caption (mean, std), float32 [L] each -- what the encoder
+        of a training step computes for the row (cap_enc = the caption without <BOS>, its <EOS> included when present; no dropout).
+        captions[b]: token-id lists of image b, with or without the leading <BOS> (stripped).  c_v [B, 90]: the cluster vectors of a
+        model that uses them.  gmm_idx (GMM prior): the mixture component 0..89 of every caption, flat over all captions in image order
+        (training draws it from the cluster vector; here the caller does).  Passes are cut by bound_rows with score()'s rule at one row
+        per caption.  ValueError: a --no_encoder model; a token id outside [0, V); an empty caption; more than SCORE_MAX_TOKENS tokens;
+        GMM without gmm_idx (or values outside 0..89); AG / GMM with an all-zero cluster vector for an image that has captions."""
+        caps, c_v, gmm_idx = self._posterior_inputs(features, captions, c_v, gmm_idx, bos)
+        res, o = [], 0
+        for g0, g1, rows, _ in self._passes(caps, 1, self.bound_rows):
+            if rows:
+                sl = slice(g0, g1)
+                mean, std, _, _ = self._encode_pass(features[sl], c_v[sl] if c_v is not None else None, caps[sl],
+                                                 gmm_idx[o:o + rows] if gmm_idx is not None else None)
+                mean, std = mean.cpu().numpy(), std.cpu().numpy()
+            j = 0
+            for b in range(g0, g1):
+                res.append([(mean[j + i].copy(), std[j + i].copy()) for i in range(len(caps[b]))])
+                j += len(caps[b])
+            o += rows
+        return res
+
+    def _bound_pass(self, features, c_v, caps, gmm_idx, eps, K, bos, return_latents):
+        """One pass of bound() over the C > 0 captions of B images: float64 host arrays logprob, logw [C, K], out [C, 5] (elbo, iwae, rec,
+        kl_mc, ess) and kl [C] from ONE copy-back, plus with return_latents (mean, std [C, L], z [C, K, S, L]) as float32 host arrays.
+        eps: [K, S, C, L] or None (Philox on device)."""
+        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        B, E, Hd, L, Sm = int(features.shape[0]), p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples
+        t_ph = _phase("", 0.0)
+        mean, std, img, h_img = self._encode_pass(features, c_v, caps, gmm_idx)
+        t_ph = _phase("bound: encoder", t_ph)
+        C = int(mean.shape[0])
+        N = C * K
+        n_pre = e.n_init_d - 1   # the decoder's steps that depend on the image only
+        tag = "bd_"
+        im = self._image_rows(tag, n_pre, features, c_v, N)
+        z, Xz, act1 = self._b("bd_z", (N, Sm, L)), self._b("bd_Xz", (1, N, E)), self._b("bd_act1", (1, N, 4 * Hd))
+        cs1, hs1 = self._b("bd_cs1", (2, N, Hd)), self._b("bd_hs1", (2, N, Hd))
+        epsd = None
+        if eps is not None:
+            epsd = self._load(self._b("bd_eps", (N, Sm, L)), np.transpose(np.asarray(eps, np.float32), (2, 0, 1, 3)))   # [K, S, C, L] -> rows c*K + k
+        rowimg = self._b(tag + "rowimg", (N,), torch.int32)
+        rowimg.copy_(torch.from_numpy(np.repeat(h_img, K)), non_blocking=False)   # the image whose state row c*K + k continues
+        dlay = FieldLayout([("logprob", N), ("logw", N), ("out", 5 * C), ("kl", C)])
+        dbuf = self._b(tag + "dbuf", (dlay.total,), torch.float64)
+        logprob, logw, out, kl = dlay.views(dbuf).values()
+        e._need_ws(lib.vc_lstm_seq_workspace_bytes(1, N, E, Hd))
+        st = _stream()
+        im.embed("gemm")
+        im.lstm(st)
+        lib.vc_beam_gather_f32(st, P(im.cs[n_pre]), P(im.hs[n_pre]), P(rowimg), N, Hd, P(cs1[0]), P(hs1[0]), None, None, e.V, 4 * Hd, None)
+        pm_args = (P(im.pmd), P(img)) if im.pmd is not None else (None, None)
+        lib.vc_posterior_latent_f32(st, N, K, Sm, L, P(mean), P(std), pm_args[0], pm_args[1], float(p.std), P(epsd), e.seed * 1000003 + 17,
+                                    8 << 32, P(e.step), P(z), P(logw))
+        e.gemm(0, 0, N, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, Xz[0], E, S.param("decoder/net/z_rnn/bias"))
+        lib.vc_lstm_seq_fwd_f32(st, 1, N, E, Hd, P(Xz), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")),
+                                P(self._ones_for(N)), P(act1), P(cs1), P(hs1), P(e.ws), e.ws_bytes, e.lstm_flags)
+        self._t_score = _phase("bound: posterior draws, z step", t_ph)
+        tf = self._teacher_force(cs1[1], hs1[1], K, caps, bos, own_rows=True)
+        lib.vc_bound_reduce_f64(st, P(tf.lp), tf.T, C, K, P(tf.clen), P(logw), P(logprob), P(out))
+        lib.vc_gauss_kl_rows_f64(st, C, Sm, L, P(mean), P(std), pm_args[0], pm_args[1], float(p.std), P(kl))
+        h = dlay.views(self._to_host(tag, None, dbuf)[1].copy())
+        self._t_score = _phase("bound: reduce + copy-back", tf.t_ph)
+        lat = None
+        if return_latents:
+            lat = (mean.cpu().numpy(), std.cpu().numpy(), z.cpu().numpy().reshape(C, K, Sm, L) if return_latents != "stats" else None)
+        return h["logprob"].reshape(C, K), h["logw"].reshape(C, K), h["out"].reshape(C, 5), h["kl"], lat
+
+    def bound(self, features, captions, c_v=None, eps=None, gmm_idx=None, bos=1, eos=2, draws=1, return_latents=False):
+        """Variational bounds on log p(caption | image) with the model's own posterior as proposal (DESIGN.md "Bounds"): per image, per
+        caption a dict of tokens (n scored, as score() counts them), elbo, iwae, rec, kl, kl_mc, ess (floats), logprob and logw (float64
+        [K]); with return_latents also mean, std (float32 [L]) and z (float32 [K, S, L]; return_latents="stats": mean and std only).
+        Draw k of a caption is z_k = mean + std * eps_k with (mean, std) = encode()'s posterior; its decoder state is init_state's with
+        z_k in place of the prior draw.  logprob[k] = log p(caption | z_k, image) exactly as score() defines it; logw[k] = log p(z_k |
+        image) - log q(z_k | caption, image) against the generation-time prior N(prior_mean, params.std^2) that score() and diverse()
+        draw from (float64, from the f32 z, eps, std).  With a_k = logprob[k] + logw[k]: elbo = mean_k a_k; iwae = log 1/K sum_k
+        exp(a_k) (Burda et al. 2016; iwae >= elbo, equal at K = 1); rec = mean_k logprob[k]; kl_mc = -mean_k logw[k]; kl = KL(q || p) in
+        closed form; ess = (sum_k v_k)^2 / sum_k v_k^2 of the importance weights v_k = exp(a_k - max a), in [1, K].
+        eps: [K, S, C, L] over all C captions in image order (Philox on device when None: those draws depend on how the passes are
+        cut).  Passes: score()'s rule on bound_rows row-steps.  ValueError: encode()'s cases, draws outside 1..DIVERSE_MAX_DRAWS, a
+        wrong eps shape."""
+        K = int(draws)
+        caps, c_v, gmm_idx = self._posterior_inputs(features, captions, c_v, gmm_idx, bos)
+        C = sum(len(cl) for cl in caps)
+        self._check_draws(K, eps, C, per="captions")
+        eps = np.asarray(eps) if eps is not None else None
+        res, o = [], 0
+        for g0, g1, rows, _ in self._passes(caps, K, self.bound_rows):
+            n = rows // K
+            if n:
+                sl = slice(g0, g1)
+                lp, lw, out, kl, lat = self._bound_pass(features[sl], c_v[sl] if c_v is not None else None, caps[sl],
+                                                        gmm_idx[o:o + n] if gmm_idx is not None else None,
+                                                        eps[:, :, o:o + n] if eps is not None else None, K, bos, return_latents)
+            j = 0
+            for b in range(g0, g1):
+                recs = []
+                for t in caps[b]:
+                    r = {"tokens": len(t), "elbo": float(out[j, 0]), "iwae": float(out[j, 1]), "rec": float(out[j, 2]), "kl": float(kl[j]),
+                         "kl_mc": float(out[j, 3]), "ess": float(out[j, 4]), "logprob": lp[j].copy(), "logw": lw[j].copy()}
+                    if return_latents:
+                        r.update(mean=lat[0][j].copy(), std=lat[1][j].copy())
+                        if lat[2] is not None:
+                            r["z"] = lat[2][j].copy()
+                    recs.append(r)
+                    j += 1
+                res.append(recs)
+            o += n
         return res
 
     def diverse(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, method="greedy", n_best=None, max_len=None, len_norm_f=0.7,

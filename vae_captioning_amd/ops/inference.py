@@ -13,6 +13,12 @@ the consensus scores; with `"marginal"` they hold each caption's likelihood over
 captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one in `./val_{gen_name}.json`.
 `params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
 (`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed.
+`params.bound_draws = K >= 1` (additive): the same human captions are bounded with K draws from the model's own posterior
+(`decoder.bound_captions`, generate.py: bound) -> `./val_{gen_name}_bound.json`: a header record {"draws", "skipped_images",
+"active_units", "latent_size"}, then per image {"image_id", "captions": [{"tokens", "elbo", "iwae", "rec", "kl", "ess"}]}; five printed
+lines: the perplexity bounds exp(-sum iwae / sum tokens) and exp(-sum elbo / sum tokens), the mean KL per caption, the mean effective
+sample size over K and the active latent units (Burda et al. 2016: dimensions whose posterior mean varies by more than 0.01 over the
+captions).
 `params.eval_captions` (additive): what was decoded for the validation images (`decoder.last_token_ids`: the whole ranked list of an
 image in the diverse modes, a list of one otherwise) is evaluated against ALL human captions of each image (taken from the generator's
 caption table by image id, `validation_references`: the batches carry one random caption per image) (`decoder.caption_evaluator`,
@@ -63,6 +69,45 @@ def perplexity(score_records):
 def store_scores(params, score_records):
     _store("./val_{}_scores.json".format(params.gen_name), score_records)
     print("Held-out perplexity of the human captions under %d prior draws: %.17g" % (params.score_draws, perplexity(score_records)))
+
+
+ACTIVE_UNIT_VARIANCE = 0.01   # Burda et al. 2016, section 5.2: a latent dimension is active when Var_x(E_q[z | x]) exceeds this
+
+
+def active_units(mu_sum, mu_sq, n, threshold=ACTIVE_UNIT_VARIANCE):
+    """How many latent dimensions are active: the (population) variance of the posterior mean over the n scored captions, from the running
+    float64 sums of mu and mu^2 per dimension, exceeds `threshold`.  0 when nothing was scored."""
+    if n <= 0:
+        return 0
+    m = np.asarray(mu_sum, np.float64) / n
+    return int(np.count_nonzero(np.asarray(mu_sq, np.float64) / n - m * m > threshold))
+
+
+def bound_summary(bound_records, draws):
+    """(perplexity bound from iwae, the same from elbo, mean kl per caption, mean ess / draws) over every bounded caption; nan when nothing
+    was bounded.  exp(-sum iwae / sum tokens) is an UPPER bound on the model's perplexity in expectation: iwae <= log p(caption | image)."""
+    caps = [c for r in bound_records for c in r["captions"]]
+    n = sum(c["tokens"] for c in caps)
+    if not n:
+        return (float("nan"),) * 4
+    return (math.exp(-sum(c["iwae"] for c in caps) / n), math.exp(-sum(c["elbo"] for c in caps) / n),
+            sum(c["kl"] for c in caps) / len(caps), sum(c["ess"] for c in caps) / (len(caps) * draws))
+
+
+def store_bounds(params, bound_records, stats):
+    """./val_{gen_name}_bound.json and the five printed lines; stats = decoder.bound_stats (None: nothing was bounded)"""
+    K, L = int(params.bound_draws), int(params.latent_size)
+    stats = stats or {"skipped_images": 0, "captions": 0, "mu_sum": np.zeros(L), "mu_sq": np.zeros(L)}
+    active = active_units(stats["mu_sum"], stats["mu_sq"], stats["captions"])
+    header = {"draws": K, "skipped_images": int(stats["skipped_images"]), "active_units": active, "latent_size": L}
+    _store("./val_{}_bound.json".format(params.gen_name), [header] + list(bound_records))
+    ppl_iwae, ppl_elbo, kl, ess = bound_summary(bound_records, K)
+    print("Perplexity bound of the human captions from the importance-weighted bound, %d posterior draws: %.17g" % (K, ppl_iwae))
+    print("Perplexity bound of the human captions from the ELBO, %d posterior draws: %.17g" % (K, ppl_elbo))
+    print("Mean KL(q || p) per caption: %.6f nats" % kl)
+    print("Mean effective sample size / draws: %.6f" % ess)
+    print("Active latent units: %d of %d (%d images without a cluster vector skipped)" % (active, L, header["skipped_images"]))
+    return header
 
 
 EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
@@ -142,6 +187,7 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
     val_cv = params.use_c_v or params.prior in ("GMM", "AG")
     records, scores = [], []
     n_score = int(getattr(params, "score_draws", 0) or 0)
+    n_bound, bounds = int(getattr(params, "bound_draws", 0) or 0), []
     evaluate = bool(getattr(params, "eval_captions", False))
     references, decoded = [], []
     all_refs = validation_references(val_gen) if evaluate else None
@@ -154,8 +200,12 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
             decoded += decoded_ids(decoder, len(ids))
         if n_score:
             scores += decoder.score_captions(ids, images, human_captions(caps, lens), _cluster_rows(c_v, val_cv), draws=n_score)
+        if n_bound:
+            bounds += decoder.bound_captions(ids, images, human_captions(caps, lens), _cluster_rows(c_v, val_cv), draws=n_bound)
     if n_score:
         store_scores(params, scores)
+    if n_bound:
+        store_bounds(params, bounds, getattr(decoder, "bound_stats", None))
     if params.sample_gen in ("diverse", "diverse_beam"):
         _store("./val_{}_diverse.json".format(params.gen_name), records)
         records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]

@@ -27,6 +27,7 @@ _DEFAULTS = dict(
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
+    bound_draws=0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -51,6 +52,7 @@ _FLAGS = [
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
     ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
+    ("--bound_draws", "bound_draws", int, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -74,7 +76,10 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--top_p": "--sample_gen sample / --diverse_method sample: draw each word from the smallest set of most likely words that holds "
                     "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)",
          "--eval_captions": "--mode inference: also evaluate the validation captions against the images' human captions on the GPU (BLEU, "
-                            "CIDEr-D, oracle CIDEr-D, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json"}
+                            "CIDEr-D, oracle CIDEr-D, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json",
+         "--bound_draws": "--mode inference: also bound the likelihood of the validation images' human captions with this many posterior "
+                          "draws per caption (ELBO, importance-weighted bound, KL, effective sample size, active latent units) and "
+                          "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)"}
 
 
 class Parameters(object):
@@ -112,6 +117,12 @@ class Parameters(object):
             ap.error("--consensus_m must be >= 1 (got %d)" % self.consensus_m)
         if not 0 <= self.score_draws <= 256:
             ap.error("--score_draws must be 0..256 (got %d)" % self.score_draws)
+        if not 0 <= self.bound_draws <= 256:
+            ap.error("--bound_draws must be 0..256 (got %d)" % self.bound_draws)
+        if self.bound_draws and self.mode != "inference":
+            ap.error("--bound_draws needs --mode inference (got --mode %s)" % self.mode)
+        if self.bound_draws and self.no_encoder:
+            ap.error("--bound_draws needs the encoder's posterior: not with --no_encoder")
         if self.sample_gen == "diverse_beam":
             if self.beam_groups < 1:
                 ap.error("--beam_groups must be >= 1 (got %d)" % self.beam_groups)

@@ -25,6 +25,7 @@ class Decoder(object):
         self.consensus_index = None  # consensus.ConsensusIndex: --diverse_rerank consensus re-ranks diverse captions against it
         self.last_token_ids = None   # per image of the last generation call its ranked token-id lists (what --eval_captions evaluates);
                                      # every generation method clears it first, so a call that fails leaves None, never older ids
+        self.bound_stats = None      # bound_captions: skipped images and the running sums behind the active-units count
         self.train_captions = None   # flat token-id lists of the training captions: `novel` of caption_evaluator (None: not reported)
 
     def px_z_fi(self, observed, gen_mode=False):
@@ -181,6 +182,52 @@ class Decoder(object):
         res = self._gen().score(self._features(in_pictures), captions, use_cv, None, bos, eos, draws=draws)
         return [{"image_id": pid, "captions": [{"tokens": int(r["tokens"]), "marginal": float(r["marginal"]), "logprob": float(np.mean(r["logprob"]))}
                                                for r in rs]} for pid, rs in zip(picture_ids, res)]
+
+    def bound_captions(self, picture_ids, in_pictures, captions, c_v=None, draws=None):
+        """Variational bounds on the likelihood of given captions with the model's posterior as proposal (generate.py: bound): captions as
+        score_captions takes them, `draws` (params.bound_draws) posterior draws per caption.  Returns per image {"image_id", "captions":
+        [{"tokens", "elbo", "iwae", "rec", "kl", "ess"}]}.  GMM prior: every caption's mixture component is drawn here from its image's
+        normalised cluster vector (encoder.py:72-75 draws it per training row), by a generator seeded from params.seed that lives as long
+        as this decoder.  AG / GMM: an image with an empty cluster vector has no posterior; it is left out and counted in
+        self.bound_stats["skipped_images"].  bound_stats also keeps running float64 sums of the posterior means and their squares per
+        latent dimension over every caption scored ("mu_sum", "mu_sq", "captions"): what ops.inference.active_units reads."""
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        p = self.params
+        use_cv = np.asarray(c_v, np.float32) if (spec.uses_ci(p) and c_v is not None and len(c_v)) else None
+        draws = int(draws if draws is not None else p.bound_draws)
+        feats = self._features(in_pictures)
+        st = self.bound_stats
+        if st is None:
+            L = p.latent_size
+            st = self.bound_stats = {"skipped_images": 0, "captions": 0, "mu_sum": np.zeros(L, np.float64), "mu_sq": np.zeros(L, np.float64),
+                                     "rng": np.random.default_rng(p.seed)}
+        keep = list(range(len(picture_ids)))
+        if p.prior in ("AG", "GMM") and use_cv is not None:
+            keep = [b for b in keep if use_cv[b].any()]
+            st["skipped_images"] += len(picture_ids) - len(keep)
+        if not keep:
+            return []
+        caps = [captions[b] for b in keep]
+        gmm_idx = None
+        if p.prior == "GMM":
+            gmm_idx = []
+            for b, cl in zip(keep, caps):
+                w = np.maximum(use_cv[b].astype(np.float64), 0.0)
+                gmm_idx += st["rng"].choice(w.size, size=len(cl), p=w / w.sum()).tolist()
+            gmm_idx = np.asarray(gmm_idx, np.int32)
+        res = self._gen().bound(feats[keep], caps, use_cv[keep] if use_cv is not None else None, None, gmm_idx, bos, eos, draws=draws,
+                                return_latents="stats")
+        out = []
+        for b, rs in zip(keep, res):
+            for r in rs:
+                mu = r["mean"].astype(np.float64)
+                st["mu_sum"] += mu
+                st["mu_sq"] += mu * mu
+                st["captions"] += 1
+            out.append({"image_id": picture_ids[b], "captions": [{k: (int(r[k]) if k == "tokens" else float(r[k]))
+                                                                   for k in ("tokens", "elbo", "iwae", "rec", "kl", "ess")} for r in rs]})
+        return out
 
     def caption_evaluator(self, references):
         """evaluate.CaptionEvaluator of the images whose human captions are `references` (per image a list of token-id lists), on this
