@@ -14,6 +14,7 @@ import torch
 from . import abi, spec
 from .abi import ptr as P
 from .engine import TAIL, CaptionEngine, FlatStore, _stream, internal_caption_variables, _round
+from .vgg_plan import WINO, conv_plan
 
 
 def imagenet_weights(weight_file):
@@ -53,13 +54,8 @@ class VggEngine(object):
         # the weight gradient of layer l and the data-gradient chain (layer l, then l-1 ...) are independent:
         # wgrads run on a side stream so that the tail of one kernel (the last partial round of workgroups)
         # is filled by the other instead of idling the chip
-        # Convolution dispatch ("which kernel runs which layer").  Activations between conv1_1 and pool5 are in the
-        # C4 layout [B][C/4][H][W][4] (include/vaecap.h); the reference's NHWC order is restored at the fc1 boundary.
-        #   conv1_1 (3 -> 64 channels, HBM-bound)      csrc/conv_first.hip
-        #   every other 3x3 layer, forward / dgrad     Winograd F(4x4,3x3) (csrc/conv_wino4.hip) where vc_conv3x3_wino4_preferred, else F(2x2,3x3) (conv_wino.hip)
-        #   weight gradient                            Winograd F(3x3,2x2) (csrc/conv_wino_wgrad.hip)
-        #   VC_CONV_WINO=0, or shapes neither takes    the NHWC implicit-GEMM kernels of csrc/conv.hip behind layout conversions (slow; also the
-        #                                              independent checker of tests/)
+        # Convolution dispatch: which kernel runs which layer, pass and launch is decided once per shape by vgg_plan.conv_plan (the rules are
+        # in its docstring, the table of kernels in DESIGN.md section 4); forward / backward / _pack_weights execute the plan of self._plan
         self.use_conv1 = True
         self.use_wino = os.environ.get("VC_CONV_WINO", "1") != "0"
         # conv4_x / conv5_x forward + data gradient on a once-transformed input (csrc/conv_wino4.hip MODE 2; bit-identical to the fused
@@ -68,6 +64,10 @@ class VggEngine(object):
         # 21.66 (its shorter weight-gradient stream leaves the chains critical).  Default: on in the split-bf16 mode only; VC_WINO4V=1 / 0 forces.
         self._wino4v_env = os.environ.get("VC_WINO4V")
         self.vws = {}   # conv chain -> workspace of the transformed input
+        # split-bf16 mode (this engine's precision): the direct weight gradient on the bf16 matrix pipe (csrc/conv_wgrad_bx.hip) replaces
+        # the f32 Winograd F(3x3,2x2) kernel (VC_WGRAD_BX=0: A/B runs)
+        self.wgrad_bx = os.environ.get("VC_WGRAD_BX", "1") != "0"
+        self._plans = {}   # conv_plan's inputs -> ConvPlan
         # Streams: 3 = two half-batch convolution chains + the weight gradients on a third stream (the tail of one launch is filled by
         # another stream's launch; the data-parallel gradient buckets are issued from the weight-gradient stream), 1 = serial
         nstreams = int(os.environ.get("VC_VGG_STREAMS", "3"))
@@ -77,7 +77,6 @@ class VggEngine(object):
         # for the chain streams layer after layer) crashes in hipStreamEndCapture (ROCm 7.2); forward-only captures are fine.  A
         # captured step therefore runs the VGG16 on the caller's stream alone.
         self.one_stream = False
-        self.wino4 = set()
         self.part = torch.zeros(self.lib.vc_sumsq_blocks(), dtype=torch.float32, device=device)
         # sum(w^2) of the regulariser: the Adam update of step t leaves the per-workgroup sums of the NEW parameters, which are step t + 1's
         # w (0.16 ms per step saved: no second pass over 0.54 GB); invalid after any other write to the parameters
@@ -101,7 +100,7 @@ class VggEngine(object):
     def _b(self, name, shape, dtype=torch.float32):
         t = self.buf.get(name)
         shape = tuple(int(s) for s in shape)
-        if t is None or tuple(t.shape) != shape:
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype:
             t = torch.zeros(shape, dtype=dtype, device=self.dev)
             self.buf[name] = t
             # the zero-fill is enqueued on the current stream: the side streams must not touch the new
@@ -117,20 +116,29 @@ class VggEngine(object):
             self.ws = torch.empty(max(int(nbytes), 1 << 20) // 4 + 16, dtype=torch.float32, device=self.dev)
             self.ws_bytes = self.ws.numel() * 4
 
-    def _chain_ws(self, i, nb):
+    def _chain_ws(self, i, nb, need):
         """Workspace of conv chain i (one per stream: chains run concurrently) for the K-split tail launches of the
-        forward / data-gradient convolutions at nb images."""
+        forward / data-gradient convolutions at nb images: `need` bytes (ConvPlan.tail_ws_bytes)."""
         key = (i, nb)
         t = self.tail_ws.get(key)
         if t is None:
-            lib, need, H, W = self.lib, 0, 224, 224
-            for name, ci, co in spec.VGG_CONV:
-                cie = 4 if ci == 3 else ci
-                need = max(need, lib.vc_conv3x3_fwd_workspace_bytes(nb, H, W, cie, co), lib.vc_conv3x3_dgrad_workspace_bytes(nb, H, W, cie, co))
-                if name in spec.VGG_POOL_AFTER:
-                    H, W = H // 2, W // 2
             t = self.tail_ws[key] = torch.empty(max(need, 16) // 4 + 16, dtype=torch.float32, device=self.dev)
         return t
+
+    def _plan(self, B, H, W):
+        """The ConvPlan of a pass over B images of H x W under the engine's current switches (they may change between steps)."""
+        fch = 2 if (self.side is not None and B % 2 == 0 and B >= 2) else 1
+        bch = 2 if (self.side2 is not None and B % 2 == 0) else 1   # (with two streams the second one takes the weight gradients)
+        key = (B, H, W, self.train, (fch, bch), self.precision, self.use_wino, self.use_conv1, self.use_wino4v, self.wgrad_bx)
+        plan = self._plans.get(key)
+        if plan is None:
+            B, H, W, train, chains, precision, use_wino, use_conv1, wino4v, wgrad_bx = key
+            plan = self._plans[key] = conv_plan(self.lib, B, H, W, train=train, chains=chains, precision=precision, use_wino=use_wino,
+                                                use_conv1=use_conv1, wino4v=wino4v, wgrad_bx=wgrad_bx)
+        for ch, need in enumerate(plan.vws_bytes):
+            if need and (ch not in self.vws or self.vws[ch].numel() * 4 < need):
+                self.vws[ch] = torch.empty(need // 4, dtype=torch.float32, device=self.dev)
+        return plan
 
     def gemm(self, ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias=None, flags=0):
         self._need_ws(self.lib.vc_gemm_workspace_bytes(M, N, K))
@@ -143,16 +151,15 @@ class VggEngine(object):
         else:
             fn()
 
-    def _pack_weights(self, backward, H=224, W=224, nb=1):
+    def _pack_weights(self, plan):
         """Transformed (G g G^T) copies of the 3x3 kernels in the Winograd kernels' operand order (forward layout, and the flipped
-        + transposed one of the data gradient when a backward pass follows).  Runs on the weight-gradient stream, which is
-        idle during the forward pass: the forward copies first, in layer order, each followed by the event its layer's
-        launches wait for (returned as {layer: event}; conv1_1 needs none), then the data-gradient copies, which only the
+        + transposed one of the data gradient when a backward pass follows), for the layers whose plan asks for them.  Runs on the
+        weight-gradient stream, which is idle during the forward pass: the forward copies first, in layer order, each followed by
+        the event its layer's launches wait for (returned as {layer: event}), then the data-gradient copies, which only the
         backward pass waits for (self.packed_bwd)."""
         self.packed_bwd = None
-        self.wino4 = set()   # layers on the F(4x4,3x3) kernels this step
         if not self.use_wino:
-            return None
+            return {}
         lib, S = self.lib, self.store
         main = torch.cuda.current_stream()
         st = self.side2 if self.side2 is not None else (self.side if self.side is not None else main)
@@ -162,64 +169,32 @@ class VggEngine(object):
         self._pack_events = evs   # (kept alive for the step: a hipGraph capture holds their records)
         with torch.cuda.stream(st):
             sh = _stream()
-            for dgrad in ((0, 1) if backward else (0,)):
-                h, w_ = H, W
-                for name, ci, co in spec.VGG_CONV:
-                    if ci % 32 == 0:
-                        w = S.param(spec.vgg_var_names(name)[0])
-                        made = True
-                        if bool(lib.vc_conv3x3_wino4_preferred(nb, h, w_, ci, co)):
-                            # F(4x4,3x3) where it is the faster form for launches over nb images (every layer of a block between two pools has
-                            # the same H x W and at least 64 channels, so a block stays in one family: the ReLU bits pass from layer to layer)
-                            self.wino4.add(name)
-                            lib.vc_conv3x3_wino4_pack_f32(sh, ci, co, P(w), dgrad, P(self._b(("vpt_" if dgrad else "vp_") + name, (36 * ci * co,))))
-                        elif bool(lib.vc_conv3x3_wino_supported(1, h, w_, ci, co, dgrad)):
-                            lib.vc_conv3x3_wino_pack_f32(sh, ci, co, P(w), dgrad, P(self._b(("vpt_" if dgrad else "vp_") + name, (16 * ci * co,))))
-                        else:    # neither family takes the shape: csrc/conv.hip reads the HWIO kernel itself
-                            made = False
-                        if not dgrad and made:
-                            evs[name] = torch.cuda.Event()
-                            evs[name].record(torch.cuda.current_stream())
-                    if name in spec.VGG_POOL_AFTER:
-                        h, w_ = h // 2, w_ // 2
-            if backward:
+            for dgrad in ((0, 1) if self.train else (0,)):
+                for L in plan.layers:
+                    fam, n = (L.dgrad_family, L.pack_dgrad) if dgrad else (L.family, L.pack_fwd)
+                    if n:
+                        w = S.param(spec.vgg_var_names(L.name)[0])
+                        getattr(lib, WINO[fam] + "pack_f32")(sh, L.cin_eff, L.cout, P(w), dgrad, P(self._b(("vpt_" if dgrad else "vp_") + L.name, (n,))))
+                        if not dgrad:
+                            evs[L.name] = torch.cuda.Event()
+                            evs[L.name].record(torch.cuda.current_stream())
+            if self.train:
                 self.packed_bwd = torch.cuda.Event()
                 self.packed_bwd.record(torch.cuda.current_stream())
         return evs
-
-    def _wino_ok(self, name, nb, H, W, ci, co, dgrad):
-        ok = self.lib.vc_conv3x3_wino4_supported if name in self.wino4 else self.lib.vc_conv3x3_wino_supported
-        return self.use_wino and (("vpt_" if dgrad else "vp_") + name) in self.buf and bool(ok(nb, H, W, ci, co, dgrad))
 
     @property
     def use_wino4v(self):
         return self._wino4v_env != "0" if self._wino4v_env is not None else self.precision == "bf16x3"
 
-    def _wino(self, name, entry, geom=None, ch=0):
-        """The Winograd entry `entry` ("fwd_f32", "dgrad_bits_f32", "mask_words" ...) of the family that holds layer `name` this
-        step: vc_conv3x3_wino4_* (F(4x4,3x3)) or vc_conv3x3_wino_* (F(2x2,3x3)) -- same arguments in both.
-        geom = (nb, H, W, Cin, Cout, dgrad) of a forward / data-gradient LAUNCH on conv chain `ch`: where the library prefers it
-        (vc_conv3x3_wino4v_preferred: conv4_x, conv5_x) the F(4x4,3x3) call runs on a once-transformed input -- the same entry with the
-        chain's transform workspace appended, bit-identical results, same mask bits (csrc/conv_wino4.hip MODE 2)."""
-        lib = self.lib
-        if geom is not None and name in self.wino4 and self.use_wino4v and bool(lib.vc_conv3x3_wino4v_preferred(*geom)):
-            nb, H, W, ci, co, dgrad = geom
-            need = lib.vc_conv3x3_wino4v_workspace_bytes(nb, H, W, co if dgrad else ci)
-            v = self.vws.get(ch)
-            if v is None or v.numel() * 4 < need:
-                v = self.vws[ch] = torch.empty(need // 4, dtype=torch.float32, device=self.dev)
-            fn = getattr(lib, "vc_conv3x3_wino4v_" + entry)
-            return lambda *a: fn(*a, P(v), v.numel() * 4)
-        return getattr(lib, ("vc_conv3x3_wino4_" if name in self.wino4 else "vc_conv3x3_wino_") + entry)
-
-    def _wino_wgrad_ok(self, B, H, W, ci, co):
-        return self.use_wino and ci % 64 == 0 and co % 64 == 0 and bool(self.lib.vc_conv3x3_wino_wgrad_supported(B, H, W, ci, co))
-
-    def _bx_wgrad_ok(self, B, H, W, ci, co):
-        """split-bf16 mode (this engine's precision): the direct weight gradient on the bf16 matrix pipe (csrc/conv_wgrad_bx.hip) replaces
-        the f32 Winograd F(3x3,2x2) kernel (VC_WGRAD_BX=0: A/B runs)"""
-        return (self.use_wino and ci % 64 == 0 and co % 64 == 0 and self.precision == "bf16x3" and os.environ.get("VC_WGRAD_BX", "1") != "0"
-                and bool(self.lib.vc_conv3x3_bx_wgrad_supported(B, H, W, ci, co)))
+    def _wino(self, family, entry, v, ch):
+        """-> (the entry `entry` ("fwd_mask_f32", "dgrad_bits_f32" ...) of a Winograd family, its trailing arguments).  v: the launch
+        runs on a once-transformed input -- the F(4x4,3x3) entry of the same name with chain ch's transform workspace appended
+        (bit-identical results, same mask bits: csrc/conv_wino4.hip MODE 2)."""
+        if v:
+            ws = self.vws[ch]
+            return getattr(self.lib, "vc_conv3x3_wino4v_" + entry), (P(ws), ws.numel() * 4)
+        return getattr(self.lib, WINO[family] + entry), ()
 
     def colsum(self, x, rows, cols, out):
         self._need_ws(self.lib.vc_colsum_workspace_bytes(rows, cols))
@@ -272,77 +247,62 @@ class VggEngine(object):
             lib.vc_vgg_preprocess_u8(st, P(images), B, H, W, P(x))
         else:
             lib.vc_vgg_preprocess_f32(st, P(images), B, H, W, P(x))
-        c1 = bool(self.use_conv1 and self.use_wino and lib.vc_conv1_supported(B, H, W))  # conv1_1 through csrc/conv_first.hip (unpadded weights)
+        plan = self.plan = self._plan(B, H, W)
+        c1 = plan.layers[0].family == "conv1"   # conv1_1 through csrc/conv_first.hip (unpadded weights)
         w4 = self._b("w1_4", (3, 3, 4, 64))
         if not c1:
             lib.vc_pad_dim_f32(st, P(S.param("cnn/conv1_1/weights")), 9, 3, 4, 64, P(w4))
-        packed = self._pack_weights(self.train, H, W, B // 2 if (self.side is not None and B % 2 == 0 and B >= 2) else B)
+        packed = self._pack_weights(plan)
         self.acts = []  # (layer name, input tensor, H, W, Cin_eff, Cout, weights used)
-        self.mask_geom = {}  # layer name -> (images per launch, launches): forward launches that left their ReLU mask as bits
-        self.mask_family = {}  # layer name -> 4 / 2: the Winograd family whose data gradient can read those bits (its lane order)
         # The conv / pool chain of one image is independent of every other image: with two streams the
         # batch is pushed through as two half-batch chains so that the tail of each kernel (its last partial
         # round of workgroups) overlaps the other chain's kernels.  Halves are contiguous slices of the leading (image) dimension.
         main = torch.cuda.current_stream()
-        side = self.side if (self.side is not None and B % 2 == 0 and B >= 2) else None
+        side = self.side if plan.fwd_chains == 2 else None
         halves = [(0, B // 2, main), (B // 2, B // 2, side)] if side is not None else [(0, B, main)]
         if side is not None:
             side.wait_stream(main)
-        for name, ci, co in spec.VGG_CONV:
+        for L in plan.layers:
+            name, cie, co, pooled = L.name, L.cin_eff, L.cout, L.pooled
             wn, bn = spec.vgg_var_names(name)
-            cie = 4 if ci == 3 else ci
-            w = w4 if ci == 3 else S.param(wn)
+            w = w4 if cie == 4 else S.param(wn)
             y = self._b("y_" + name, (B, co // 4, H, W, 4))
-            pooled = name in spec.VGG_POOL_AFTER
             yp = self._b("p_" + name, (B, co // 4, H // 2, W // 2, 4)) if pooled else None
-            pool_bits = None   # set when every chain's forward of this pooled layer left routing codes
+            # pooled layer in training: the 2x2 max-pool is register math in the epilogue; it also leaves MaxPoolGrad's routing codes (4 bits
+            # per pooled element), so the backward pass does not re-read the pre-pool activation
+            pool_bits = self._b("pb_" + name, (L.bit_words,), dtype=torch.int32) if L.variant == "pool" else None
             for ch, (b0, nb, strm) in enumerate(halves):
-                tws = self._chain_ws(ch, nb)
+                tws = self._chain_ws(ch, nb, plan.tail_ws_bytes[0])
                 with torch.cuda.stream(strm):
                     sh = _stream()
-                    if ci == 3 and c1:  # conv1_1: its own HBM-bound kernel, unpadded weights
-                        if (self.train and "conv1_2" in self.wino4 and H % 16 == 0 and W % 16 == 0
-                                and lib.vc_conv3x3_wino_single_launch_supported(nb, H, W, co, co)):
-                            # conv1_2's F(4x4,3x3) data gradient takes its ReLU mask as bits from here instead of re-reading this activation
-                            mk = self._b("mk_%s_%d" % (name, ch), (lib.vc_conv3x3_wino4_mask_words(nb, H, W, co),), dtype=torch.int32)
-                            self.mask_geom[name], self.mask_family[name] = (nb, len(halves)), 4
-                            self._timed("conv_fwd", 2.0 * nb * H * W * 9 * ci * co,
-                                        lambda: lib.vc_conv1_fwd_mask_f32(sh, nb, H, W, P(x[b0:]), P(S.param(wn)), P(S.param(bn)), P(y[b0:]), P(mk)))
+                    fl = 2.0 * nb * H * W * 9 * (3 if cie == 4 else cie) * co
+                    # "mask": the next layer is a convolution on this output -- leave (y > 0) as bits in the lane order of ITS data gradient
+                    # (conv1_1: conv1_2's F(4x4,3x3) data gradient), per tile of THIS launch geometry
+                    mk = self._b("mk_%s_%d" % (name, ch), (L.bit_words,), dtype=torch.int32) if L.variant == "mask" else None
+                    if L.family == "conv1":  # conv1_1: its own HBM-bound kernel, unpadded weights
+                        if mk is not None:
+                            self._timed("conv_fwd", fl, lambda: lib.vc_conv1_fwd_mask_f32(sh, nb, H, W, P(x[b0:]), P(S.param(wn)), P(S.param(bn)), P(y[b0:]), P(mk)))
                         else:
-                            self._timed("conv_fwd", 2.0 * nb * H * W * 9 * ci * co,
-                                        lambda: lib.vc_conv1_fwd_f32(sh, nb, H, W, P(x[b0:]), P(S.param(wn)), P(S.param(bn)), P(y[b0:]), 1))
-                        continue
-                    fl = 2.0 * nb * H * W * 9 * ci * co
-                    if packed is not None and name in packed:   # this layer's transformed weights of this step are ready
-                        torch.cuda.current_stream().wait_event(packed[name])
-                    if self._wino_ok(name, nb, H, W, cie, co, 0):   # Winograd (calls over 2 GiB are cut into image ranges inside the library)
-                        if self.train and not pooled and lib.vc_conv3x3_wino_single_launch_supported(nb, H, W, cie, co):
-                            # the next layer is a convolution on this output: leave (y > 0) as bits in the lane order of ITS data gradient
-                            mk = self._b("mk_%s_%d" % (name, ch), (self._wino(name, "mask_words")(nb, H, W, co),), dtype=torch.int32)
-                            self.mask_geom[name] = (nb, len(halves))   # the bits are per tile of THIS launch geometry
-                            self.mask_family[name] = 4 if name in self.wino4 else 2
-                            self._timed("conv_fwd", fl, lambda: self._wino(name, "fwd_mask_f32", (nb, H, W, cie, co, 0), ch)(
-                                sh, nb, H, W, cie, co, P(x[b0:]), P(self.buf["vp_" + name]), P(S.param(bn)), P(y[b0:]), 1, P(mk)))
-                        elif pooled and self.train:
-                            # the 2x2 max-pool is register math in the epilogue; it also leaves MaxPoolGrad's routing codes (4 bits per pooled
-                            # element), so the backward pass does not re-read the pre-pool activation
-                            pb = self._b("pb_" + name, (lib.vc_conv3x3_wino_pool_words(B, H, W, co),), dtype=torch.int32)
-                            pool_bits = pb
-                            w0 = b0 * (H // 2) * (W // 2) * (co // 8)
-                            self._timed("conv_fwd", fl, lambda: self._wino(name, "fwd_pool_f32", (nb, H, W, cie, co, 0), ch)(
-                                sh, nb, H, W, cie, co, P(x[b0:]), P(self.buf["vp_" + name]), P(S.param(bn)), P(y[b0:]), P(yp[b0:]), P(pb[w0:])))
+                            self._timed("conv_fwd", fl, lambda: lib.vc_conv1_fwd_f32(sh, nb, H, W, P(x[b0:]), P(S.param(wn)), P(S.param(bn)), P(y[b0:]), 1))
+                    elif L.family in WINO:   # Winograd (calls over 2 GiB are cut into image ranges inside the library)
+                        torch.cuda.current_stream().wait_event(packed[name])   # this layer's transformed weights of this step are ready
+                        if L.variant == "mask":
+                            out = (P(y[b0:]), 1, P(mk))
+                        elif L.variant == "pool":
+                            out = (P(y[b0:]), P(yp[b0:]), P(pool_bits[b0 * (H // 2) * (W // 2) * (co // 8):]))
                         else:
-                            self._timed("conv_fwd", fl, lambda: self._wino(name, "fwd_f32", (nb, H, W, cie, co, 0), ch)(
-                                sh, nb, H, W, cie, co, P(x[b0:]), P(self.buf["vp_" + name]), P(S.param(bn)), P(y[b0:]), P(yp[b0:]) if pooled else None, 1))
-                        continue
-                    # NHWC implicit-GEMM kernels of csrc/conv.hip behind layout conversions: any shape (VC_CONV_WINO=0, odd image sizes)
-                    xn = self._to_nhwc("x_%s_%d" % (name, ch), x[b0:], nb, H, W, cie)   # (buffers keyed by layer: a shared name would be re-allocated at every shape change)
-                    yn = self._b("nhwc_y_%s_%d" % (name, ch), (nb, H, W, co))
-                    self._timed("conv_fwd", fl, lambda: lib.vc_conv3x3_fwd_f32(
-                        sh, nb, H, W, cie, co, P(xn), P(w), P(S.param(bn)), P(yn), 1, P(tws), tws.numel() * 4))
-                    lib.vc_nhwc_to_c4_f32(sh, nb, H, W, co, P(yn), P(y[b0:]))
-                    if pooled:   # (B * co / 4 planes of H x W four-channel pixels: the NHWC kernel on C4 data)
-                        lib.vc_maxpool2x2_fwd_f32(sh, nb * (co // 4), H, W, 4, P(y[b0:]), P(yp[b0:]))
+                            out = (P(y[b0:]), P(yp[b0:]) if pooled else None, 1)
+                        fn, va = self._wino(L.family, {"mask": "fwd_mask_f32", "pool": "fwd_pool_f32", "plain": "fwd_f32"}[L.variant], L.fwd_v, ch)
+                        self._timed("conv_fwd", fl, lambda: fn(sh, nb, H, W, cie, co, P(x[b0:]), P(self.buf["vp_" + name]), P(S.param(bn)), *out, *va))
+                    else:
+                        # NHWC implicit-GEMM kernels of csrc/conv.hip behind layout conversions: any shape (VC_CONV_WINO=0, odd image sizes)
+                        xn = self._to_nhwc("x_%s_%d" % (name, ch), x[b0:], nb, H, W, cie)   # (buffers keyed by layer: a shared name would be re-allocated at every shape change)
+                        yn = self._b("nhwc_y_%s_%d" % (name, ch), (nb, H, W, co))
+                        self._timed("conv_fwd", fl, lambda: lib.vc_conv3x3_fwd_f32(
+                            sh, nb, H, W, cie, co, P(xn), P(w), P(S.param(bn)), P(yn), 1, P(tws), tws.numel() * 4))
+                        lib.vc_nhwc_to_c4_f32(sh, nb, H, W, co, P(yn), P(y[b0:]))
+                        if pooled:   # (B * co / 4 planes of H x W four-channel pixels: the NHWC kernel on C4 data)
+                            lib.vc_maxpool2x2_fwd_f32(sh, nb * (co // 4), H, W, 4, P(y[b0:]), P(yp[b0:]))
             self.acts.append((name, x, H, W, cie, co, w))
             x = y
             if pooled:
@@ -422,16 +382,14 @@ class VggEngine(object):
         if after_fc is not None:
             after_fc()
         dw4 = self._b("dw1_4", (3, 3, 4, 64))
-        self._need_ws(max(lib.vc_conv1_wgrad_workspace_bytes(),
-                          max(max(lib.vc_conv3x3_wgrad_workspace_bytes(B, a[2], a[3], a[4], a[5]),
-                                  lib.vc_conv3x3_wino_wgrad_workspace_bytes(B, a[2], a[3], a[4], a[5]) if self._wino_wgrad_ok(B, a[2], a[3], a[4], a[5]) else 0,
-                                  lib.vc_conv3x3_bx_wgrad_workspace_bytes(B, a[2], a[3], a[4], a[5]) if self._bx_wgrad_ok(B, a[2], a[3], a[4], a[5]) else 0)
-                              for a in self.acts if a[0] != "P")))
+        plan = self.plan
+        layer = {L.name: L for L in plan.layers}
+        self._need_ws(plan.wgrad_ws_bytes)
         main = torch.cuda.current_stream()
         side, side2 = self.side, self.side2
         # streams: with 3, the data-gradient chain runs as two half-batch chains (main, side) and every
         # weight gradient (full batch) on side2; with 2, one full-batch chain (main) + weight gradients (side)
-        split = side2 is not None and B % 2 == 0
+        split = plan.bwd_chains == 2
         wst = side2 if split else side
         halves = [(0, B // 2, main), (B // 2, B // 2, side)] if split else [(0, B, main)]
         if self.packed_bwd is not None:   # the data-gradient weight copies made during the forward pass
@@ -450,24 +408,26 @@ class VggEngine(object):
                             lib.vc_maxpool2x2_bwd_f32(_stream(), nb * (co // 4), H, W, 4, P(x[b0:]), P(d[b0:]), P(dx[b0:]), 1)
                 d = dx
                 continue
+            L = layer[name]
             wn, bn = spec.vgg_var_names(name)
             cr = 3 if ci == 4 else ci  # algorithmic channel count (conv1_1 is zero-padded 3 -> 4)
             fl = 2.0 * B * H * W * 9 * cr * co
 
-            def wgrad(x=x, d=d, wn=wn, bn=bn, ci=ci, co=co, H=H, W=W, fl=fl):
+            def wgrad(L=L, x=x, d=d, wn=wn, bn=bn, ci=ci, co=co, H=H, W=W, fl=fl):
                 sw = _stream()
-                if ci == 4 and self.use_conv1 and self.use_wino and lib.vc_conv1_supported(B, H, W):
+                if L.wgrad == "conv1":
                     self._timed("conv_wgrad", fl, lambda: lib.vc_conv1_wgrad_f32(sw, B, H, W, P(x), P(d), P(S.grad(wn)), P(S.grad(bn)), 0, P(self.ws), self.ws_bytes))
-                elif ci != 4 and self._bx_wgrad_ok(B, H, W, ci, co):   # split-bf16 mode: direct, K = the pixels, operands split in registers
-                    self._timed("conv_wgrad", fl, lambda: lib.vc_conv3x3_bx_wgrad_f32(sw, B, H, W, ci, co, P(x), P(d), P(S.grad(wn)), P(S.grad(bn)), 0, P(self.ws), self.ws_bytes))
-                elif ci != 4 and self._wino_wgrad_ok(B, H, W, ci, co):   # Winograd F(3x3,2x2): both operands transformed in registers, K = the 2x2 tiles
-                    self._timed("conv_wgrad", fl, lambda: lib.vc_conv3x3_wino_wgrad_f32(sw, B, H, W, ci, co, P(x), P(d), P(S.grad(wn)), P(S.grad(bn)), 0, P(self.ws), self.ws_bytes))
-                else:   # csrc/conv.hip on NHWC copies (conv1_1: zero-padded 4-channel weights)
+                elif L.wgrad == "gemm":   # csrc/conv.hip on NHWC copies (conv1_1: zero-padded 4-channel weights)
                     xn, dn_ = self._to_nhwc("wx_" + wn, x, B, H, W, ci), self._to_nhwc("wd_" + wn, d, B, H, W, co)
                     self._timed("conv_wgrad", fl, lambda: lib.vc_conv3x3_wgrad_f32(sw, B, H, W, ci, co, P(xn), P(dn_), P(dw4 if ci == 4 else S.grad(wn)), P(S.grad(bn)), 0,
                                                                                    P(self.ws), self.ws_bytes))
                     if ci == 4:
                         lib.vc_pad_dim_f32(sw, P(dw4), 9, 4, 3, 64, P(S.grad(wn)))
+                else:
+                    # "bx": split-bf16 mode, direct, K = the pixels, operands split in registers
+                    # "wino": Winograd F(3x3,2x2), both operands transformed in registers, K = the 2x2 tiles
+                    fn = {"bx": lib.vc_conv3x3_bx_wgrad_f32, "wino": lib.vc_conv3x3_wino_wgrad_f32}[L.wgrad]
+                    self._timed("conv_wgrad", fl, lambda: fn(sw, B, H, W, ci, co, P(x), P(d), P(S.grad(wn)), P(S.grad(bn)), 0, P(self.ws), self.ws_bytes))
             if wst is not None:
                 wst.wait_stream(main)  # d (this layer's pre-activation gradient) is final on the chain stream(s)
                 if split:
@@ -484,26 +444,24 @@ class VggEngine(object):
                 prev_is_pool = self.acts[li - 1][0] == "P"
                 dx = self._b("dx_%d" % li, (B, ci // 4, H, W, 4))
                 for ch, (b0, nb, strm) in enumerate(halves):
-                    tws = self._chain_ws(ch, nb)
+                    tws = self._chain_ws(ch, nb, plan.tail_ws_bytes[1])
                     with torch.cuda.stream(strm):
                         sh = _stream()
-                        if (self._wino_ok(name, nb, H, W, ci, co, 1) and not prev_is_pool
-                              and self.mask_geom.get(self.acts[li - 1][0]) == (nb, len(halves))
-                              and self.mask_family.get(self.acts[li - 1][0]) == (4 if name in self.wino4 else 2)   # (bits are in their family's lane order)
-                              and lib.vc_conv3x3_wino_single_launch_supported(nb, H, W, ci, co)):
-                            # ReluGrad from the bits the previous layer's forward left (one 8-byte load per lane instead of sixteen 16-byte ones)
-                            self._timed("conv_dgrad", fl * nb / B, lambda: self._wino(name, "dgrad_bits_f32", (nb, H, W, ci, co, 1), ch)(
-                                sh, nb, H, W, ci, co, P(d[b0:]), P(self.buf["vpt_" + name]), P(self.buf["mk_%s_%d" % (self.acts[li - 1][0], ch)]), P(dx[b0:])))
-                        elif self._wino_ok(name, nb, H, W, ci, co, 1):
-                            self._timed("conv_dgrad", fl * nb / B, lambda: self._wino(name, "dgrad_f32", (nb, H, W, ci, co, 1), ch)(
-                                sh, nb, H, W, ci, co, P(d[b0:]), P(self.buf["vpt_" + name]), None if prev_is_pool else P(x[b0:]), P(dx[b0:])))
-                        else:   # csrc/conv.hip on NHWC copies
+                        if L.dgrad == "gemm":   # csrc/conv.hip on NHWC copies
                             dn_ = self._to_nhwc("d_%s_%d" % (name, ch), d[b0:], nb, H, W, co)
                             xn = None if prev_is_pool else self._to_nhwc("x_%s_%d" % (name, ch), x[b0:], nb, H, W, ci)
                             dxn = self._b("nhwc_dx_%s_%d" % (name, ch), (nb, H, W, ci))
                             self._timed("conv_dgrad", fl * nb / B, lambda: lib.vc_conv3x3_dgrad_f32(
                                 sh, nb, H, W, ci, co, P(dn_), P(w), P(xn), P(dxn), P(tws), tws.numel() * 4))
                             lib.vc_nhwc_to_c4_f32(sh, nb, H, W, ci, P(dxn), P(dx[b0:]))
+                            continue
+                        if L.dgrad == "bits":
+                            # ReluGrad from the bits the previous layer's forward left (one 8-byte load per lane instead of sixteen 16-byte ones)
+                            relu = P(self.buf["mk_%s_%d" % (self.acts[li - 1][0], ch)])
+                        else:
+                            relu = None if prev_is_pool else P(x[b0:])
+                        fn, va = self._wino(L.dgrad_family, {"bits": "dgrad_bits_f32", "plain": "dgrad_f32"}[L.dgrad], L.dgrad_v, ch)
+                        self._timed("conv_dgrad", fl * nb / B, lambda: fn(sh, nb, H, W, ci, co, P(d[b0:]), P(self.buf["vpt_" + name]), relu, P(dx[b0:]), *va))
                 d = dx
         if split:
             main.wait_stream(side)
