@@ -4,7 +4,7 @@
 
     python gen_caption.py --img_path cat.jpg --checkpoint ./checkpoints/last_run.ckpt \\
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
-        [--gen_method greedy|beam_search|sample|diverse] [--beam_size 2] [--diverse_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
+        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
         [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
@@ -117,11 +117,12 @@ class Generator(object):
         fc2 = self._vgg.forward(torch.from_numpy(x).cuda())
         return fc2.cpu().numpy(), img
 
-    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None):
+    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
         "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
         the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
-        the params unless given."""
+        the params unless given.  gen_method "marginal_greedy" / "marginal_beam" (additive): the search under the mixture of
+        `marginal_draws` latent draws (beam_size hypotheses for marginal_beam); the record also holds "marginal" and "draws"."""
         if top_k is not None:
             self.params.top_k = int(top_k)
         if top_p is not None:
@@ -141,7 +142,10 @@ class Generator(object):
             return sent
         if self.gen_method == "diverse":
             return decoder.diverse_inference(None, im_id, feature_vector, None, c_v, draws=diverse_draws)
-        raise ValueError("gen_method must be greedy, beam_search, sample or diverse")
+        if self.gen_method in ("marginal_greedy", "marginal_beam"):
+            return decoder.marginal_inference(None, im_id, feature_vector, None, c_v, method=self.gen_method, draws=marginal_draws,
+                                              beam_size=int(beam_size))
+        raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy or marginal_beam")
 
 
 if __name__ == "__main__":
@@ -151,7 +155,7 @@ if __name__ == "__main__":
     parser.add_argument("--vocab_path", default="./pickles/capt_vocab.pickle", help="Indices to words dictionary")
     parser.add_argument("--gpu", default="", help="Specify GPU number if use GPU")
     parser.add_argument("--c_v_generator", default=None, help="If use cluster vectors, specify tensorflow api model (unused, as in the reference)")
-    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample or diverse")
+    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy or marginal_beam")
     parser.add_argument("--params_path", default=None, help="specify params pickle file")
     parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size")
     parser.add_argument("--vgg_weights", default=None, help="vgg16_weights.npz for the feature extractor (additive flag)")
@@ -159,7 +163,11 @@ if __name__ == "__main__":
     parser.add_argument("--top_k", type=int, default=None, help="sampled decoding: draw from the k most likely words (0 = all; default: the params')")
     parser.add_argument("--top_p", type=float, default=None, help="sampled decoding: draw from the nucleus holding this share of the probability "
                                                                   "((0, 1], 1 = all; default: the params')")
+    parser.add_argument("--marginal_draws", type=int, default=None, help="--gen_method marginal_greedy / marginal_beam: latent draws whose "
+                                                                         "mixture is searched (1..256; default: the params' marginal_draws)")
     args = parser.parse_args()
+    if args.marginal_draws is not None and not 1 <= args.marginal_draws <= 256:
+        parser.error("--marginal_draws must be 1..256 (got %d)" % args.marginal_draws)
     if args.top_k is not None and args.top_k < 0:
         parser.error("--top_k must be >= 0 (got %d)" % args.top_k)
     if args.top_p is not None and not (0.0 < args.top_p <= 1.0):
@@ -168,7 +176,7 @@ if __name__ == "__main__":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
                           gen_method=args.gen_method, vgg_weights=args.vgg_weights)
-    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p)
+    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

@@ -41,6 +41,8 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the caption-evaluation entry vc_ngram_overlap.
  *      Added within 4 (additive, no layout change): the posterior-bound entries vc_posterior_latent_f32 / vc_gauss_kl_rows_f64 /
  *      vc_bound_reduce_f64.
+ *      Added within 4 (additive, no layout change): the marginal-decoding entries vc_mixture_topk_workspace_bytes / vc_mixture_topk_f32 /
+ *      vc_mixture_advance_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -626,6 +628,38 @@ int vc_gauss_kl_rows_f64(void* stream, long C, int S, int L, const float* mean, 
                          float prior_std, double* kl);
 int vc_bound_reduce_f64(void* stream, const float* lp, int T, int C, int K, const int32_t* len, const double* logw, double* logprob,
                         double* out);
+
+/* ------------------------------------------------------------------------------------
+ * Marginal decoding: search under the K-draw mixture p(y | I) ~ 1/K sum_k p(y | z_k, I) (generate.py: CaptionGenerator.marginal_greedy /
+ * marginal_beam_search; csrc/mixture.hip; DESIGN.md "Marginal decoding").  A hypothesis group g owns the K consecutive rows r = g*K + k
+ * (draw-minor: vc_diverse_*'s image-major rows).  Per row, x = logits[r, :V] (row pitch ld; columns >= V are never read): M_r = max x,
+ * S_r = sum_v exp(x_v - M_r), lsm_r(v) = (x_v - M_r) - log S_r, all f32 with vc_decode_pick_f32's expressions.  logw[r] (float64): the
+ * log-likelihood of the group's prefix under draw k; w_r = exp(logw[r] - max_k logw) / sum_k exp(logw - max_k logw) (float64).
+ *   mixture_topk      q_g(v) = sum_k w_r exp(x_rv - M_r) / S_r (f32, k ascending): top_p / top_i [G, kc] = the first kc (1..16, <= V) words
+ *                     of q_g under (value descending, index ascending), top_p the f32 probabilities in the form vc_beam_update takes;
+ *                     stat [G*K, 2] = (M_r, log S_r).  1 <= G <= 65535.  A group's outputs depend on its K rows only: no atomics, every
+ *                     sum in a fixed order, the same bits in every call, for any G and any place of the group in the launch.  Rows of
+ *                     dead beams may hold anything: words are selected by comparing (value, column) pairs, never through an offset
+ *                     computed from a value, top_i is always in [0, V), and a q that is not a number is reported as -1.
+ *                     Three launches: the row statistics (one workgroup per row), the best kc of every (group, 1024-column chunk), a
+ *                     per-group merge.  ws: vc_mixture_topk_workspace_bytes(G, V, kc) = G * cdiv(V, 1024) * kc * 8 bytes, 4-byte
+ *                     aligned; a smaller one is VC_EWORKSPACE.
+ *   mixture_advance   for every new group g < Gn and draw k, with src = (parent ? parent[g] : g) * K + k (parent[g]: a group of the round
+ *                     that stat / logits describe, clamped to [0, Gn)) and w = tok[g]: logw_out[g*K + k] = logw_in[src] + (double)
+ *                     lsm_src(w) (f32 term from stat, f64 sum; logw_in != logw_out), parent_rows[g*K + k] = src (NULL: not wanted),
+ *                     tok_rows[g*K + k] = w: what vc_beam_gather_f32 and the embedding gather take for the expanded rows.
+ *                     Greedy form (done [Gn], seq [Gn, Lmax], len [Gn] given, parent NULL): a group with done[g] == 0 and len[g] < Lmax
+ *                     appends w to seq[g, len[g]], len[g] += 1, and its logw advances; then done[g] = (w == eos).  A group with
+ *                     done[g] != 0 changes nothing and its logw is copied through, as is that of a group whose seq row is full.
+ *                     Beam form: done, seq and len all NULL.  One workgroup per group.
+ * K outside 1..256, kc outside 1..min(16, V), ld < V, a NULL required pointer or a mixed greedy / beam form is VC_EINVAL.
+ * ---------------------------------------------------------------------------------- */
+size_t vc_mixture_topk_workspace_bytes(long G, int V, int kc);
+int vc_mixture_topk_f32(void* stream, const float* logits, long G, int K, int V, long ld, const double* logw, int kc, float* top_p,
+                        int32_t* top_i, float* stat, void* ws, size_t ws_bytes);
+int vc_mixture_advance_f32(void* stream, const float* logits, int V, long ld, const float* stat, long Gn, int K, const int32_t* parent,
+                           const int32_t* tok, const double* logw_in, double* logw_out, int32_t* parent_rows, int32_t* tok_rows, int eos,
+                           int32_t* done, int32_t* seq, int Lmax, int32_t* len);
 
 /* ------------------------------------------------------------------------------------
  * Host-side helper (the only entry point that takes HOST pointers): CRC-32C (Castagnoli) of a byte

@@ -276,6 +276,8 @@ def main(params):
                 sent = decoder.diverse_beam_search(None, ids, pics, None, c_v)
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (groups %s)" % (t, ",".join(map(str, g))) for t, g in zip(r["captions"], r["groups"]))))
+            elif params.sample_gen in ("marginal_greedy", "marginal_beam"):   # search under the mixture of --marginal_draws latent draws
+                sent = decoder.marginal_inference(None, ids, pics, None, c_v)
             elif params.sample_gen == "beam_search":
                 sent = decoder.beam_search(None, ids, pics, None, c_v, beam_size=params.beam_size)
             else:

@@ -1050,6 +1050,164 @@ class CaptionGenerator(object):
         self.last_candidates = cands
         return res
 
+    # ------------------------------------------------------------------ marginal decoding (search under the K-draw mixture)
+    def _mixture_ws(self, tag, G, kc):
+        """vc_mixture_topk_f32's workspace for G groups of kc words, a persistent buffer of the pass (a captured round bakes it)"""
+        nbytes = int(self.lib.vc_mixture_topk_workspace_bytes(G, self.e.V, kc))
+        return self._b(tag + "mixws", (nbytes // 4,), torch.int32), nbytes
+
+    def _marginal_passes(self, B, rows_per_image):
+        """diverse()'s cut for marginal decoding: slices of images whose rows together stay within diverse_rows; an image that exceeds
+        the cap alone gets a pass of its own"""
+        G = max(1, self.diverse_rows // rows_per_image)
+        return [slice(g0, min(B, g0 + G)) for g0 in range(0, B, G)]
+
+    def _marginal_greedy_pass(self, features, c_v, eps, K, bos, eos, max_len, check_every):
+        """One pass of marginal_greedy(): the B*K rows of B images decoded together, one hypothesis group per image."""
+        lib, e = self.lib, self.e
+        c0, h0 = self._diverse_init(features, c_v, eps, K)
+        M, V = int(c0.shape[0]), e.V
+        B = M // K
+        i32 = torch.int32
+        tag = "mg%d_%d_%d_" % (B, K, max_len)
+        lay, dlay = FieldLayout([("done", B), ("len", B), ("seq", B * max_len)]), FieldLayout([("logw0", M), ("logw1", M)])
+        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), torch.float64)
+        f, logw = lay.views(ibuf), list(dlay.views(dbuf).values())
+        tok_rows, tok, tv = self._b(tag + "tok_rows", (M,), i32), self._b(tag + "tok", (B,), i32), self._b(tag + "tv", (B,))
+        stat, pending = self._b(tag + "stat", (M, 2)), self._b(tag + "pending", (1,))
+        ws, ws_bytes = self._mixture_ws(tag, B, 1)
+
+        def reset():
+            tok_rows.fill_(bos); ibuf.zero_(); dbuf.zero_()
+
+        sets, state = self._round_state(tag, M, c0, h0)
+
+        def one(r, timed):   # round r of a chunk reads logw[r & 1] and writes the other (chunks hold an even number of rounds)
+            src, dst = sets(r)
+            logits, _, _ = self.step(tok_rows, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
+            st = _stream()
+            lib.vc_mixture_topk_f32(st, P(logits), B, K, V, V, P(logw[r & 1]), 1, P(tv), P(tok), P(stat), P(ws), ws_bytes)
+            lib.vc_mixture_advance_f32(st, P(logits), V, V, P(stat), B, K, None, P(tok), P(logw[r & 1]), P(logw[1 - (r & 1)]), None, P(tok_rows),
+                                       int(eos), P(f["done"]), P(f["seq"]), max_len, P(f["len"]))
+            lib.vc_decode_round_end_i32(st, P(f["done"]), B, P(pending), None)
+
+        Kc = self._chunk_rounds(check_every)
+        steps = self._run_chunks(("marginal_greedy", B, K, Kc, max_len, int(eos)), [tok_rows, tok, tv, stat, pending, ibuf, dbuf, ws] + state,
+                                 one, reset, Kc, max_len, check_every, pending)
+        ints, dbls = self._to_host(tag, ibuf, dbuf)
+        lw = dbls[(steps % 2) * M:(steps % 2 + 1) * M].reshape(B, K).copy()   # the buffer the last round wrote
+        mx = lw.max(axis=1)
+        marg = mx + np.log(np.exp(lw - mx[:, None]).sum(axis=1)) - np.log(K)
+        ln, seq = ints[lay.off["len"]:lay.off["len"] + B].tolist(), ints[lay.off["seq"]:].tolist()
+        return [{"tokens": seq[b * max_len:b * max_len + ln[b]], "marginal": float(marg[b]), "logprob": lw[b]} for b in range(B)]
+
+    def marginal_greedy(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, max_len=None, check_every=4):
+        """Greedy decoding under the K-draw mixture p(y | I) ~ 1/K sum_k p(y | z_k, I) (DESIGN.md "Marginal decoding"): per image
+        {"tokens": ids up to and including the first <EOS> (at most max_len), "marginal": float, "logprob": float64 [K]}.
+        The K = `draws` draws of an image are diverse()'s and score()'s (z = prior_mean + std * eps[k]; eps [K, S, B, L], Philox on
+        device when None: those draws depend on how the passes are cut).  Every round steps all B*K rows, mixes each image's K next-word
+        distributions with the draws' posterior weights w_k ~ p(prefix | z_k) (vc_mixture_topk_f32), takes the mixture's best word,
+        feeds it to all K rows and adds its log-softmax to each draw's logprob (vc_mixture_advance_f32).  By the chain rule
+        marginal = logsumexp_k logprob - log K is the sum of the mixture's conditional log-probabilities of the tokens: score()'s
+        marginal of the returned caption for the same eps.  <BOS> is fed once, as in greedy().  Rounds replay as hipGraph chunks of
+        check_every rounds (VC_DECODE_GRAPH=0: the eager loop, same ids); images are decoded in passes of <= diverse_rows rows, an
+        image with all its draws in one pass.  A --no_encoder model has no z: every draw is the same and the ids are greedy()'s."""
+        K, B = int(draws), int(features.shape[0])
+        self._check_draws(K, eps, B)
+        max_len = int(max_len or self.p.gen_max_len)
+        c_v = np.asarray(c_v) if c_v is not None else None
+        eps = np.asarray(eps) if eps is not None else None
+        res = []
+        for sl in self._marginal_passes(B, K):
+            res += self._marginal_greedy_pass(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None,
+                                              K, bos, eos, max_len, check_every)
+        return res
+
+    def _marginal_beam_pass(self, features, c_v, eps, K, n, bos, eos, max_len, len_norm_f, check_every):
+        """One pass of marginal_beam_search(): B images x n hypothesis groups x K draws; rows (b*n + j)*K + k.  _beam_run's procedure
+        on ONE slice: the TopN bookkeeping is vc_beam_update's on the B*n groups, every row move goes through parent_rows / tok_rows."""
+        lib, e = self.lib, self.e
+        c0, h0 = self._diverse_init(features, c_v, eps, K)
+        BK, Hd, V = int(c0.shape[0]), self.p.decoder_hidden, e.V
+        B = BK // K
+        G = B * n
+        M = G * K
+        i32, f64 = torch.int32, torch.float64
+        tok0 = self._b("mb_tok0_%d" % BK, (BK,), i32)
+        tok0.fill_(bos)
+        _, c1, h1 = self.step(tok0, c0, h0, want="state", bufs=self._round_bufs("mb0_%d_" % BK, BK))   # decoder.py:230-236: the state only
+        L, rounds = max_len + 2, max_len - 1
+        xproj = self._project_vocab() if (M * rounds >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
+        tag = "mb%d_%d_%d_%d_" % (B, K, n, L)
+        lay = FieldLayout(beam_fields(B, n, L))
+        dlay = FieldLayout([(k_, G) for k_ in ("p_score", "c_score", "p_logprob", "c_logprob")] + [("logw0", M), ("logw1", M)])
+        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), f64)
+        iv, dv = lay.views(ibuf), dlay.views(dbuf)
+        pcount, ccount, p_len, c_len, c_slot = (iv[k_] for k_ in ("pcount", "ccount", "p_len", "c_len", "c_slot"))
+        sent, c_sent = [iv["sent0"], iv["sent1"]], iv["c_sent"]
+        p_score, c_score, p_logprob, c_logprob, logw = dv["p_score"], dv["c_score"], dv["p_logprob"], dv["c_logprob"], [dv["logw0"], dv["logw1"]]
+        c_free, parent, tok = self._b(tag + "c_free", (B,), i32), self._b(tag + "parent", (G,), i32), self._b(tag + "tok", (G,), i32)
+        parent_rows, tok_rows, rows0 = self._b(tag + "parent_rows", (M,), i32), self._b(tag + "tok_rows", (M,), i32), self._b(tag + "rows0", (M,), i32)
+        rows0.copy_(torch.arange(M, dtype=i32, device=e.dev))
+        tv, ti, stat = self._b(tag + "tv", (G, n)), self._b(tag + "ti", (G, n), i32), self._b(tag + "stat", (M, 2))
+        bufs = self._round_bufs(tag, M)
+        cg, hg, alive = self._b(tag + "cg", (M, Hd)), self._b(tag + "hg", (M, Hd)), self._b(tag + "alive", (1,))
+        ws, ws_bytes = self._mixture_ws(tag, G, n)
+        self._pack_wh(M)
+
+        def reset():   # vc_beam_init with H = K * Hd: group b*n + j starts from the K states of image b, i.e. row (b*n + j)*K + k from row b*K + k
+            lib.vc_beam_init(_stream(), B, n, L, int(bos), K * Hd, P(c1), P(h1), P(bufs["c2"]), P(bufs["h2"]), P(pcount), P(ccount), P(p_score),
+                             P(p_logprob), P(p_len), P(sent[0]), P(sent[1]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent),
+                             P(parent), P(tok))
+            parent_rows.copy_(rows0); tok_rows.fill_(bos); logw[0].zero_(); logw[1].zero_()
+
+        def one(it, timed):
+            s_, par = _stream(), it & 1
+            lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent_rows), M, Hd, P(cg), P(hg), P(xproj), P(tok_rows), V, 4 * Hd, P(bufs["gact"]))
+            logits, _, _ = self.step(tok_rows, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
+            lib.vc_mixture_topk_f32(s_, P(logits), G, K, V, V, P(logw[par]), n, P(tv), P(ti), P(stat), P(ws), ws_bytes)
+            lib.vc_beam_update(s_, B, n, L, int(eos), float(len_norm_f), P(tv), P(ti), P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len),
+                               P(sent[par]), P(sent[1 - par]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
+            lib.vc_mixture_advance_f32(s_, P(logits), V, V, P(stat), G, K, P(parent), P(tok), P(logw[par]), P(logw[1 - par]), P(parent_rows),
+                                       P(tok_rows), int(eos), None, None, 0, None)
+
+        def count_alive(steps, k):
+            lib.vc_count_nonzero_i32(_stream(), P(pcount), B, P(alive))
+
+        Kc = self._chunk_rounds(check_every)
+        steps = 0
+        if rounds > 0:
+            steps = self._run_chunks(("marginal_beam", B, K, n, L, Kc, int(eos), float(len_norm_f)),
+                                     [ibuf, dbuf, c_free, parent, tok, parent_rows, tok_rows, tv, ti, stat, cg, hg, alive, ws, xproj, self._ones_for(M)]
+                                     + list(bufs.values()), one, reset, Kc, rounds, check_every, alive, count_alive)
+        else:
+            reset()
+        ints, dbls = self._to_host(tag, ibuf, dbuf[:dlay.off["p_logprob"]])   # (the host reads the scores only)
+        return beams_from_host(ints, dbls, lay.off, B, n, L, steps & 1)
+
+    def marginal_beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, beam_size=2, max_len=None, len_norm_f=0.7,
+                             check_every=4):
+        """Beam search under the K-draw mixture (DESIGN.md "Marginal decoding"): beam_search's procedure and return shape -- per image
+        the (sentence, score) of the kept beams, descending -- with a hypothesis = one sentence carried by K decoder states, one per
+        latent draw (marginal_greedy's draws; eps [K, S, B, L]).  A round gathers the rows of the kept hypotheses (vc_beam_gather_f32 by
+        parent_rows / tok_rows), steps them, reduces each hypothesis's K rows to the mixture's beam_size best words
+        (vc_mixture_topk_f32), runs the unchanged TopN bookkeeping (vc_beam_update: its log-probabilities are now the mixture's, so a
+        caption's logprob is log 1/K sum_k p(caption | z_k)) and advances the draws' weights (vc_mixture_advance_f32).  As in
+        beam_search, <BOS> is consumed twice (the first time for the state only) and max_len - 1 rounds run.  One slice, one stream;
+        passes of <= diverse_rows rows (images x beam_size x draws), an image with all its rows in one pass.  beam_size is 1..16."""
+        K, B, n = int(draws), int(features.shape[0]), int(beam_size)
+        self._check_draws(K, eps, B)
+        if not 1 <= n <= min(16, self.e.V):
+            raise ValueError("marginal_beam_search: beam_size must be 1..16 and at most the vocabulary (got %d)" % n)
+        max_len = int(max_len or self.p.gen_max_len)
+        c_v = np.asarray(c_v) if c_v is not None else None
+        eps = np.asarray(eps) if eps is not None else None
+        res = []
+        for sl in self._marginal_passes(B, n * K):
+            res += self._marginal_beam_pass(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None,
+                                            K, n, bos, eos, max_len, len_norm_f, check_every)
+        return res
+
     # ------------------------------------------------------------------ beam search
     def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups=None):
         """The persistent device state of one slice of images (vae_model/decoder.py:238-247) and its round function.  A call decodes its

@@ -11,6 +11,9 @@ always decoded with `online_inference`, as in the reference.  `sample_gen == "di
 the consensus scores; with `"marginal"` they hold each caption's likelihood over all of the image's draws.
 `sample_gen == "diverse_beam"` (additive): group beam search (`decoder.diverse_beam_search`), written the same way: the merged ranked
 captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one in `./val_{gen_name}.json`.
+`sample_gen == "marginal_greedy"` / `"marginal_beam"` (additive): greedy decoding / beam search under the mixture of
+`params.marginal_draws` latent draws (`decoder.marginal_inference`); the records of `./val_{gen_name}.json` gain `"marginal"` (the
+caption's log-likelihood over the draws) and `"draws"`.
 `params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
 (`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed.
 `params.bound_draws = K >= 1` (additive): the same human captions are bounded with K draws from the model's own posterior
@@ -44,6 +47,8 @@ def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
         return decoder.diverse_inference(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "diverse_beam":
         return decoder.diverse_beam_search(sess, ids, images, placeholder, c_v)
+    if allow_beam and params.sample_gen in ("marginal_greedy", "marginal_beam"):
+        return decoder.marginal_inference(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "beam_search":
         return decoder.beam_search(sess, ids, images, placeholder, c_v, beam_size=params.beam_size)
     return decoder.online_inference(sess, ids, images, placeholder, c_v=c_v)[0]
@@ -111,7 +116,7 @@ def store_bounds(params, bound_records, stats):
 
 
 EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
-              "beam_diversity", "top_k", "top_p")
+              "beam_diversity", "top_k", "top_p", "marginal_draws")
 
 
 def store_metrics(params, metrics, images, captions):

@@ -27,7 +27,7 @@ _DEFAULTS = dict(
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
-    bound_draws=0,
+    bound_draws=0, marginal_draws=20,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -52,7 +52,7 @@ _FLAGS = [
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
     ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
-    ("--bound_draws", "bound_draws", int, None),
+    ("--bound_draws", "bound_draws", int, None), ("--marginal_draws", "marginal_draws", int, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -79,7 +79,11 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                             "CIDEr-D, oracle CIDEr-D, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json",
          "--bound_draws": "--mode inference: also bound the likelihood of the validation images' human captions with this many posterior "
                           "draws per caption (ELBO, importance-weighted bound, KL, effective sample size, active latent units) and "
-                          "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)"}
+                          "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)",
+         "--marginal_draws": "--sample_gen marginal_greedy / marginal_beam: latent draws per image whose mixture is searched (1..256; "
+                             "default 20)",
+         "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
+                         "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16)"}
 
 
 class Parameters(object):
@@ -132,6 +136,10 @@ class Parameters(object):
                 ap.error("--beam_size must be divisible by --beam_groups (got %d and %d)" % (self.beam_size, self.beam_groups))
             if not (0.0 <= self.beam_diversity < float("inf")):
                 ap.error("--beam_diversity must be finite and >= 0 (got %r)" % self.beam_diversity)
+        if not 1 <= self.marginal_draws <= 256:
+            ap.error("--marginal_draws must be 1..256 (got %d)" % self.marginal_draws)
+        if self.sample_gen == "marginal_beam" and not 1 <= self.beam_size <= 16:
+            ap.error("--beam_size must be 1..16 with --sample_gen marginal_beam (got %d)" % self.beam_size)
         if self.top_k < 0:
             ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
         if not (0.0 < self.top_p <= 1.0):

@@ -171,6 +171,38 @@ class Decoder(object):
         self.last_token_ids = token_ids
         return cap_list
 
+    def marginal_inference(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, method=None, draws=None, beam_size=None,
+                           len_norm_f=0.7):
+        """Decoding under the mixture of `draws` (params.marginal_draws) latent draws per image (generate.py: marginal_greedy /
+        marginal_beam_search): `method` (params.sample_gen) "marginal_greedy" takes the mixture's best word every round,
+        "marginal_beam" runs a beam search of beam_size (params.beam_size) hypotheses over it.  Returns cap_list: per image
+        {"image_id", "caption", "marginal": log 1/K sum_k p(caption | z_k, image) as the decoder accumulated it, "draws": K}."""
+        self.last_token_ids = None
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        method = method if method is not None else self.params.sample_gen
+        K = int(draws if draws is not None else self.params.marginal_draws)
+        feats = self._features(in_pictures)
+        if method == "marginal_greedy":
+            res = self._gen().marginal_greedy(feats, use_cv, None, bos, eos, draws=K, max_len=self.params.gen_max_len)
+            toks, marg = [r["tokens"] for r in res], [r["marginal"] for r in res]
+        elif method == "marginal_beam":
+            n = int(beam_size if beam_size is not None else self.params.beam_size)
+            res = self._gen().marginal_beam_search(feats, use_cv, None, bos, eos, draws=K, beam_size=n, max_len=self.params.gen_max_len,
+                                                   len_norm_f=len_norm_f)
+            toks, marg = [], []
+            for beams in res:   # a finished caption's score is logprob / len**len_norm_f (decoder.py:285-286), a cut one's its logprob
+                s, sc = beams[0]
+                toks.append(list(s))
+                marg.append(sc * len(s) ** len_norm_f if (s and s[-1] == eos and len_norm_f > 0) else sc)
+        else:
+            raise ValueError("marginal_inference: method must be 'marginal_greedy' or 'marginal_beam' (got %r)" % (method,))
+        cap_list = [{"image_id": pid, "caption": " ".join(d.idx2word[t] for t in s if t not in (bos, eos)), "marginal": float(m), "draws": K}
+                    for pid, s, m in zip(picture_ids, toks, marg)]
+        self.last_token_ids = [[list(s)] for s in toks]
+        return cap_list
+
     def score_captions(self, picture_ids, in_pictures, captions, c_v=None, draws=None):
         """Held-out likelihood of given captions (generate.py: score): captions[b] = token-id lists of image b (with or without <BOS>; the
         <EOS> counts when present), scored under `draws` (params.score_draws) prior draws.  Returns per image {"image_id", "captions":
