@@ -4,7 +4,7 @@
 
     python gen_caption.py --img_path cat.jpg --checkpoint ./checkpoints/last_run.ckpt \\
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
-        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
+        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam|constrained_beam] [--must_include "dog,puppy;frisbee"] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
         [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
@@ -117,12 +117,14 @@ class Generator(object):
         fc2 = self._vgg.forward(torch.from_numpy(x).cuda())
         return fc2.cpu().numpy(), img
 
-    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None):
+    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None, must_include=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
         "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
         the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
         the params unless given.  gen_method "marginal_greedy" / "marginal_beam" (additive): the search under the mixture of
-        `marginal_draws` latent draws (beam_size hypotheses for marginal_beam); the record also holds "marginal" and "draws"."""
+        `marginal_draws` latent draws (beam_size hypotheses for marginal_beam); the record also holds "marginal" and "draws".
+        gen_method "constrained_beam" (additive): beam search whose caption mentions the words of `must_include` ("dog,puppy;frisbee":
+        ';' separates sets, ',' the words of a set, any of which satisfies it); the record also holds "constraints", "satisfied", "score"."""
         if top_k is not None:
             self.params.top_k = int(top_k)
         if top_p is not None:
@@ -145,7 +147,13 @@ class Generator(object):
         if self.gen_method in ("marginal_greedy", "marginal_beam"):
             return decoder.marginal_inference(None, im_id, feature_vector, None, c_v, method=self.gen_method, draws=marginal_draws,
                                               beam_size=int(beam_size))
-        raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy or marginal_beam")
+        if self.gen_method == "constrained_beam":
+            from vae_captioning_amd.constraints import parse_must_include
+            w2i = self.data_dict.word2idx
+            decoder.constraints = parse_must_include(must_include or "", w2i, self.data_dict.vocab_size, w2i["<BOS>"], w2i["<EOS>"])
+            print(decoder.constraints.summary())
+            return decoder.constrained_beam_search(None, im_id, feature_vector, None, c_v)
+        raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam or constrained_beam")
 
 
 if __name__ == "__main__":
@@ -155,7 +163,7 @@ if __name__ == "__main__":
     parser.add_argument("--vocab_path", default="./pickles/capt_vocab.pickle", help="Indices to words dictionary")
     parser.add_argument("--gpu", default="", help="Specify GPU number if use GPU")
     parser.add_argument("--c_v_generator", default=None, help="If use cluster vectors, specify tensorflow api model (unused, as in the reference)")
-    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy or marginal_beam")
+    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam or constrained_beam")
     parser.add_argument("--params_path", default=None, help="specify params pickle file")
     parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size")
     parser.add_argument("--vgg_weights", default=None, help="vgg16_weights.npz for the feature extractor (additive flag)")
@@ -165,7 +173,12 @@ if __name__ == "__main__":
                                                                   "((0, 1], 1 = all; default: the params')")
     parser.add_argument("--marginal_draws", type=int, default=None, help="--gen_method marginal_greedy / marginal_beam: latent draws whose "
                                                                          "mixture is searched (1..256; default: the params' marginal_draws)")
+    parser.add_argument("--must_include", default=None, help="--gen_method constrained_beam: words the caption must mention, e.g. "
+                                                             "\"dog,puppy;frisbee\" (';' separates sets, ',' the words of a set; any word of a "
+                                                             "set satisfies it; at most 3 sets of 4 words)")
     args = parser.parse_args()
+    if (args.gen_method == "constrained_beam") != (args.must_include is not None):
+        parser.error("--gen_method constrained_beam and --must_include go together")
     if args.marginal_draws is not None and not 1 <= args.marginal_draws <= 256:
         parser.error("--marginal_draws must be 1..256 (got %d)" % args.marginal_draws)
     if args.top_k is not None and args.top_k < 0:
@@ -176,7 +189,7 @@ if __name__ == "__main__":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
                           gen_method=args.gen_method, vgg_weights=args.vgg_weights)
-    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws)
+    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws, args.must_include)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

@@ -43,6 +43,7 @@ extern "C" {
  *      vc_bound_reduce_f64.
  *      Added within 4 (additive, no layout change): the marginal-decoding entries vc_mixture_topk_workspace_bytes / vc_mixture_topk_f32 /
  *      vc_mixture_advance_f32.
+ *      Added within 4 (additive, no layout change): the constrained beam search entry vc_beam_update_constrained.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -475,6 +476,25 @@ int vc_beam_update_groups(void* stream, int B, int groups, int w, int kc, int Lm
                           double* p_logprob, int32_t* p_len, const int32_t* sent_cur, int32_t* sent_next, double* c_score,
                           double* c_logprob, int32_t* c_len, int32_t* c_slot, int32_t* c_free, int32_t* c_sent, int32_t* parent,
                           int32_t* tok);
+
+/* Constrained beam search bookkeeping after one decoder step (Anderson et al., EMNLP 2017): every image has C <= 3 constraints, each a
+ * set of <= Wc <= 4 words that is satisfied once ANY of them has been emitted, and one beam search of width w per state s = the bit mask
+ * of satisfied constraints (S = 2^C "banks", w * S <= 16).  One wave per image.  Per round every bank t is rebuilt from the OLD live beams
+ * of bank t itself -- each row's first w of its kc listed words that belong to no set t lacks -- and then of the banks one constraint
+ * short of t (missing bit ascending), which contribute every word of the missing set, forced, in table order; rows are walked in heap
+ * array order like vc_beam_update walks them, p < 1e-12 skipped, <EOS> into the bank's complete heap.
+ * The state is vc_beam_update's for B*S "virtual images" v = b*S + s of beam w (vc_beam_init with B*S images, then pcount of every bank
+ * s > 0 set to 0): rows, heaps [B*S, w]; pool c_sent [B*S, w+1, Lmax]; pcount / ccount / c_free [B*S]; parent / tok [B*S*w], where parent
+ * is the GLOBAL row (b*S + s)*w + i the new beam continues -- possibly a row of another bank of its image.
+ *   cons [B, C, Wc]      the sets, padded with -1 (entries outside [0, V) count as absent; an all-absent set is never satisfied)
+ *   top_p / top_i [B*S*w, kc]  vc_topk_rows_f32 of probs, kc = min(V, w + the largest number of constraint words of an image) <= w + C*Wc
+ *   probs [B*S*w, ld >= V]     the softmax rows the lists were made from: the forced words' probabilities are read here
+ * Rows of empty slots and banks are never read.  C == 0 is vc_beam_update(beam = w) move for move (cons and probs may be NULL). */
+int vc_beam_update_constrained(void* stream, int B, int C, int Wc, int w, int kc, int Lmax, int eos, double len_norm_f,
+                               const int32_t* cons, const float* top_p, const int32_t* top_i, const float* probs, long ld, int V,
+                               int32_t* pcount, int32_t* ccount, double* p_score, double* p_logprob, int32_t* p_len,
+                               const int32_t* sent_cur, int32_t* sent_next, double* c_score, double* c_logprob, int32_t* c_len,
+                               int32_t* c_slot, int32_t* c_free, int32_t* c_sent, int32_t* parent, int32_t* tok);
 
 /* The state vc_beam_update starts from, in ONE launch (vae_model/decoder.py:238-247: partial = [Beam([bos], state, 0.0, 0.0)], complete
  * empty): pcount = 1, ccount = 0, p_score = p_logprob = 0, p_len = 1, every sent_cur token = bos, sent_next / c_* / c_sent = 0,

@@ -252,6 +252,11 @@ def main(params):
         decoder = Decoder(None, None, None, params, cap_dict)
         if params.sample_gen == "diverse" and params.diverse_rerank == "consensus":
             decoder.consensus_index = consensus_index(params, tr, cap_dict, coco_train)
+        if params.sample_gen == "constrained_beam":   # the words the captions must mention, looked up in the vocabulary once
+            from vae_captioning_amd.constraints import load_constraints
+            decoder.constraints = load_constraints(params.constraints, cap_dict.word2idx, cap_dict.vocab_size, cap_dict.word2idx["<BOS>"],
+                                                   cap_dict.word2idx["<EOS>"], params.cbs_width)
+            say(decoder.constraints.summary())
         if params.eval_captions and rank == 0:
             decoder.train_captions = training_captions(params, coco_train)
         if coco_val is not None:  # ops/inference.py:4-56 on the validation / test image sets
@@ -278,6 +283,8 @@ def main(params):
                     say("%s: %s" % (r["image_id"], " | ".join("%s (groups %s)" % (t, ",".join(map(str, g))) for t, g in zip(r["captions"], r["groups"]))))
             elif params.sample_gen in ("marginal_greedy", "marginal_beam"):   # search under the mixture of --marginal_draws latent draws
                 sent = decoder.marginal_inference(None, ids, pics, None, c_v)
+            elif params.sample_gen == "constrained_beam":   # beam search whose captions mention the words of --constraints
+                sent = decoder.constrained_beam_search(None, ids, pics, None, c_v)
             elif params.sample_gen == "beam_search":
                 sent = decoder.beam_search(None, ids, pics, None, c_v, beam_size=params.beam_size)
             else:

@@ -172,6 +172,59 @@ def check_truncation(top_k, top_p, method="sample"):
     return int(top_k), top_p
 
 
+CBS_MAX_SETS, CBS_MAX_WORDS = 3, 4   # constrained beam search: constraints per image, words per constraint (vc_beam_update_constrained)
+
+
+def check_constraints(constraints, B, V, bos, eos, beam_size):
+    """constrained_beam_search's `constraints` (per image a list of at most 3 lists of 1..4 token ids) as the call's table:
+    (C, Wc, cons [B, C, Wc] int32 padded with -1, NW = the largest number of constraint words of an image).  C and Wc are the call's
+    largest; an image with fewer sets has all -1 sets behind its own.  ValueError for more than 3 sets, a set of more than 4 words or of
+    none, overlapping sets, ids outside [0, V), a set holding bos or eos, or beam_size << C > 16."""
+    if len(constraints) != B:
+        raise ValueError("constrained_beam_search: %d constraint lists for %d images" % (len(constraints), B))
+    w = int(beam_size)
+    C = Wc = NW = 0
+    for b, sets in enumerate(constraints):
+        if len(sets) > CBS_MAX_SETS:
+            raise ValueError("constrained_beam_search: image %d has %d constraints (at most %d)" % (b, len(sets), CBS_MAX_SETS))
+        seen = set()
+        for st in sets:
+            st = list(st)
+            if not 1 <= len(st) <= CBS_MAX_WORDS:
+                raise ValueError("constrained_beam_search: image %d has a constraint of %d words (1..%d)" % (b, len(st), CBS_MAX_WORDS))
+            for v in st:
+                if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < V:
+                    raise ValueError("constrained_beam_search: image %d: word id %r outside [0, %d)" % (b, v, V))
+                if int(v) in (int(bos), int(eos)):
+                    raise ValueError("constrained_beam_search: image %d: a constraint holds <BOS> or <EOS> (%d)" % (b, int(v)))
+                if int(v) in seen:
+                    raise ValueError("constrained_beam_search: image %d: word %d appears twice in its constraints (sets must be disjoint)" % (b, int(v)))
+                seen.add(int(v))
+            Wc = max(Wc, len(st))
+        C, NW = max(C, len(sets)), max(NW, len(seen))
+    if w < 1 or (w << C) > 16:
+        raise ValueError("constrained_beam_search: beam_size << constraints must be 1..16, got %d << %d" % (w, C))
+    cons = np.full((B, C, max(Wc, 1)), -1, np.int32)
+    for b, sets in enumerate(constraints):
+        for j, st in enumerate(sets):
+            cons[b, j, :len(st)] = [int(v) for v in st]
+    return C, max(Wc, 1), cons, NW
+
+
+def select_bank(banks, full, eos):
+    """constrained_beam_search's default result from an image's per-state lists of (sentence, score): the submasks of `full` (the
+    image's accepting state) with more satisfied constraints first, then the smaller mask; the first bank with a complete caption
+    gives the result, else the first with live beams.  -> (beams, state)."""
+    order = sorted((s for s in range(full + 1) if s & ~full == 0), key=lambda s: (-bin(s).count("1"), s))
+    for s in order:   # (a bank's list is its complete captions if it has any -- they end in <EOS> -- else its live beams, which never do)
+        if banks[s] and banks[s][0][0][-1] == eos:
+            return banks[s], s
+    for s in order:
+        if banks[s]:
+            return banks[s], s
+    return [], 0
+
+
 class CaptionGenerator(object):
     def __init__(self, engine):
         self.e = engine
@@ -1209,12 +1262,15 @@ class CaptionGenerator(object):
         return res
 
     # ------------------------------------------------------------------ beam search
-    def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups=None):
+    def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups=None, cons=None):
         """The persistent device state of one slice of images (vae_model/decoder.py:238-247) and its round function.  A call decodes its
         images as `nparts` independent slices on `nparts` streams (beam_search): buffers are per (slice, beam width, length) and a
         captured chunk of rounds bakes their addresses.
         groups = (G, diversity): group beam search (diverse_beam_search).  c, h then hold one row per "virtual image" b*G + g, a beam
-        search of width n of its own; a row has kc = min(G*n, V) candidates and the round's bookkeeping is vc_beam_update_groups."""
+        search of width n of its own; a row has kc = min(G*n, V) candidates and the round's bookkeeping is vc_beam_update_groups.
+        cons = (C, Wc, kc, table [images, C, Wc]): constrained beam search.  c, h hold one row per virtual image b*S + s, the bank of state
+        s (S = 2^C) of image b; the round is softmax + top-kc into persistent buffers + vc_beam_update_constrained, which reads the forced
+        words' probabilities from the softmax rows; the table is a persistent buffer, loaded here."""
         lib, e = self.lib, self.e
         B, Hd, V = int(c.shape[0]), self.p.decoder_hidden, e.V
         M = B * n
@@ -1225,6 +1281,10 @@ class CaptionGenerator(object):
             G, lam = int(groups[0]), float(groups[1])
             kc = min(G * n, V)
             tag = "bmg%d_%r_" % (G, lam) + tag   # (per setting: a captured chunk of one setting is never replayed for another)
+        if cons is not None:
+            C, Wc, kc, table = cons
+            S = 1 << C
+            tag = "bmc%d_%d_%d_" % (C, Wc, kc) + tag
         pt = types.SimpleNamespace(B=B, k=k)
         # everything the host reads at the end lives in TWO flat buffers (int32 fields, float64 scores): two copies into pinned memory
         # bring a slice's results back, with no gathering launches in between
@@ -1245,12 +1305,22 @@ class CaptionGenerator(object):
                          P(parent), P(tok))
         cg, hg = self._b(tag + "cg", (M, Hd)), self._b(tag + "hg", (M, Hd))
         alive = self._b(tag + "alive", (1,))
+        cons_t = probs_t = None
+        if cons is not None:   # only bank 0 starts with a beam; the constraint table of THIS call into the buffer the rounds read
+            pcount.view(B // S, S)[:, 1:] = 0
+            cons_t, probs_t = self._b(tag + "cons", (B // S, C, Wc), i32), self._b(tag + "probs", (M, V))
+            if C > 0:
+                cons_t.copy_(torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)), non_blocking=True)
 
         def one(it, timed):
             s_ = _stream()
             # every new beam continues its parent's state and feeds its last word: three row moves, one launch
             lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent), M, Hd, P(cg), P(hg), P(xproj), P(tok), V, 4 * Hd, P(bufs["gact"]))
-            if fused:   # softmax + top-k in one read of the logits (vc_softmax_topk_rows_f32: bit-identical to the two calls)
+            if cons is not None:   # the two calls for every kc: the bookkeeping reads the forced words' probabilities from the rows
+                logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
+                lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs_t), V)
+                lib.vc_topk_rows_f32(s_, P(probs_t), M, V, V, kc, P(tv), P(ti))
+            elif fused:   # softmax + top-k in one read of the logits (vc_softmax_topk_rows_f32: bit-identical to the two calls)
                 logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
                 lib.vc_softmax_topk_rows_f32(s_, P(logits), M, V, V, kc, P(tv), P(ti))
             else:
@@ -1258,7 +1328,10 @@ class CaptionGenerator(object):
                 lib.vc_topk_rows_f32(s_, P(probs), M, V, V, kc, P(tv), P(ti))
             state = (P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len), P(sent[it & 1]), P(sent[1 - (it & 1)]), P(c_score), P(c_logprob),
                      P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
-            if groups is None:
+            if cons is not None:   # the S banks of an image inside one wave; a beam may move to the bank of one more constraint
+                lib.vc_beam_update_constrained(s_, B // S, C, Wc, n, kc, L, int(eos), float(len_norm_f), P(cons_t) if C else None, P(tv), P(ti),
+                                               P(probs_t), V, V, *state)
+            elif groups is None:
                 lib.vc_beam_update(s_, B, n, L, int(eos), float(len_norm_f), P(tv), P(ti), *state)
             else:   # the G groups of an image in order inside one wave, each penalised by the words the earlier ones have just taken
                 lib.vc_beam_update_groups(s_, B // G, G, n, kc, L, int(eos), float(len_norm_f), lam, P(tv), P(ti), *state)
@@ -1271,9 +1344,11 @@ class CaptionGenerator(object):
         pt.one, pt.chunk_fn, pt.alive, pt.pcount = one, chunk_fn, alive, pcount
         # (the key names the engine's workspace: recomputed before the capture, since the eager rounds of a first call may grow it)
         kind = ("beam",) if groups is None else ("beam_groups", G, kc, lam)
+        if cons is not None:
+            kind = ("beam_constrained", C, Wc, kc)
         pt.key_fn = lambda: self._graph_key(*kind, B, n, L, K, int(eos), float(len_norm_f),
                                             tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot,
-                                                     c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M)] + list(bufs.values()))
+                                                     c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M), cons_t, probs_t] + list(bufs.values()))
         pt.graph = self._graphs.get(pt.key_fn()) if fused else None
         pt.tag, pt.ibuf, pt.scores, pt.ioff = tag, ibuf, dbuf[:dlay.off["p_logprob"]], lay.off   # (the host reads the scores only)
         pt.it, pt.last, pt.done, pt.pending = 0, 0, rounds <= 0, []
@@ -1312,9 +1387,36 @@ class CaptionGenerator(object):
         flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, groups=(G, lam))
         return [flat[b * G:(b + 1) * G] for b in range(len(flat) // G)]
 
-    def _beam_run(self, features, c_v, eps, bos, eos, n, max_len, len_norm_f, check_every, groups=None):
+    def constrained_beam_search(self, features, constraints, c_v=None, eps=None, bos=1, eos=2, beam_size=2, max_len=None, len_norm_f=0.7,
+                                check_every=4, all_states=False):
+        """Constrained beam search (Anderson et al., EMNLP 2017) for a batch of images: captions that must mention given words.
+        `constraints` is, per image, a list of at most 3 lists of 1..4 token ids; a list is satisfied once ANY of its words has been
+        emitted.  Every state -- the bit mask of satisfied constraints, 2^C of them -- has a beam search of width `beam_size` of its own
+        (beam_size << C <= 16).  Per round a state's beams are extended by their most probable words outside the sets they have not
+        satisfied yet, and a beam one constraint short of a state enters it by emitting a word of the missing set, whatever its rank.
+        Returns per image (beams, state): the (sentence, score) list, descending, of the state with the most satisfied constraints that
+        holds a complete caption (ties: the smaller mask; no complete caption anywhere: the first such state with live beams), and that
+        state's mask -- bit j tells whether constraint j was met.  all_states=True returns per image the 2^C states' lists instead (each
+        its complete captions if it has any, else its live beams).  No constraints at all is beam_search(beam_size) move for move.
+
+        The loop is beam_search's: rows [B, 2^C, beam_size]; a round is softmax + the kc = min(V, beam_size + constraint words of an
+        image) best words + vc_beam_update_constrained (one wave per image, a beam may move between its image's banks) -- same graph
+        replay, alive check and slices.  The constraint table is a persistent buffer: a captured chunk serves other constraints of
+        the same shape."""
+        B, V = int(features.shape[0]), self.e.V
+        C, Wc, table, NW = check_constraints(constraints, B, V, bos, eos, beam_size)
+        w, S = int(beam_size), 1 << C
+        flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, cons=(C, Wc, min(V, w + NW), table))
+        banks = [flat[b * S:(b + 1) * S] for b in range(B)]
+        if all_states:
+            return banks
+        full = [sum(1 << j for j in range(C) if (table[b, j] >= 0).any()) for b in range(B)]
+        return [select_bank(banks[b], full[b], int(eos)) for b in range(B)]
+
+    def _beam_run(self, features, c_v, eps, bos, eos, n, max_len, len_norm_f, check_every, groups=None, cons=None):
         """beam_search's loop over B * G "virtual images" of beam n (G = 1: beam_search itself; groups = (G, diversity): group beam
-        search, virtual image b*G + g = group g of image b).  Returns the virtual images' beams in order."""
+        search, virtual image b*G + g = group g of image b; cons = (C, Wc, kc, table [B, C, Wc]): constrained beam search, G = 2^C and
+        virtual image b*G + s = the bank of state s of image b).  Returns the virtual images' beams in order."""
         lib, e = self.lib, self.e
         max_len = max_len or self.p.gen_max_len
         t_ph = _phase("", 0.0)
@@ -1330,7 +1432,13 @@ class CaptionGenerator(object):
             G = int(groups[0])
             c, h = c.repeat_interleave(G, 0), h.repeat_interleave(G, 0)
             B *= G
+        if cons is not None:   # every bank of an image starts from the image's state (only bank 0 with a beam)
+            G = 1 << int(cons[0])
+            c, h = c.repeat_interleave(G, 0), h.repeat_interleave(G, 0)
+            B *= G
         fused = (n if groups is None else min(G * n, V)) <= 8   # (candidates per row: the fused softmax-top-k holds 8)
+        if cons is not None:   # (its round writes the probabilities to a persistent buffer: every kc can be captured)
+            fused = True
         # the words' input projections from a table (rows x rounds of lookups against ONE product over the vocabulary)
         xproj = self._project_vocab() if (B * n * rounds >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
         # Rounds run as hipGraph replays of K rounds each (nine launches per round otherwise): every buffer of a slice is persistent and
@@ -1343,8 +1451,9 @@ class CaptionGenerator(object):
         nb = B // nparts
         if nparts > 1 and lib.vc_gemm_workspace_bytes(nb * n, V, Hd) != 0:
             nparts, nb = 1, B    # (a K-split logits product writes the engine's ONE workspace: slices on two streams would share it)
-        parts = [self._beam_part(k, nparts, c[k * nb:(k + 1) * nb], h[k * nb:(k + 1) * nb], n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups)
-                 for k in range(nparts)]
+        part_cons = lambda k: None if cons is None else cons[:3] + (cons[3][k * nb // G:(k + 1) * nb // G],)   # (slices cut between images)
+        parts = [self._beam_part(k, nparts, c[k * nb:(k + 1) * nb], h[k * nb:(k + 1) * nb], n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups,
+                                 part_cons(k)) for k in range(nparts)]
         main = torch.cuda.current_stream()
         while len(self._side) < nparts - 1:
             self._side.append(torch.cuda.Stream())

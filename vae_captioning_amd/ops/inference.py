@@ -14,6 +14,9 @@ captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one i
 `sample_gen == "marginal_greedy"` / `"marginal_beam"` (additive): greedy decoding / beam search under the mixture of
 `params.marginal_draws` latent draws (`decoder.marginal_inference`); the records of `./val_{gen_name}.json` gain `"marginal"` (the
 caption's log-likelihood over the draws) and `"draws"`.
+`sample_gen == "constrained_beam"` (additive): constrained beam search (`decoder.constrained_beam_search` with the
+`constraints.Constraints` attached to the decoder); the records of `./val_{gen_name}.json` gain `"constraints"` (the token ids used),
+`"satisfied"` (one bool per constraint) and `"score"`.
 `params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
 (`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed.
 `params.bound_draws = K >= 1` (additive): the same human captions are bounded with K draws from the model's own posterior
@@ -49,6 +52,8 @@ def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
         return decoder.diverse_beam_search(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen in ("marginal_greedy", "marginal_beam"):
         return decoder.marginal_inference(sess, ids, images, placeholder, c_v)
+    if allow_beam and params.sample_gen == "constrained_beam":
+        return decoder.constrained_beam_search(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "beam_search":
         return decoder.beam_search(sess, ids, images, placeholder, c_v, beam_size=params.beam_size)
     return decoder.online_inference(sess, ids, images, placeholder, c_v=c_v)[0]
@@ -116,7 +121,7 @@ def store_bounds(params, bound_records, stats):
 
 
 EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
-              "beam_diversity", "top_k", "top_p", "marginal_draws")
+              "beam_diversity", "top_k", "top_p", "marginal_draws", "constraints", "cbs_width")
 
 
 def store_metrics(params, metrics, images, captions):

@@ -27,7 +27,7 @@ _DEFAULTS = dict(
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
-    bound_draws=0, marginal_draws=20,
+    bound_draws=0, marginal_draws=20, constraints=None, cbs_width=0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -53,6 +53,7 @@ _FLAGS = [
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
     ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
     ("--bound_draws", "bound_draws", int, None), ("--marginal_draws", "marginal_draws", int, None),
+    ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -82,8 +83,14 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                           "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)",
          "--marginal_draws": "--sample_gen marginal_greedy / marginal_beam: latent draws per image whose mixture is searched (1..256; "
                              "default 20)",
+         "--constraints": "--sample_gen constrained_beam: JSON file {image_id: [[word, ...], ...]} of the words the captions must mention "
+                          "(at most 3 sets of at most 4 words per image; a set is met by any of its words; \"*\" = every other image; words "
+                          "are vocabulary strings or integer token ids)",
+         "--cbs_width": "--sample_gen constrained_beam: beams per state of satisfied constraints (default 0 = the largest that fits, "
+                        "16 >> the number of constraints)",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
-                         "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16)"}
+                         "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
+                         "constrained_beam: beam search whose captions mention the words of --constraints"}
 
 
 class Parameters(object):
@@ -140,6 +147,13 @@ class Parameters(object):
             ap.error("--marginal_draws must be 1..256 (got %d)" % self.marginal_draws)
         if self.sample_gen == "marginal_beam" and not 1 <= self.beam_size <= 16:
             ap.error("--beam_size must be 1..16 with --sample_gen marginal_beam (got %d)" % self.beam_size)
+        if self.sample_gen == "constrained_beam":
+            if not self.constraints:
+                ap.error("--sample_gen constrained_beam needs --constraints FILE")
+            if not 0 <= self.cbs_width <= 16:
+                ap.error("--cbs_width must be 0..16 (0 = the largest that fits; got %d)" % self.cbs_width)
+        elif self.constraints is not None or args["cbs_width"] is not None:
+            ap.error("--constraints / --cbs_width belong to --sample_gen constrained_beam (got --sample_gen %s)" % self.sample_gen)
         if self.top_k < 0:
             ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
         if not (0.0 < self.top_p <= 1.0):

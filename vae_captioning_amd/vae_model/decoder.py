@@ -26,6 +26,7 @@ class Decoder(object):
         self.last_token_ids = None   # per image of the last generation call its ranked token-id lists (what --eval_captions evaluates);
                                      # every generation method clears it first, so a call that fails leaves None, never older ids
         self.bound_stats = None      # bound_captions: skipped images and the running sums behind the active-units count
+        self.constraints = None      # constraints.Constraints: what --sample_gen constrained_beam makes the captions mention
         self.train_captions = None   # flat token-id lists of the training captions: `novel` of caption_evaluator (None: not reported)
 
     def px_z_fi(self, observed, gen_mode=False):
@@ -168,6 +169,36 @@ class Decoder(object):
             cap_list.append({"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
                              "scores": [float(e[1]) for e in entries], "counts": [len(e[2]) for e in entries],
                              "groups": [[int(g) for g in e[2]] for e in entries]})
+        self.last_token_ids = token_ids
+        return cap_list
+
+    def constrained_beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, constraints=None, beam_size=None,
+                                len_norm_f=0.7):
+        """Constrained beam search (Anderson et al. 2017; generate.py: constrained_beam_search): captions that must mention given words.
+        `constraints`: per image a list of at most 3 sets of at most 4 token ids (default: self.constraints.for_images(picture_ids)); a
+        set is satisfied once any of its words is in the caption.  beam_size: beams per state (default: self.constraints.width, else the
+        largest that fits, 16 >> the largest number of sets).  Returns cap_list: per image {"image_id", "caption", "constraints": the ids
+        used, "satisfied": one bool per constraint, "score"} -- the best caption of the state with the most constraints met."""
+        self.last_token_ids = None
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        if constraints is None:
+            if self.constraints is None:
+                raise RuntimeError("constrained_beam_search needs constraints: pass them or attach decoder.constraints = "
+                                   "vae_captioning_amd.constraints.load_constraints(...)")
+            constraints = self.constraints.for_images(picture_ids)
+        if beam_size is None:
+            beam_size = self.constraints.width if self.constraints is not None else 16 >> max([len(c) for c in constraints] + [0])
+        res = self._gen().constrained_beam_search(self._features(in_pictures), constraints, use_cv, None, bos, eos, beam_size=int(beam_size),
+                                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+        cap_list, token_ids = [], []
+        for pid, sets, (beams, state) in zip(picture_ids, constraints, res):
+            toks, score = (list(beams[0][0]), float(beams[0][1])) if beams else ([], float("-inf"))
+            token_ids.append([toks])
+            cap_list.append({"image_id": pid, "caption": " ".join(d.idx2word[t] for t in toks if t not in (bos, eos)),
+                             "constraints": [[int(v) for v in st] for st in sets],
+                             "satisfied": [bool((state >> j) & 1) for j in range(len(sets))], "score": score})
         self.last_token_ids = token_ids
         return cap_list
 
