@@ -117,14 +117,17 @@ class Generator(object):
         fc2 = self._vgg.forward(torch.from_numpy(x).cuda())
         return fc2.cpu().numpy(), img
 
-    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None, must_include=None):
+    def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None, must_include=None,
+                         controls=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
         "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
         the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
         the params unless given.  gen_method "marginal_greedy" / "marginal_beam" (additive): the search under the mixture of
         `marginal_draws` latent draws (beam_size hypotheses for marginal_beam); the record also holds "marginal" and "draws".
         gen_method "constrained_beam" (additive): beam search whose caption mentions the words of `must_include` ("dog,puppy;frisbee":
-        ';' separates sets, ',' the words of a set, any of which satisfies it); the record also holds "constraints", "satisfied", "score"."""
+        ';' separates sets, ',' the words of a set, any of which satisfies it); the record also holds "constraints", "satisfied", "score".
+        controls (additive): a vae_captioning_amd.controls.DecodeControls -- no repeated n-gram, minimum length, repetition penalty,
+        banned words -- for every gen_method but the marginal ones."""
         if top_k is not None:
             self.params.top_k = int(top_k)
         if top_p is not None:
@@ -134,6 +137,7 @@ class Generator(object):
             raise ValueError("Image not found")
         self._build()
         decoder = Decoder(None, None, None, self.params, self.data_dict)
+        decoder.controls = controls
         im_id = [img_path.split("/")[-1]]
         feature_vector, image = self._get_features(img_path)
         c_v = self._c_v_generator(image) if self.params.use_c_v else None
@@ -176,7 +180,21 @@ if __name__ == "__main__":
     parser.add_argument("--must_include", default=None, help="--gen_method constrained_beam: words the caption must mention, e.g. "
                                                              "\"dog,puppy;frisbee\" (';' separates sets, ',' the words of a set; any word of a "
                                                              "set satisfies it; at most 3 sets of 4 words)")
+    parser.add_argument("--no_repeat_ngram", type=int, default=0, help="no n-gram of this length twice in the caption (0..8; 0 = off)")
+    parser.add_argument("--min_len", type=int, default=0, help="no <EOS> before this many words (0 = off)")
+    parser.add_argument("--repetition_penalty", type=float, default=1.0, help="the logit of every word already in the caption is divided "
+                                                                              "(positive) or multiplied (negative) by this (1..10; 1 = off)")
+    parser.add_argument("--must_exclude", default=None, help="words the caption must not hold, e.g. \"a,the\" (vocabulary words or token ids)")
     args = parser.parse_args()
+    if not 0 <= args.no_repeat_ngram <= 8:
+        parser.error("--no_repeat_ngram must be 0..8 (got %d)" % args.no_repeat_ngram)
+    if args.min_len < 0:
+        parser.error("--min_len must be >= 0 (got %d)" % args.min_len)
+    if not (1.0 <= args.repetition_penalty <= 10.0):
+        parser.error("--repetition_penalty must be in [1, 10] (got %r)" % args.repetition_penalty)
+    controlled = args.no_repeat_ngram or args.min_len or args.repetition_penalty != 1.0 or args.must_exclude is not None
+    if controlled and args.gen_method in ("marginal_greedy", "marginal_beam"):
+        parser.error("--no_repeat_ngram / --min_len / --repetition_penalty / --must_exclude do not go with --gen_method %s" % args.gen_method)
     if (args.gen_method == "constrained_beam") != (args.must_include is not None):
         parser.error("--gen_method constrained_beam and --must_include go together")
     if args.marginal_draws is not None and not 1 <= args.marginal_draws <= 256:
@@ -189,7 +207,13 @@ if __name__ == "__main__":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
                           gen_method=args.gen_method, vgg_weights=args.vgg_weights)
-    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws, args.must_include)
+    controls = None
+    if controlled:
+        from vae_captioning_amd.controls import DecodeControls, parse_banned
+        words = [int(w) if w.lstrip("-").isdigit() else w for w in (x.strip() for x in (args.must_exclude or "").split(",")) if w]
+        controls = DecodeControls(args.no_repeat_ngram, args.min_len, args.repetition_penalty, parse_banned(words, generator.data_dict))
+    caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws, args.must_include,
+                                         controls)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

@@ -44,6 +44,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the marginal-decoding entries vc_mixture_topk_workspace_bytes / vc_mixture_topk_f32 /
  *      vc_mixture_advance_f32.
  *      Added within 4 (additive, no layout change): the constrained beam search entry vc_beam_update_constrained.
+ *      Added within 4 (additive, no layout change): the decoding-controls entry vc_decode_controls_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -549,6 +550,27 @@ int vc_decode_pick_trunc_f32(void* stream, const float* logits, long rows, int V
 int vc_decode_round_end_i32(void* stream, const int32_t* done, long rows, float* pending, int32_t* round);
 int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32_t* seq, const int32_t* len, const int32_t* ended,
                     const double* logprob, double len_norm_f, int32_t* n_distinct, int32_t* rep, int32_t* count, double* score);
+
+/* ------------------------------------------------------------------------------------
+ * Decoding controls (csrc/decode_controls.hip; controls.py: DecodeControls): what a decoder may NOT say.  Before a round chooses words,
+ * the logits [rows, V] (ld) are processed IN PLACE from every row's history, the W caption words it has emitted so far (no <BOS>):
+ * hist[r*hist_ld + skip + i], i < W = clamp(len[r], skip, Lmax) - skip.  skip = 0: the candidate layout of vc_decode_pick_* (seq / len /
+ * done); skip = 1: the beam layout (sent_cur / p_len, position 0 = <BOS>).  len outside [0, Lmax] is clamped (beam slots past pcount hold
+ * stale lengths: nothing is read or written out of bounds for them).  Rows with done[r] != 0 (done may be NULL) are left alone; so are
+ * the columns V..ld.  History entries outside [0, V) are ignored.  In this order:
+ *   1. penalty     every DISTINCT history word w once: x[w] = x[w] > 0 ? x[w] * (1.0f / penalty) : x[w] * penalty  (f32)
+ *   2. ngram = n   (n > 0, W >= n) for every p in [n-1, W) with h[p-n+1 .. p) == h[W-n+1 .. W): h[p] is banned (n = 1: every emitted
+ *                  word; overlapping occurrences count: a a a with n = 2 bans a)
+ *   3. banned      every id of the table (sorted ascending, unique, <= 256; NULL when n_banned == 0) is banned
+ *   4. min_len     W < min_len: eos is banned
+ * Banned: x[w] = -FLT_MAX (finite: probability exactly 0 in every consumer, and top-k still returns valid, distinct indices); a ban wins
+ * over the penalty.  One wave per row; every touched logit has one owner lane and one store, so the result does not depend on rows, on
+ * the row's place in the launch or on the call.  ngram 0..8, penalty finite >= 1, min_len >= 0, 0 <= eos < V, ld >= V,
+ * 0 < Lmax <= 2048, hist_ld >= Lmax, 0 <= skip <= Lmax; ngram 0, min_len 0, penalty 1, n_banned 0 changes nothing.  rows == 0
+ * launches nothing. */
+int vc_decode_controls_f32(void* stream, float* logits, long rows, int V, long ld, const int32_t* hist, long hist_ld, int Lmax, int skip,
+                           const int32_t* len, const int32_t* done, int ngram, int min_len, int eos, float penalty, const int32_t* banned,
+                           int n_banned);
 
 /* ------------------------------------------------------------------------------------
  * Consensus re-ranking of diverse captions (consensus.py: ConsensusIndex; Devlin et al. 2015).  An index of D images (fc2 feature row,

@@ -257,6 +257,10 @@ def main(params):
             decoder.constraints = load_constraints(params.constraints, cap_dict.word2idx, cap_dict.vocab_size, cap_dict.word2idx["<BOS>"],
                                                    cap_dict.word2idx["<EOS>"], params.cbs_width)
             say(decoder.constraints.summary())
+        from vae_captioning_amd.controls import from_params   # --no_repeat_ngram / --min_len / --repetition_penalty / --banned_words
+        decoder.controls = from_params(params, cap_dict)
+        if decoder.controls is not None:
+            say(decoder.controls.summary())
         if params.eval_captions and rank == 0:
             decoder.train_captions = training_captions(params, coco_train)
         if coco_val is not None:  # ops/inference.py:4-56 on the validation / test image sets

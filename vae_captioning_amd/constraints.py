@@ -9,6 +9,18 @@ import json
 MAX_SETS, MAX_WORDS, MAX_ROWS = 3, 4, 16   # vc_beam_update_constrained: constraints per image, words per constraint, beams x states
 
 
+def lookup_word(word, word2idx, V, special=()):
+    """A word of a constraints or banned-words list as a token id: a string is looked up in the vocabulary, an integer is taken as an
+    id.  None for an unknown word (a string the vocabulary lacks, an id outside [0, V), an id in `special`); ValueError for anything
+    that is neither a string nor an integer."""
+    if isinstance(word, bool) or not isinstance(word, (int, str)):
+        raise ValueError("a word must be a string or an integer id (got %r)" % (word,))
+    v = word2idx.get(word) if isinstance(word, str) else word
+    if v is None or not 0 <= int(v) < V or int(v) in special:
+        return None
+    return int(v)
+
+
 class Constraints(object):
     """by_id {str(image_id): [[token id, ...], ...]}, default (the "*" entry or []), C = the largest number of sets of an entry,
     width = beams per state, dropped_words / dropped_sets = what cleaning removed."""
@@ -40,8 +52,8 @@ class Constraints(object):
             for word in st:
                 if isinstance(word, bool) or not isinstance(word, (int, str)):
                     raise ValueError("constraints: entry %r: a word must be a string or an integer id (got %r)" % (key, word))
-                v = word2idx.get(word) if isinstance(word, str) else word
-                if v is None or not 0 <= int(v) < V or int(v) in special:
+                v = lookup_word(word, word2idx, V, special)
+                if v is None:
                     self.dropped_words += 1
                     continue
                 if int(v) in ids:

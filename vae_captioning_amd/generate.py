@@ -20,6 +20,7 @@ import torch
 
 from . import spec
 from .abi import ptr as P
+from .controls import MAX_BANNED, active as active_controls
 from .engine import K_CL, _stream
 
 # vae_model/decoder.py:56 -- category ids absent from MSCOCO (obj_vectors/category_index.pickle)
@@ -535,6 +536,51 @@ class CaptionGenerator(object):
                 break
         return steps
 
+    # ------------------------------------------------------------------ decoding controls
+    def _controls_table(self, tag, ctl):
+        """The banned words of THIS call in the persistent buffer the rounds of `tag` read (a captured chunk bakes its address and the
+        number of words, not the words: it serves another list of the same length)."""
+        table = self._b(tag + "banned", (MAX_BANNED,), torch.int32)
+        if ctl.banned.size:
+            table[:ctl.banned.size].copy_(torch.from_numpy(ctl.banned), non_blocking=True)
+        return table
+
+    def _apply_controls(self, ctl, table, logits, rows, hist, hist_ld, skip, lens, done, eos):
+        """One vc_decode_controls_f32 launch on a round's logits [rows, V], in place, between the logits product and the round's pick /
+        softmax / top-k.  hist [rows, hist_ld] / lens / done: the rows' histories (skip = 1: position 0 is <BOS>)."""
+        n = int(ctl.banned.size)
+        self.lib.vc_decode_controls_f32(_stream(), P(logits), rows, self.e.V, self.e.V, P(hist), hist_ld, hist_ld, skip, P(lens),
+                                        P(done) if done is not None else None, ctl.no_repeat_ngram, ctl.min_len, int(eos),
+                                        ctl.repetition_penalty, P(table) if n else None, n)
+
+    def _greedy_controls(self, ctl, features, c_v, eps, bos, eos, max_len, check_every):
+        """greedy() under decoding controls: the rounds keep a candidate per row (diverse()'s bookkeeping: seq, len, ended), which is
+        the history the controls read, and pick with vc_decode_pick_f32 (argmax) -- still hipGraph chunks of check_every rounds."""
+        lib, e = self.lib, self.e
+        c0, h0 = self.init_state(features, c_v, eps)
+        B, V, i32 = int(c0.shape[0]), e.V, torch.int32
+        tag = "gc%d_%d_" % (B, max_len)
+        seq, ln, ended = self._b(tag + "seq", (B, max_len), i32), self._b(tag + "len", (B,), i32), self._b(tag + "ended", (B,), i32)
+        tok, logprob, pending = self._b(tag + "tok", (B,), i32), self._b(tag + "lp", (B,), torch.float64), self._b(tag + "pending", (1,))
+        table = self._controls_table(tag, ctl)
+        sets, state = self._round_state(tag, B, c0, h0)
+
+        def reset():
+            tok.fill_(bos); ended.zero_(); ln.zero_(); logprob.zero_()
+
+        def one(r, timed):
+            src, dst = sets(r)
+            logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
+            self._apply_controls(ctl, table, logits, B, seq, max_len, 0, ln, ended, eos)
+            lib.vc_decode_pick_f32(_stream(), P(logits), B, V, V, 1.0, None, 1, None, int(eos), P(tok), P(ended), P(seq), max_len, P(ln), P(logprob))
+            lib.vc_decode_round_end_i32(_stream(), P(ended), B, P(pending), None)
+
+        K = self._chunk_rounds(check_every)
+        self._run_chunks(("greedy_controls", B, K, max_len, int(eos)) + ctl.key(), [seq, ln, ended, tok, logprob, pending, table] + state,
+                         one, reset, K, max_len, check_every, pending)
+        rows, lens = seq.cpu().numpy(), ln.cpu().numpy()
+        return [rows[b, :lens[b]].tolist() for b in range(B)]
+
     # ------------------------------------------------------------------ greedy (online_inference)
     def _trim(self, ids, eos):
         """[steps, B] token ids -> per image the tokens up to and including its first <EOS>."""
@@ -545,14 +591,20 @@ class CaptionGenerator(object):
             out.append(col[:col.index(eos) + 1] if eos in col else col)
         return out
 
-    def greedy(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, check_every=4):
+    def greedy(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, check_every=4, controls=None):
         """decoder.py:145-201 with sample_gen='greedy' for a batch of images: returns the list
         of generated token-id lists (each ends with <EOS> unless max_len was hit).  Tokens stay on the
         device; the host only asks "has every image emitted <EOS>?" every `check_every` steps (4 bytes, vc_eos_track_i32).
         Rounds run as hipGraph replays of `check_every` decoder steps each (embedding gather, input projection, LSTM step, logits,
-        argmax, stop-word tracking: six launches per step otherwise); VC_DECODE_GRAPH=0 keeps the eager loop -- same kernels, same ids."""
+        argmax, stop-word tracking: six launches per step otherwise); VC_DECODE_GRAPH=0 keeps the eager loop -- same kernels, same ids.
+        controls: a controls.DecodeControls (no repeated n-gram, minimum length, repetition penalty, banned words; DESIGN.md "Decoding
+        controls"): every round's logits are processed from the row's words so far before the argmax.  None or a no-op value: this path."""
         lib, e = self.lib, self.e
         max_len = max_len or self.p.gen_max_len
+        ctl = active_controls(controls)
+        if ctl is not None:
+            ctl.check(e.V, eos, max_len)
+            return self._greedy_controls(ctl, features, c_v, eps, bos, eos, int(max_len), check_every)
         c0, h0 = self.init_state(features, c_v, eps)
         B, V = c0.shape[0], e.V
         K = self._chunk_rounds(check_every)
@@ -576,13 +628,19 @@ class CaptionGenerator(object):
         steps = self._run_chunks(("greedy", B, K, int(eos)), [chunk, done, pending] + state, one, done.zero_, K, max_len, check_every, pending, keep)
         return self._trim(ids[:steps], eos)
 
-    def sample(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, uniforms=None, check_every=4, top_k=0, top_p=1.0):
+    def sample(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, uniforms=None, check_every=4, top_k=0, top_p=1.0,
+               controls=None):
         """decoder.py:145-201 with sample_gen='sample': tokens drawn from softmax(logits / temperature)
         (tf.multinomial).  uniforms [max_len, B] in [0,1) may be injected; otherwise Philox.
         top_k > 0 / top_p < 1: the draw is truncated to the top_k best words and / or the smallest set of best words holding a share
-        top_p of the probability (vc_decode_pick_trunc_f32; DESIGN.md "Truncated sampling"); the defaults leave it as it is."""
+        top_p of the probability (vc_decode_pick_trunc_f32; DESIGN.md "Truncated sampling"); the defaults leave it as it is.
+        controls: a controls.DecodeControls; the draw is from the softmax of the processed logits (then truncated, if asked).  The
+        rows' candidates are then always kept, and an untruncated draw is vc_decode_pick_f32's (vc_multinomial_rows_f32's token)."""
         top_k, top_p = check_truncation(top_k, top_p)
         max_len = max_len or self.p.gen_max_len
+        ctl = active_controls(controls)
+        if ctl is not None:
+            ctl.check(self.e.V, eos, max_len)
         c, h = self.init_state(features, c_v, eps)
         B = c.shape[0]
         tok = torch.full((B,), bos, dtype=torch.int32, device=self.e.dev)
@@ -591,13 +649,16 @@ class CaptionGenerator(object):
         ud = self._dev(uniforms, np.float32) if uniforms is not None else None
         steps = 0
         trunc = top_k != 0 or top_p != 1.0
-        if trunc:   # the entry keeps a candidate per row (diverse()'s bookkeeping): scratch here, the ids are what sample() returns
+        if trunc or ctl is not None:   # the entry keeps a candidate per row (diverse()'s bookkeeping): scratch here, the ids are what sample() returns
             i32 = torch.int32
             t_done, t_len, t_seq = self._b("st_done", (B,), i32), self._b("st_len", (B,), i32), self._b("st_seq", (B, max_len), i32)
             t_lp = self._b("st_lp", (B,), torch.float64)
             t_done.zero_(); t_len.zero_(); t_lp.zero_()
+            table = self._controls_table("st_", ctl) if ctl is not None else None
         for it in range(max_len):
             logits, c, h = self.step(tok, c, h, want="logits")
+            if ctl is not None:
+                self._apply_controls(ctl, table, logits, B, t_seq, max_len, 0, t_len, t_done, eos)
             if ud is not None:
                 u = ud[it]
             else:
@@ -606,6 +667,9 @@ class CaptionGenerator(object):
             if trunc:
                 self.lib.vc_decode_pick_trunc_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), top_k, top_p, P(u), 1,
                                                   None, int(eos), P(tok), P(t_done), P(t_seq), max_len, P(t_len), P(t_lp), None)
+            elif ctl is not None:
+                self.lib.vc_decode_pick_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), 1, None, int(eos), P(tok),
+                                            P(t_done), P(t_seq), max_len, P(t_len), P(t_lp))
             else:
                 self.lib.vc_multinomial_rows_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), P(tok))
             steps = it + 1
@@ -658,7 +722,7 @@ class CaptionGenerator(object):
         return cs1[1], hs1[1]
 
     def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every, rerank="likelihood",
-                      top_k=0, top_p=1.0):
+                      top_k=0, top_p=1.0, ctl=None):
         """One pass of diverse(): the B*K candidate rows of B images decoded together, ranked per image on device (vc_diverse_rank),
         results in two flat buffers brought back by two copies into pinned memory."""
         lib, e, p = self.lib, self.e, self.p
@@ -680,6 +744,7 @@ class CaptionGenerator(object):
                 lib.vc_philox_uniform_f32(_stream(), P(ud), ud.numel(), e.seed * 1000003 + 29, 7 << 32, P(e.step))
         temp = float(p.temperature) if method == "sample" else 1.0
         trunc = top_k != 0 or top_p != 1.0
+        table = self._controls_table(tag, ctl) if ctl is not None else None
 
         def reset():
             tok.fill_(bos); f["ended"].zero_(); f["len"].zero_(); logprob.zero_(); rnd.zero_()
@@ -689,6 +754,8 @@ class CaptionGenerator(object):
         def one(r, timed):
             src, dst = sets(r)
             logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
+            if ctl is not None:   # the candidates so far are the histories
+                self._apply_controls(ctl, table, logits, M, f["seq"], max_len, 0, f["len"], f["ended"], eos)
             if trunc:
                 lib.vc_decode_pick_trunc_f32(_stream(), P(logits), M, V, V, temp, top_k, top_p, P(ud), max_len, P(rnd), int(eos), P(tok),
                                              P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob), None)
@@ -698,8 +765,8 @@ class CaptionGenerator(object):
             lib.vc_decode_round_end_i32(_stream(), P(f["ended"]), M, P(pending), P(rnd))
 
         Kc = self._chunk_rounds(check_every)
-        self._run_chunks(("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p),   # (a captured chunk bakes the truncation)
-                         [tok, rnd, pending, ibuf, dbuf, ud] + state, one, reset, Kc, max_len, check_every, pending)
+        self._run_chunks(("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p) + (ctl.key() if ctl is not None else ()),   # (a captured chunk bakes the truncation and the controls)
+                         [tok, rnd, pending, ibuf, dbuf, ud] + ([table] if ctl is not None else []) + state, one, reset, Kc, max_len, check_every, pending)
         lib.vc_diverse_rank(_stream(), M, B, K, max_len, P(f["seq"]), P(f["len"]), P(f["ended"]), P(logprob), float(len_norm_f),
                             P(f["n_distinct"]), P(f["rep"]), P(f["count"]), P(score))
         res, cands = diverse_from_host(*self._to_host(tag, ibuf, dbuf), lay.off, B, K, max_len, n_best if rerank != "marginal" else None, candidates=True)
@@ -1060,7 +1127,7 @@ class CaptionGenerator(object):
         return res
 
     def diverse(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, method="greedy", n_best=None, max_len=None, len_norm_f=0.7,
-                uniforms=None, check_every=4, rerank="likelihood", top_k=0, top_p=1.0):
+                uniforms=None, check_every=4, rerank="likelihood", top_k=0, top_p=1.0, controls=None):
         """Diverse captioning (the AG-CVAE paper's purpose of z): per image `draws` = K independent latent draws, each decoded with
         `greedy` (argmax) or `sample` (inverse CDF at params.temperature) up to and including its first <EOS> (at most max_len tokens),
         log-likelihood = sum of the emitted tokens' log-softmax at temperature 1 (f32 terms, f64 sum), score = logprob / (1 + n)**len_norm_f
@@ -1078,7 +1145,10 @@ class CaptionGenerator(object):
         with `score` the new one.  n_best cuts after the re-ranking.  "likelihood" (default) is the order described above.
         top_k > 0 / top_p < 1 (method="sample" only): every draw's tokens come from the truncated distribution (the top_k best words and /
         or the smallest set of best words holding a share top_p of the probability; DESIGN.md "Truncated sampling"); log-likelihoods stay
-        the model's, over the full vocabulary, so score() of a candidate under its own draw still returns its logprob."""
+        the model's, over the full vocabulary, so score() of a candidate under its own draw still returns its logprob.
+        controls: a controls.DecodeControls; every draw is decoded from the softmax of its PROCESSED logits and `logprob` is taken
+        under it (DESIGN.md "Decoding controls": a penalty has no "model's own" reading); rerank="marginal" still re-scores under the
+        unprocessed model.  None or a no-op value: the launches and graph keys of a call without the keyword."""
         K, B = int(draws), int(features.shape[0])
         self._check_draws(K, eps, B)
         if method not in ("greedy", "sample"):
@@ -1087,6 +1157,9 @@ class CaptionGenerator(object):
             raise ValueError("rerank must be 'likelihood' or 'marginal' (got %r)" % (rerank,))
         top_k, top_p = check_truncation(top_k, top_p, method)
         max_len = int(max_len or self.p.gen_max_len)
+        ctl = active_controls(controls)
+        if ctl is not None:
+            ctl.check(self.e.V, eos, max_len)
         if uniforms is not None and tuple(np.shape(uniforms)) != (K, max_len, B):
             raise ValueError("uniforms must be [draws, max_len, images] = %s" % ((K, max_len, B),))
         if c_v is not None:
@@ -1097,7 +1170,7 @@ class CaptionGenerator(object):
             sl = slice(g0, min(B, g0 + G))
             r, c = self._diverse_pass(features[sl], c_v[sl] if c_v is not None else None, np.asarray(eps)[:, :, sl] if eps is not None else None,
                                       K, method, bos, eos, max_len, len_norm_f, n_best,
-                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every, rerank, top_k, top_p)
+                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every, rerank, top_k, top_p, ctl)
             res += r
             cands += c
         self.last_candidates = cands
@@ -1262,7 +1335,7 @@ class CaptionGenerator(object):
         return res
 
     # ------------------------------------------------------------------ beam search
-    def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups=None, cons=None):
+    def _beam_part(self, k, nparts, c, h, n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups=None, cons=None, ctl=None):
         """The persistent device state of one slice of images (vae_model/decoder.py:238-247) and its round function.  A call decodes its
         images as `nparts` independent slices on `nparts` streams (beam_search): buffers are per (slice, beam width, length) and a
         captured chunk of rounds bakes their addresses.
@@ -1270,7 +1343,9 @@ class CaptionGenerator(object):
         search of width n of its own; a row has kc = min(G*n, V) candidates and the round's bookkeeping is vc_beam_update_groups.
         cons = (C, Wc, kc, table [images, C, Wc]): constrained beam search.  c, h hold one row per virtual image b*S + s, the bank of state
         s (S = 2^C) of image b; the round is softmax + top-kc into persistent buffers + vc_beam_update_constrained, which reads the forced
-        words' probabilities from the softmax rows; the table is a persistent buffer, loaded here."""
+        words' probabilities from the softmax rows; the table is a persistent buffer, loaded here.
+        ctl = an active controls.DecodeControls: one vc_decode_controls_f32 launch on the round's logits, the histories being the live
+        beams' sentences (sent[it & 1] / p_len, position 0 = <BOS>); its banned table is a persistent buffer too."""
         lib, e = self.lib, self.e
         B, Hd, V = int(c.shape[0]), self.p.decoder_hidden, e.V
         M = B * n
@@ -1311,12 +1386,29 @@ class CaptionGenerator(object):
             cons_t, probs_t = self._b(tag + "cons", (B // S, C, Wc), i32), self._b(tag + "probs", (M, V))
             if C > 0:
                 cons_t.copy_(torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)), non_blocking=True)
+        ban_t = self._controls_table(tag, ctl) if ctl is not None else None
+
+        def controlled(it, timed):   # the round's logits, processed in place from the live beams' sentences
+            logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
+            self._apply_controls(ctl, ban_t, logits, M, sent[it & 1], L, 1, p_len, None, eos)
+            return logits
 
         def one(it, timed):
             s_ = _stream()
             # every new beam continues its parent's state and feeds its last word: three row moves, one launch
             lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent), M, Hd, P(cg), P(hg), P(xproj), P(tok), V, 4 * Hd, P(bufs["gact"]))
-            if cons is not None:   # the two calls for every kc: the bookkeeping reads the forced words' probabilities from the rows
+            if ctl is not None:   # (None: the launches below, exactly)
+                logits = controlled(it, timed)
+                if cons is not None:
+                    lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs_t), V)
+                    lib.vc_topk_rows_f32(s_, P(probs_t), M, V, V, kc, P(tv), P(ti))
+                elif fused:
+                    lib.vc_softmax_topk_rows_f32(s_, P(logits), M, V, V, kc, P(tv), P(ti))
+                else:
+                    probs = torch.empty_like(logits)
+                    lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs), V)
+                    lib.vc_topk_rows_f32(s_, P(probs), M, V, V, kc, P(tv), P(ti))
+            elif cons is not None:   # the two calls for every kc: the bookkeeping reads the forced words' probabilities from the rows
                 logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
                 lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs_t), V)
                 lib.vc_topk_rows_f32(s_, P(probs_t), M, V, V, kc, P(tv), P(ti))
@@ -1346,15 +1438,17 @@ class CaptionGenerator(object):
         kind = ("beam",) if groups is None else ("beam_groups", G, kc, lam)
         if cons is not None:
             kind = ("beam_constrained", C, Wc, kc)
+        if ctl is not None:
+            kind = kind + ctl.key()
         pt.key_fn = lambda: self._graph_key(*kind, B, n, L, K, int(eos), float(len_norm_f),
                                             tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot,
-                                                     c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M), cons_t, probs_t] + list(bufs.values()))
+                                                     c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M), cons_t, probs_t] + ([ban_t] if ctl is not None else []) + list(bufs.values()))
         pt.graph = self._graphs.get(pt.key_fn()) if fused else None
         pt.tag, pt.ibuf, pt.scores, pt.ioff = tag, ibuf, dbuf[:dlay.off["p_logprob"]], lay.off   # (the host reads the scores only)
         pt.it, pt.last, pt.done, pt.pending = 0, 0, rounds <= 0, []
         return pt
 
-    def beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, beam_size=2, max_len=None, len_norm_f=0.7, check_every=4):
+    def beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, beam_size=2, max_len=None, len_norm_f=0.7, check_every=4, controls=None):
         """decoder.py:203-320 for a batch of images.  Returns per image the list of
         (sentence, score) of the kept beams in descending score order.
 
@@ -1365,11 +1459,15 @@ class CaptionGenerator(object):
         Images are independent, and a round is a chain of one throughput-bound kernel (the logits product) and four latency-bound
         ones (state gather, LSTM step, top-k, the heap bookkeeping: together half the round's time at 640 rows, on a fraction of
         the CUs).  A batch of >= 512 rows is therefore decoded as TWO slices of images on two streams: while one slice is in its
-        latency-bound kernels the other's logits product has the CUs.  VC_DECODE_SLICES=1 keeps one slice -- same beams."""
-        return self._beam_run(features, c_v, eps, bos, eos, int(beam_size), max_len, len_norm_f, check_every)
+        latency-bound kernels the other's logits product has the CUs.  VC_DECODE_SLICES=1 keeps one slice -- same beams.
+
+        controls: a controls.DecodeControls; every round's logits are processed from each live beam's words so far (one
+        vc_decode_controls_f32 launch before the softmax), and probabilities, the p < 1e-12 skip and scores are taken under the softmax
+        of the processed logits (DESIGN.md "Decoding controls").  None or a no-op value: the launches and graph keys of today."""
+        return self._beam_run(features, c_v, eps, bos, eos, int(beam_size), max_len, len_norm_f, check_every, ctl=self._checked_controls(controls, eos, max_len))
 
     def diverse_beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, groups=5, group_size=2, diversity=0.5, max_len=None,
-                            len_norm_f=0.7, check_every=4):
+                            len_norm_f=0.7, check_every=4, controls=None):
         """Group beam search (Diverse Beam Search, Vijayakumar et al. 2016, Hamming dissimilarity) for a batch of images: `groups`
         beam searches of width `group_size` per image advance in lock step; within a round the groups run in order, and a word that
         c live beams of the round's earlier groups have just taken costs a candidate diversity * c of its heap key (the stored
@@ -1378,17 +1476,19 @@ class CaptionGenerator(object):
         group that search.
 
         The loop is beam_search's: rows [B, groups, group_size], groups * group_size candidates per row, and vc_beam_update_groups
-        for the bookkeeping (one wave per image, its groups in order) -- same graph replay, alive check and slices."""
+        for the bookkeeping (one wave per image, its groups in order) -- same graph replay, alive check and slices.
+        controls: a controls.DecodeControls, as in beam_search (the diversity penalty acts on the processed probabilities)."""
         G, w, lam = int(groups), int(group_size), float(diversity)
         if G < 1 or w < 1 or G * w > 16:
             raise ValueError("diverse_beam_search: groups * group_size must be 1..16, got %d x %d" % (G, w))
         if not (lam >= 0.0 and lam < float("inf")):
             raise ValueError("diverse_beam_search: diversity must be finite and >= 0, got %r" % (diversity,))
-        flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, groups=(G, lam))
+        flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, groups=(G, lam),
+                              ctl=self._checked_controls(controls, eos, max_len))
         return [flat[b * G:(b + 1) * G] for b in range(len(flat) // G)]
 
     def constrained_beam_search(self, features, constraints, c_v=None, eps=None, bos=1, eos=2, beam_size=2, max_len=None, len_norm_f=0.7,
-                                check_every=4, all_states=False):
+                                check_every=4, all_states=False, controls=None):
         """Constrained beam search (Anderson et al., EMNLP 2017) for a batch of images: captions that must mention given words.
         `constraints` is, per image, a list of at most 3 lists of 1..4 token ids; a list is satisfied once ANY of its words has been
         emitted.  Every state -- the bit mask of satisfied constraints, 2^C of them -- has a beam search of width `beam_size` of its own
@@ -1402,18 +1502,29 @@ class CaptionGenerator(object):
         The loop is beam_search's: rows [B, 2^C, beam_size]; a round is softmax + the kc = min(V, beam_size + constraint words of an
         image) best words + vc_beam_update_constrained (one wave per image, a beam may move between its image's banks) -- same graph
         replay, alive check and slices.  The constraint table is a persistent buffer: a captured chunk serves other constraints of
-        the same shape."""
+        the same shape.
+        controls: a controls.DecodeControls, as in beam_search; a forced word's probability is read from the processed rows too, so a
+        constraint word that an n-gram ban or min_len rules out in a round is not forced in it.  A word both banned and in a constraint
+        set is a ValueError."""
         B, V = int(features.shape[0]), self.e.V
         C, Wc, table, NW = check_constraints(constraints, B, V, bos, eos, beam_size)
+        ctl = self._checked_controls(controls, eos, max_len, constraints)
         w, S = int(beam_size), 1 << C
-        flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, cons=(C, Wc, min(V, w + NW), table))
+        flat = self._beam_run(features, c_v, eps, bos, eos, w, max_len, len_norm_f, check_every, cons=(C, Wc, min(V, w + NW), table), ctl=ctl)
         banks = [flat[b * S:(b + 1) * S] for b in range(B)]
         if all_states:
             return banks
         full = [sum(1 << j for j in range(C) if (table[b, j] >= 0).any()) for b in range(B)]
         return [select_bank(banks[b], full[b], int(eos)) for b in range(B)]
 
-    def _beam_run(self, features, c_v, eps, bos, eos, n, max_len, len_norm_f, check_every, groups=None, cons=None):
+    def _checked_controls(self, controls, eos, max_len, constraints=None):
+        """`controls` of a beam search as an active, checked DecodeControls, or None (ValueError before any launch)"""
+        ctl = active_controls(controls)
+        if ctl is not None:
+            ctl.check(self.e.V, eos, max_len or self.p.gen_max_len, constraints)
+        return ctl
+
+    def _beam_run(self, features, c_v, eps, bos, eos, n, max_len, len_norm_f, check_every, groups=None, cons=None, ctl=None):
         """beam_search's loop over B * G "virtual images" of beam n (G = 1: beam_search itself; groups = (G, diversity): group beam
         search, virtual image b*G + g = group g of image b; cons = (C, Wc, kc, table [B, C, Wc]): constrained beam search, G = 2^C and
         virtual image b*G + s = the bank of state s of image b).  Returns the virtual images' beams in order."""
@@ -1453,7 +1564,7 @@ class CaptionGenerator(object):
             nparts, nb = 1, B    # (a K-split logits product writes the engine's ONE workspace: slices on two streams would share it)
         part_cons = lambda k: None if cons is None else cons[:3] + (cons[3][k * nb // G:(k + 1) * nb // G],)   # (slices cut between images)
         parts = [self._beam_part(k, nparts, c[k * nb:(k + 1) * nb], h[k * nb:(k + 1) * nb], n, L, rounds, K, bos, eos, len_norm_f, xproj, fused, groups,
-                                 part_cons(k)) for k in range(nparts)]
+                                 part_cons(k), ctl) for k in range(nparts)]
         main = torch.cuda.current_stream()
         while len(self._side) < nparts - 1:
             self._side.append(torch.cuda.Stream())

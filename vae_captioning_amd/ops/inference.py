@@ -29,7 +29,10 @@ captions).
 image in the diverse modes, a list of one otherwise) is evaluated against ALL human captions of each image (taken from the generator's
 caption table by image id, `validation_references`: the batches carry one random caption per image) (`decoder.caption_evaluator`,
 evaluate.py: BLEU, CIDEr-D, oracle and diversity metrics) once after the loop -> `./val_{gen_name}_metrics.json`, one printed line
-per metric.  The caption files are written exactly as without the flag."""
+per metric.  The caption files are written exactly as without the flag.
+`params.no_repeat_ngram` / `min_len` / `repetition_penalty` / `banned_words` (additive): the decoding controls
+(`controls.DecodeControls`, attached to the decoder as `decoder.controls`) go to whichever mode decodes, the test set's
+`online_inference` included; the caption records gain nothing, `./val_{gen_name}_metrics.json` lists the four flags."""
 import json
 import math
 import os
@@ -121,7 +124,8 @@ def store_bounds(params, bound_records, stats):
 
 
 EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
-              "beam_diversity", "top_k", "top_p", "marginal_draws", "constraints", "cbs_width")
+              "beam_diversity", "top_k", "top_p", "marginal_draws", "constraints", "cbs_width",
+              "no_repeat_ngram", "min_len", "repetition_penalty", "banned_words")
 
 
 def store_metrics(params, metrics, images, captions):
@@ -194,6 +198,9 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
     _restore(saver, sess, "./checkpoints/{}.ckpt".format(params.checkpoint))
     if not params.fine_tune:
         print("Captioning from precomputed fc2 features; pass --fine_tune to run the fine-tuned VGG16 on the images.")
+    if getattr(decoder, "controls", None) is None:   # (main.py attaches them; a caller with its own decoder gets them from the flags)
+        from ..controls import from_params
+        decoder.controls = from_params(params, getattr(decoder, "data_dict", None))
     val_cv = params.use_c_v or params.prior in ("GMM", "AG")
     records, scores = [], []
     n_score = int(getattr(params, "score_draws", 0) or 0)

@@ -28,6 +28,7 @@ _DEFAULTS = dict(
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
     bound_draws=0, marginal_draws=20, constraints=None, cbs_width=0,
+    no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -54,6 +55,8 @@ _FLAGS = [
     ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
     ("--bound_draws", "bound_draws", int, None), ("--marginal_draws", "marginal_draws", int, None),
     ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
+    ("--no_repeat_ngram", "no_repeat_ngram", int, None), ("--min_len", "min_len", int, None),
+    ("--repetition_penalty", "repetition_penalty", float, None), ("--banned_words", "banned_words", str, None),
 ]
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
@@ -88,6 +91,12 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                           "are vocabulary strings or integer token ids)",
          "--cbs_width": "--sample_gen constrained_beam: beams per state of satisfied constraints (default 0 = the largest that fits, "
                         "16 >> the number of constraints)",
+         "--no_repeat_ngram": "decoding controls: no n-gram of this length appears twice in a caption (0..8; default 0 = off)",
+         "--min_len": "decoding controls: no <EOS> before this many words (>= 0, below gen_max_len; default 0 = off)",
+         "--repetition_penalty": "decoding controls: the logit of every word already in the caption is divided (positive) or multiplied "
+                                 "(negative) by this (1..10; default 1.0 = off)",
+         "--banned_words": "decoding controls: JSON file with a list of words (vocabulary strings or integer token ids, at most 256) that "
+                           "no caption may hold; not with --sample_gen marginal_greedy / marginal_beam, like the three flags above",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints"}
@@ -154,6 +163,15 @@ class Parameters(object):
                 ap.error("--cbs_width must be 0..16 (0 = the largest that fits; got %d)" % self.cbs_width)
         elif self.constraints is not None or args["cbs_width"] is not None:
             ap.error("--constraints / --cbs_width belong to --sample_gen constrained_beam (got --sample_gen %s)" % self.sample_gen)
+        if not 0 <= self.no_repeat_ngram <= 8:
+            ap.error("--no_repeat_ngram must be 0..8 (0 = off; got %d)" % self.no_repeat_ngram)
+        if not 0 <= self.min_len < self.gen_max_len:
+            ap.error("--min_len must be >= 0 and below gen_max_len = %d (0 = off; got %d)" % (self.gen_max_len, self.min_len))
+        if not (1.0 <= self.repetition_penalty <= 10.0):
+            ap.error("--repetition_penalty must be in [1, 10] (1 = off; got %r)" % self.repetition_penalty)
+        if self.sample_gen in ("marginal_greedy", "marginal_beam") and any(args[k] is not None for k in ("no_repeat_ngram", "min_len", "repetition_penalty", "banned_words")):
+            ap.error("--no_repeat_ngram / --min_len / --repetition_penalty / --banned_words do not go with --sample_gen %s (the mixture "
+                     "it searches is score()'s marginal, which they would change)" % self.sample_gen)
         if self.top_k < 0:
             ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
         if not (0.0 < self.top_p <= 1.0):

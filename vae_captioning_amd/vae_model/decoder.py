@@ -27,6 +27,8 @@ class Decoder(object):
                                      # every generation method clears it first, so a call that fails leaves None, never older ids
         self.bound_stats = None      # bound_captions: skipped images and the running sums behind the active-units count
         self.constraints = None      # constraints.Constraints: what --sample_gen constrained_beam makes the captions mention
+        self.controls = None         # controls.DecodeControls: what the captions may NOT say (--no_repeat_ngram, --min_len, --repetition_penalty,
+                                     # --banned_words); every generation method but marginal_inference passes it to its decoder
         self.train_captions = None   # flat token-id lists of the training captions: `novel` of caption_evaluator (None: not reported)
 
     def px_z_fi(self, observed, gen_mode=False):
@@ -75,9 +77,9 @@ class Decoder(object):
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
         if self.params.sample_gen == "sample":  # tf.multinomial(logits / temperature): same distribution, own Philox stream
             raw = self._gen().sample(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len,
-                                     top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0))
+                                     top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
         else:
-            raw = self._gen().greedy(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len)
+            raw = self._gen().greedy(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len, controls=self.controls)
         cap_list = []
         for pid, toks in zip(picture_ids, raw):
             words = [d.idx2word[t] for t in toks if t not in (bos, eos)]
@@ -93,7 +95,7 @@ class Decoder(object):
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
         res = self._gen().beam_search(self._features(in_pictures), use_cv, None, bos, eos, beam_size,
-                                      self.params.gen_max_len, len_norm_f)
+                                      self.params.gen_max_len, len_norm_f, controls=self.controls)
         cap_list = []
         for pid, beams in zip(picture_ids, res):
             texts = [" ".join(d.idx2word[t] for t in s if t not in (bos, eos)) for s, _ in beams]
@@ -126,7 +128,7 @@ class Decoder(object):
         feats = self._features(in_pictures)
         res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus else n_best,
                                   max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood",
-                                  top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0))
+                                  top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
         if consensus:
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
         cap_list = []
@@ -160,7 +162,8 @@ class Decoder(object):
         if G < 1 or total < G or total % G or total > 16:
             raise ValueError("diverse_beam_search: beam_size must be a multiple of groups and at most 16 (got %d and %d)" % (total, G))
         res = self._gen().diverse_beam_search(self._features(in_pictures), use_cv, None, bos, eos, groups=G, group_size=total // G,
-                                              diversity=lam, max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+                                              diversity=lam, max_len=self.params.gen_max_len, len_norm_f=len_norm_f,
+                                              controls=self.controls)
         cap_list, token_ids = [], []
         for pid, per_group in zip(picture_ids, res):
             entries = merge_groups(per_group)
@@ -191,7 +194,7 @@ class Decoder(object):
         if beam_size is None:
             beam_size = self.constraints.width if self.constraints is not None else 16 >> max([len(c) for c in constraints] + [0])
         res = self._gen().constrained_beam_search(self._features(in_pictures), constraints, use_cv, None, bos, eos, beam_size=int(beam_size),
-                                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f)
+                                                  max_len=self.params.gen_max_len, len_norm_f=len_norm_f, controls=self.controls)
         cap_list, token_ids = [], []
         for pid, sets, (beams, state) in zip(picture_ids, constraints, res):
             toks, score = (list(beams[0][0]), float(beams[0][1])) if beams else ([], float("-inf"))
@@ -209,6 +212,9 @@ class Decoder(object):
         "marginal_beam" runs a beam search of beam_size (params.beam_size) hypotheses over it.  Returns cap_list: per image
         {"image_id", "caption", "marginal": log 1/K sum_k p(caption | z_k, image) as the decoder accumulated it, "draws": K}."""
         self.last_token_ids = None
+        if self.controls is not None and not self.controls.is_noop():
+            raise ValueError("marginal_inference takes no decoding controls: renormalising every draw's distribution would break the "
+                             "mode's identity with score()'s marginal")
         d = self.data_dict
         bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
         use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
