@@ -4,7 +4,7 @@
 
     python gen_caption.py --img_path cat.jpg --checkpoint ./checkpoints/last_run.ckpt \\
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
-        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam|constrained_beam] [--must_include "dog,puppy;frisbee"] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
+        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam|constrained_beam|stochastic_beam] [--must_include "dog,puppy;frisbee"] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
         [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
@@ -127,7 +127,9 @@ class Generator(object):
         gen_method "constrained_beam" (additive): beam search whose caption mentions the words of `must_include` ("dog,puppy;frisbee":
         ';' separates sets, ',' the words of a set, any of which satisfies it); the record also holds "constraints", "satisfied", "score".
         controls (additive): a vae_captioning_amd.controls.DecodeControls -- no repeated n-gram, minimum length, repetition penalty,
-        banned words -- for every gen_method but the marginal ones."""
+        banned words -- for every gen_method but the marginal ones.  gen_method "stochastic_beam" (additive): beam_size distinct captions
+        sampled without replacement (stochastic beam search); the record holds diverse's lists plus "logprob", "perturbed", "weight",
+        "norm_weight" and "kappa"."""
         if top_k is not None:
             self.params.top_k = int(top_k)
         if top_p is not None:
@@ -157,7 +159,9 @@ class Generator(object):
             decoder.constraints = parse_must_include(must_include or "", w2i, self.data_dict.vocab_size, w2i["<BOS>"], w2i["<EOS>"])
             print(decoder.constraints.summary())
             return decoder.constrained_beam_search(None, im_id, feature_vector, None, c_v)
-        raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam or constrained_beam")
+        if self.gen_method == "stochastic_beam":
+            return decoder.stochastic_beam_search(None, im_id, feature_vector, None, c_v, beam_size=int(beam_size))
+        raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam or stochastic_beam")
 
 
 if __name__ == "__main__":
@@ -167,9 +171,9 @@ if __name__ == "__main__":
     parser.add_argument("--vocab_path", default="./pickles/capt_vocab.pickle", help="Indices to words dictionary")
     parser.add_argument("--gpu", default="", help="Specify GPU number if use GPU")
     parser.add_argument("--c_v_generator", default=None, help="If use cluster vectors, specify tensorflow api model (unused, as in the reference)")
-    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam or constrained_beam")
+    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam or stochastic_beam")
     parser.add_argument("--params_path", default=None, help="specify params pickle file")
-    parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size")
+    parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size; --gen_method stochastic_beam: distinct captions to sample (1..32)")
     parser.add_argument("--vgg_weights", default=None, help="vgg16_weights.npz for the feature extractor (additive flag)")
     parser.add_argument("--diverse_draws", type=int, default=None, help="--gen_method diverse: latent draws (default: the params' diverse_draws)")
     parser.add_argument("--top_k", type=int, default=None, help="sampled decoding: draw from the k most likely words (0 = all; default: the params')")
@@ -203,6 +207,8 @@ if __name__ == "__main__":
         parser.error("--top_k must be >= 0 (got %d)" % args.top_k)
     if args.top_p is not None and not (0.0 < args.top_p <= 1.0):
         parser.error("--top_p must be in (0, 1] (got %r)" % args.top_p)
+    if args.gen_method == "stochastic_beam" and not 1 <= int(args.beam_size) <= 32:
+        parser.error("--beam_size must be 1..32 with --gen_method stochastic_beam (got %s)" % args.beam_size)
     if args.gpu != "":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
@@ -217,5 +223,8 @@ if __name__ == "__main__":
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))
+    elif args.gen_method == "stochastic_beam":   # distinct captions sampled without replacement: probability, normalised weight, text
+        for text, lp, w in zip(caption[0]["captions"], caption[0]["logprob"], caption[0]["norm_weight"]):
+            print("logp %.4f w %.4f %s" % (lp, w, text))
     else:
         print(caption[0]["caption"])

@@ -45,6 +45,7 @@ extern "C" {
  *      vc_mixture_advance_f32.
  *      Added within 4 (additive, no layout change): the constrained beam search entry vc_beam_update_constrained.
  *      Added within 4 (additive, no layout change): the decoding-controls entry vc_decode_controls_f32.
+ *      Added within 4 (additive, no layout change): the stochastic beam search entries vc_sbs_init / vc_sbs_expand_f32 / vc_sbs_update.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -571,6 +572,49 @@ int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32
 int vc_decode_controls_f32(void* stream, float* logits, long rows, int V, long ld, const int32_t* hist, long hist_ld, int Lmax, int skip,
                            const int32_t* len, const int32_t* done, int ngram, int min_len, int eos, float penalty, const int32_t* banned,
                            int n_banned);
+
+/* ------------------------------------------------------------------------------------
+ * Stochastic beam search (csrc/sbs.hip; generate.py: CaptionGenerator.stochastic_beam_search; Kool, van Hoof, Welling, ICML 2019): per
+ * image n <= 32 DISTINCT captions, an exact sample without replacement from the model, by Gumbel top-k.  Beam rows are image-major: row
+ * r = b*n + i is entry i of image b.  The state of an image: count [B] entries in rank order (best perturbed score first), each with
+ * p_phi (float64 log-probability of its words), p_G (float64 perturbed score), p_len (words, <BOS> included), p_done (finished: its last
+ * word is eos or it holds Lmax words; finished entries stay IN the beam and compete), its words in sent_cur [B, n, Lmax]; kappa [B]
+ * (float64): the running maximum of the best perturbed score NOT taken, -inf while nothing was rejected.  Slots past count hold
+ * p_phi = p_G = 0, p_len = 1, p_done = 1 (no round expands them), parent = their own row, tok = bos.
+ *   sbs_init    count = 1, entry 0 = ([bos], 0, 0, not done), kappa = -inf, every sent_cur token = bos, sent_next = 0, parent[r] = r,
+ *               tok[r] = bos, round[0] = 0 (round may be NULL), and the images' LSTM state expanded to the beam rows as vc_beam_init
+ *               does: c_out[r] = c_in[r / n], h_out[r] = h_in[r / n] ([B, H] -> [B*n, H]).  VC_EINVAL: n outside 1..32, Lmax < 2, a NULL
+ *               pointer.
+ *   sbs_expand  one workgroup per row of logits [rows, V] (ld), rows = B*n; rows with r % n >= count[r / n] or done[r] != 0 are skipped
+ *               (nothing read, nothing written).  lsm(v) = (x_v - M) - log S, M = max x, S = sum exp(x - M): f32, vc_decode_pick_f32's
+ *               expressions and order (the same bits).  key(v) = (double)lsm(v) + g(v); the first kc words under (key descending, index
+ *               ascending) go to cand_key [rows, kc] (float64, the key), cand_lsm [rows, kc] (f32) and cand_idx [rows, kc], always in
+ *               [0, V) and distinct (a key that is no number ranks as -inf).  Noise: gumbel != NULL (float64 [g_rounds, rows, V]):
+ *               g = gumbel[(rd * rows + r) * V + v], rd = round[0] (NULL: 0) clamped to g_rounds - 1.  gumbel == NULL: element
+ *               i = r*V + v of the Philox stream (seed, offset) under the key step round[0] + step[0] (each NULL: 0), vc_philox_u32's
+ *               counter convention, gives the word w; u = (w + 0.5) * 2^-32, g = -log(-log(u)), both float64.  The row is read from
+ *               memory once (V <= 12288: staged in LDS; wider rows twice).  No atomics, every sum in a fixed order; a row's outputs
+ *               depend on its own logits and noise only.  VC_EINVAL: rows no multiple of n, n outside 1..32, kc outside 1..33 or
+ *               > V, ld < V, g_rounds < 1 with gumbel, a NULL pointer (gumbel, round, step may be NULL).
+ *   sbs_update  one wave per image.  Candidates: the kc children of every live unfinished entry i,
+ *               Gt = p_phi_i + key, Z = p_phi_i + key_0, t = G_i - Gt + log1mexp(Gt - Z), G' = G_i - max(0, t) - log1p(exp(-|t|))
+ *               (the arg-max child: G' = G_i exactly), and every finished entry itself (G', p_phi unchanged).  The new beam is the best
+ *               min(n, candidates) by (G' descending, parent ascending, word ascending), written IN PLACE in rank order: p_phi += the
+ *               f32 lsm of the word, p_G = G', p_len + 1, p_done = (word == eos) or p_len == Lmax, sent_next = the parent's words of
+ *               sent_cur plus the new one (sent_next != sent_cur), and for the next round parent [B*n] / tok [B*n] as vc_beam_gather_f32
+ *               takes them (a carried finished entry: its own row before the update and eos).  kappa = max(kappa, G' of the best
+ *               candidate not taken) when there is one; round[0] += 1 once per launch (round may be NULL).  kc is vc_sbs_expand_f32's
+ *               (kappa is exact only with kc = min(n + 1, V)).  VC_EINVAL: n outside 1..32, kc outside 1..33, Lmax < 2,
+ *               sent_cur == sent_next, a NULL pointer. */
+int vc_sbs_init(void* stream, int B, int n, int Lmax, int bos, int H, const float* c_in, const float* h_in, float* c_out, float* h_out,
+                int32_t* count, double* p_phi, double* p_G, int32_t* p_len, int32_t* p_done, int32_t* sent_cur, int32_t* sent_next,
+                double* kappa, int32_t* parent, int32_t* tok, int32_t* round);
+int vc_sbs_expand_f32(void* stream, const float* logits, long rows, int n, int V, long ld, const int32_t* count, const int32_t* done, int kc,
+                      const double* gumbel, int g_rounds, const int32_t* round, uint64_t seed, uint64_t offset, const int32_t* step,
+                      double* cand_key, float* cand_lsm, int32_t* cand_idx);
+int vc_sbs_update(void* stream, int B, int n, int kc, int Lmax, int bos, int eos, const double* cand_key, const float* cand_lsm,
+                  const int32_t* cand_idx, int32_t* count, double* p_phi, double* p_G, int32_t* p_len, int32_t* p_done,
+                  const int32_t* sent_cur, int32_t* sent_next, double* kappa, int32_t* parent, int32_t* tok, int32_t* round);
 
 /* ------------------------------------------------------------------------------------
  * Consensus re-ranking of diverse captions (consensus.py: ConsensusIndex; Devlin et al. 2015).  An index of D images (fc2 feature row,

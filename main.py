@@ -250,7 +250,7 @@ def main(params):
     if params.mode == "inference":
         # ops/inference.py:4-39: captions for the validation images -> ./val_{gen_name}.json
         decoder = Decoder(None, None, None, params, cap_dict)
-        if params.sample_gen == "diverse" and params.diverse_rerank == "consensus":
+        if params.sample_gen in ("diverse", "stochastic_beam") and params.diverse_rerank == "consensus":
             decoder.consensus_index = consensus_index(params, tr, cap_dict, coco_train)
         if params.sample_gen == "constrained_beam":   # the words the captions must mention, looked up in the vocabulary once
             from vae_captioning_amd.constraints import load_constraints
@@ -285,6 +285,10 @@ def main(params):
                 sent = decoder.diverse_beam_search(None, ids, pics, None, c_v)
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (groups %s)" % (t, ",".join(map(str, g))) for t, g in zip(r["captions"], r["groups"]))))
+            elif params.sample_gen == "stochastic_beam":   # --beam_size distinct captions sampled without replacement, with their weights
+                sent = decoder.stochastic_beam_search(None, ids, pics, None, c_v)
+                for r in sent:
+                    say("%s: %s" % (r["image_id"], " | ".join("%s (logp %.3f, w %.3g)" % (t, lp, w) for t, lp, w in zip(r["captions"], r["logprob"], r["norm_weight"]))))
             elif params.sample_gen in ("marginal_greedy", "marginal_beam"):   # search under the mixture of --marginal_draws latent draws
                 sent = decoder.marginal_inference(None, ids, pics, None, c_v)
             elif params.sample_gen == "constrained_beam":   # beam search whose captions mention the words of --constraints
@@ -308,7 +312,7 @@ def main(params):
         if rank == 0:
             with open("./val_{}.json".format(params.gen_name), "w") as wj:
                 json.dump(captions_gen, wj)
-            if params.sample_gen in ("diverse", "diverse_beam"):   # the full per-image lists under the name ops/inference.py gives them
+            if params.sample_gen in ("diverse", "diverse_beam", "stochastic_beam"):   # the full per-image lists under the name ops/inference.py gives them
                 with open("./val_{}_diverse.json".format(params.gen_name), "w") as wj:
                     json.dump(captions_gen, wj)
             if params.score_draws:

@@ -139,6 +139,17 @@ def rerank_by_marginal(entries, marginals, eos, len_norm_f):
     return sorted(new, key=lambda x: (not (len(x[0]) > 0 and x[0][-1] == eos), -x[1]))
 
 
+def sbs_weights(logprobs, kappa):
+    """Importance weights of a stochastic beam search's captions (Kool et al. 2019, section 4.2), float64: with phi their
+    log-probabilities and kappa the (n+1)-th largest perturbed score, q_i = P(perturbed_i > kappa) = -expm1(-exp(phi_i - kappa)) (kappa =
+    -inf: 1), w_i = exp(phi_i) / q_i, norm_i = w_i / sum_j w_j.  Returns (w, norm)."""
+    phi = np.asarray(logprobs, np.float64)
+    with np.errstate(over="ignore"):
+        q = -np.expm1(-np.exp(phi - float(kappa)))
+    w = np.exp(phi) / q
+    return w, w / w.sum()
+
+
 def merge_groups(groups):
     """diverse_beam_search's per-image result (a list of G lists of (tokens, score)) as ONE ranked list of distinct captions:
     [(tokens, score, [groups that produced it]), ...], equal token sequences merged under their best score, score descending (ties
@@ -1624,4 +1635,106 @@ class CaptionGenerator(object):
             for pt in parts:
                 if pt.graph is None:
                     self._capture(pt.key_fn(), pt.chunk_fn)   # (the results are on the host: the capture touches no state)
+        return res
+
+    # ------------------------------------------------------------------ stochastic beam search (Gumbel top-k)
+    def stochastic_beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, beam_size=10, max_len=None, len_norm_f=0.7, gumbel=None,
+                               seed=None, check_every=4, controls=None):
+        """Stochastic beam search (Kool, van Hoof, Welling, ICML 2019) for a batch of images: per image `beam_size` = n DISTINCT captions,
+        an exact sample WITHOUT replacement from the model p(y | z, image), for the cost of one beam search of width n (DESIGN.md
+        "Stochastic beam search").  Every entry carries phi (the log-probability of its words; f32 log-softmax terms, f64 sum) and G
+        (its Gumbel-perturbed score); a round perturbs the log-softmax of every live entry's row, conditions the children on their
+        parent's G and keeps the best n by G; finished captions stay in the beam and compete.  The search starts from the image's
+        state like diverse() (<BOS> fed once) and runs until every entry has ended or holds max_len words.
+        Returns per image {"kappa": the (n+1)-th largest perturbed score (-inf: nothing was ever rejected), "captions": [(words without
+        <BOS>, logprob, perturbed, ended, weight, norm_weight), ...]} in rank order of `perturbed`; the weights are sbs_weights'
+        (w = p / q, q = P(perturbed > kappa)): sum_i w_i f(y_i) is an unbiased estimate of E f(y), sum_i norm_weight_i f(y_i) its
+        normalised form.  len_norm_f is not used by the search (the command line ranks its files with it).
+        The round is vc_beam_gather_f32 -> step -> (controls) -> vc_sbs_expand_f32 -> vc_sbs_update, replayed as hipGraph chunks of
+        check_every rounds with a 4-byte "all ended" read between chunks (VC_DECODE_GRAPH=0: the eager loop, same result); the round
+        counter is a device int, so replays draw fresh noise.
+        gumbel: [max_len, B * n, V] float64 noise to inject (row b*n + i of round t perturbs entry i of image b); None: Philox stream
+        9 << 32 under seed (None: engine seed * 1000003 + 29, and every call of this generator draws another stream; a given seed
+        repeats its result).  controls: a controls.DecodeControls; every round's logits are processed from each entry's words so far and
+        phi is taken under the processed distribution, as in the other decoders.  There is no temperature in this mode: the weights
+        need phi under the distribution that was sampled."""
+        lib, e, p = self.lib, self.e, self.p
+        n = int(beam_size)
+        if n < 1 or n > 32:
+            raise ValueError("stochastic_beam_search: beam_size must be 1..32, got %r" % (beam_size,))
+        if float(p.temperature) != 1.0:
+            raise ValueError("stochastic_beam_search samples the model itself: --temperature must be 1 (got %r)" % (p.temperature,))
+        max_len = int(max_len or p.gen_max_len)
+        ctl = self._checked_controls(controls, eos, max_len)
+        c0, h0 = self.init_state(features, c_v, eps)
+        B, Hd, V = int(c0.shape[0]), p.decoder_hidden, e.V
+        M, L, kc = B * n, max_len + 1, min(n + 1, V)
+        i32, f64 = torch.int32, torch.float64
+        tag = "sbs%d_%d_%d_" % (B, n, L)
+        lay = FieldLayout([("count", B), ("len", M), ("done", M), ("sent0", M * L), ("sent1", M * L)])
+        dlay = FieldLayout([("phi", M), ("G", M), ("kappa", B)])
+        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), f64)
+        iv, (phi, G, kappa) = lay.views(ibuf), dlay.views(dbuf).values()
+        count, p_len, p_done, sent = iv["count"], iv["len"], iv["done"], [iv["sent0"].view(M, L), iv["sent1"].view(M, L)]
+        parent, tok = self._b(tag + "parent", (M,), i32), self._b(tag + "tok", (M,), i32)
+        ck, cl, ci = self._b(tag + "ck", (M, kc), f64), self._b(tag + "cl", (M, kc)), self._b(tag + "ci", (M, kc), i32)
+        rnd, base, pending = self._b(tag + "round", (1,), i32), self._b(tag + "base", (1,), i32), self._b(tag + "pending", (1,))
+        bufs = self._round_bufs(tag, M)
+        cg, hg = self._b(tag + "cg", (M, Hd)), self._b(tag + "hg", (M, Hd))
+        gd = None
+        if gumbel is not None:
+            if tuple(np.shape(gumbel)) != (max_len, M, V):
+                raise ValueError("gumbel must be [max_len, images * beam_size, V] = %s" % ((max_len, M, V),))
+            gd = self._b(tag + "gumbel", (max_len, M, V), f64)
+            gd.copy_(torch.from_numpy(np.ascontiguousarray(gumbel, dtype=np.float64)), non_blocking=True)
+        if seed is None:   # another stream per call: the key's step is the round counter plus this base
+            self._sbs_calls = getattr(self, "_sbs_calls", 0) + 1
+            seed_, base_ = e.seed * 1000003 + 29, (self._sbs_calls << 12) & 0x7fffffff
+        else:
+            seed_, base_ = int(seed), 0
+        seed_ &= (1 << 64) - 1
+        xproj = self._project_vocab() if (M * max_len >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
+        self._pack_wh(M)
+        ban_t = self._controls_table(tag, ctl) if ctl is not None else None
+        trace = getattr(self, "sbs_trace", None)   # (tests: a list here receives every eager round's logits as a host array)
+
+        def reset():
+            lib.vc_sbs_init(_stream(), B, n, L, int(bos), Hd, P(c0), P(h0), P(bufs["c2"]), P(bufs["h2"]), P(count), P(phi), P(G), P(p_len),
+                            P(p_done), P(sent[0]), P(sent[1]), P(kappa), P(parent), P(tok), P(rnd))
+            base.fill_(base_)
+            if trace is not None:
+                del trace[:]
+
+        def one(r, timed):
+            s_ = _stream()
+            lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent), M, Hd, P(cg), P(hg), P(xproj), P(tok), V, 4 * Hd, P(bufs["gact"]))
+            logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
+            if ctl is not None:
+                self._apply_controls(ctl, ban_t, logits, M, sent[r & 1], L, 1, p_len, p_done, eos)
+            if trace is not None and timed:
+                trace.append(logits.cpu().numpy().copy())
+            lib.vc_sbs_expand_f32(s_, P(logits), M, n, V, V, P(count), P(p_done), kc, P(gd), max_len, P(rnd), seed_, 9 << 32, P(base),
+                                  P(ck), P(cl), P(ci))
+            lib.vc_sbs_update(s_, B, n, kc, L, int(bos), int(eos), P(ck), P(cl), P(ci), P(count), P(phi), P(G), P(p_len), P(p_done),
+                              P(sent[r & 1]), P(sent[1 - (r & 1)]), P(kappa), P(parent), P(tok), P(rnd))
+            lib.vc_decode_round_end_i32(s_, P(p_done), M, P(pending), None)
+
+        K = self._chunk_rounds(check_every)
+        steps = self._run_chunks(("sbs", B, n, L, K, kc, int(bos), int(eos), gd is None, seed_) + (ctl.key() if ctl is not None else ()),
+                                 [ibuf, dbuf, parent, tok, ck, cl, ci, rnd, base, pending, cg, hg, xproj, gd, c0, h0, self._ones_for(M)]
+                                 + ([ban_t] if ctl is not None else []) + list(bufs.values()), one, reset, K, max_len, check_every, pending)
+        ints, dbls = self._to_host(tag, ibuf, dbuf)
+        cnt, ln = ints[lay.off["count"]:lay.off["count"] + B].tolist(), ints[lay.off["len"]:lay.off["len"] + M].tolist()
+        o = lay.off["sent%d" % (steps & 1)]
+        words = ints[o:o + M * L].tolist()
+        ph, Gs, kap = dbls[:M].tolist(), dbls[M:2 * M].tolist(), dbls[2 * M:2 * M + B].tolist()
+        res = []
+        for b in range(B):
+            rows = range(b * n, b * n + cnt[b])
+            w, nw = sbs_weights([ph[r] for r in rows], kap[b])
+            caps = []
+            for j, r in enumerate(rows):
+                s = words[r * L + 1:r * L + ln[r]]
+                caps.append((s, ph[r], Gs[r], bool(s) and s[-1] == eos, float(w[j]), float(nw[j])))
+            res.append({"kappa": kap[b], "captions": caps})
         return res

@@ -11,6 +11,9 @@ always decoded with `online_inference`, as in the reference.  `sample_gen == "di
 the consensus scores; with `"marginal"` they hold each caption's likelihood over all of the image's draws.
 `sample_gen == "diverse_beam"` (additive): group beam search (`decoder.diverse_beam_search`), written the same way: the merged ranked
 captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one in `./val_{gen_name}.json`.
+`sample_gen == "stochastic_beam"` (additive): stochastic beam search (`decoder.stochastic_beam_search`), written the same way: the
+`params.beam_size` distinct captions sampled without replacement for an image, ranked, in `./val_{gen_name}_diverse.json` (each with
+its `logprob`, `perturbed` score, `weight` and `norm_weight`, the image with its `kappa`), the first in `./val_{gen_name}.json`.
 `sample_gen == "marginal_greedy"` / `"marginal_beam"` (additive): greedy decoding / beam search under the mixture of
 `params.marginal_draws` latent draws (`decoder.marginal_inference`); the records of `./val_{gen_name}.json` gain `"marginal"` (the
 caption's log-likelihood over the draws) and `"draws"`.
@@ -53,6 +56,8 @@ def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
         return decoder.diverse_inference(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "diverse_beam":
         return decoder.diverse_beam_search(sess, ids, images, placeholder, c_v)
+    if allow_beam and params.sample_gen == "stochastic_beam":
+        return decoder.stochastic_beam_search(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen in ("marginal_greedy", "marginal_beam"):
         return decoder.marginal_inference(sess, ids, images, placeholder, c_v)
     if allow_beam and params.sample_gen == "constrained_beam":
@@ -223,7 +228,7 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
         store_scores(params, scores)
     if n_bound:
         store_bounds(params, bounds, getattr(decoder, "bound_stats", None))
-    if params.sample_gen in ("diverse", "diverse_beam"):
+    if params.sample_gen in ("diverse", "diverse_beam", "stochastic_beam"):
         _store("./val_{}_diverse.json".format(params.gen_name), records)
         records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]
     _store("./val_{}.json".format(params.gen_name), records)

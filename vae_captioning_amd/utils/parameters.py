@@ -72,7 +72,8 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--consensus_m": "--diverse_rerank consensus: best-matching pool captions averaged per candidate (>= 1; default 125)",
          "--score_draws": "--mode inference: also score the validation images' human captions under this many prior draws and write "
                           "./val_{gen_name}_scores.json (0..256; default 0 = off)",
-         "--beam_size": "beams per image (default 10); --sample_gen diverse_beam: the total over the groups, a multiple of --beam_groups, <= 16",
+         "--beam_size": "beams per image (default 10); --sample_gen diverse_beam: the total over the groups, a multiple of --beam_groups, <= 16; "
+                        "--sample_gen stochastic_beam: distinct captions sampled per image, 1..32",
          "--beam_groups": "--sample_gen diverse_beam: groups per image, each a beam search of beam_size / beam_groups beams (default 5)",
          "--beam_diversity": "--sample_gen diverse_beam: what a word costs a candidate per live beam of the round's earlier groups that "
                              "has just taken it (>= 0; default 0.5)",
@@ -99,7 +100,8 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                            "no caption may hold; not with --sample_gen marginal_greedy / marginal_beam, like the three flags above",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
-                         "constrained_beam: beam search whose captions mention the words of --constraints"}
+                         "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
+                         "distinct captions sampled without replacement, each with its probability and importance weight"}
 
 
 class Parameters(object):
@@ -156,6 +158,12 @@ class Parameters(object):
             ap.error("--marginal_draws must be 1..256 (got %d)" % self.marginal_draws)
         if self.sample_gen == "marginal_beam" and not 1 <= self.beam_size <= 16:
             ap.error("--beam_size must be 1..16 with --sample_gen marginal_beam (got %d)" % self.beam_size)
+        if self.sample_gen == "stochastic_beam":
+            if not 1 <= self.beam_size <= 32:
+                ap.error("--beam_size must be 1..32 with --sample_gen stochastic_beam (got %d)" % self.beam_size)
+            if self.temperature != 1.0:
+                ap.error("--temperature must be 1 with --sample_gen stochastic_beam: its weights need the captions' probabilities under "
+                         "the distribution that was sampled (got %r)" % self.temperature)
         if self.sample_gen == "constrained_beam":
             if not self.constraints:
                 ap.error("--sample_gen constrained_beam needs --constraints FILE")

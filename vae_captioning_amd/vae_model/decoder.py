@@ -175,6 +175,53 @@ class Decoder(object):
         self.last_token_ids = token_ids
         return cap_list
 
+    def stochastic_beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, beam_size=None, len_norm_f=0.7):
+        """Stochastic beam search (Kool et al. 2019; generate.py: stochastic_beam_search): beam_size (params.beam_size, 1..32) distinct
+        captions per image, sampled without replacement from the model, each with its exact log-probability and importance weight.
+        Returns cap_list in diverse_inference's record shape, ranked as vc_diverse_rank ranks (<EOS>-ended first, then logprob /
+        (1 + len)^len_norm_f descending): per image {"image_id", "caption", "captions", "scores", "counts" (all 1: the captions are
+        distinct), "logprob", "perturbed", "weight", "norm_weight" (aligned with "captions"), "kappa"}.  params.diverse_rerank ==
+        "consensus" re-ranks by the attached consensus index and adds "consensus"; "marginal" adds "marginal" (one latent draw per
+        image: the caption's logprob, so the order is the likelihood order)."""
+        from ..generate import rerank_by_marginal
+        self.last_token_ids = None
+        d = self.data_dict
+        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        n = int(beam_size if beam_size is not None else self.params.beam_size)
+        consensus = getattr(self.params, "diverse_rerank", "likelihood") == "consensus"
+        marginal = getattr(self.params, "diverse_rerank", "likelihood") == "marginal"
+        if consensus and self.consensus_index is None:
+            raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
+                               "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
+        feats = self._features(in_pictures)
+        res = self._gen().stochastic_beam_search(feats, use_cv, None, bos, eos, beam_size=n, max_len=self.params.gen_max_len,
+                                                 len_norm_f=len_norm_f, controls=self.controls)
+        ranked = []
+        for r in res:
+            caps = sorted(r["captions"], key=lambda c: (not c[3], -(c[1] / (1 + len(c[0])) ** len_norm_f)))
+            ranked.append([(list(c[0]), c[1] / (1 + len(c[0])) ** len_norm_f, 1) for c in caps])
+        if consensus:
+            ranked = self.consensus_index.rerank(feats, ranked)
+        if marginal:
+            ranked = [rerank_by_marginal(entries, [by[tuple(e[0])][1] for e in entries], eos, len_norm_f)
+                      for entries, by in zip(ranked, [{tuple(c[0]): c for c in r["captions"]} for r in res])]
+        cap_list = []
+        for pid, entries, r in zip(picture_ids, ranked, res):
+            by = {tuple(c[0]): c for c in r["captions"]}
+            own = [by[tuple(e[0])] for e in entries]
+            texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
+            rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts, "scores": [float(e[1]) for e in entries],
+                   "counts": [1] * len(entries), "logprob": [float(c[1]) for c in own], "perturbed": [float(c[2]) for c in own],
+                   "weight": [float(c[4]) for c in own], "norm_weight": [float(c[5]) for c in own], "kappa": float(r["kappa"])}
+            if consensus:
+                rec["consensus"] = [float(e[3]) for e in entries]
+            if marginal:
+                rec["marginal"] = [float(e[3]) for e in entries]
+            cap_list.append(rec)
+        self.last_token_ids = [[list(e[0]) for e in entries] for entries in ranked]
+        return cap_list
+
     def constrained_beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, constraints=None, beam_size=None,
                                 len_norm_f=0.7):
         """Constrained beam search (Anderson et al. 2017; generate.py: constrained_beam_search): captions that must mention given words.
