@@ -231,6 +231,31 @@ int vc_loss_finalize_f32(void* stream, const float* ce_num, const float* ce_den,
                          const float* kl_sum, float inv_n, const float* ann, float* out4);
 
 /* ------------------------------------------------------------------------------------
+ * Training objective options (additive in ABI 4; DESIGN.md "Training objective options").  Each entry stands BESIDE its plain
+ * form above and is called only when its option is on -- the plain entries and their kernels are unchanged.
+ *   vc_softmax_xent_smooth_f32: label smoothing, target (1 - eps) * onehot + eps / V over the V real columns, eps in [0, 1):
+ *     row_loss = mask * (lse - (1 - eps) * x[label] - (eps / V) * sum_{v<V} x[v]);  write_grad: logits[v] <- mask * (gscale / den) *
+ *     (softmax[v] - (1 - eps) * [v == label] - eps / V) for v < V and exactly 0 for the pitch padding V <= v < ld (all of it).
+ *     Same two kernels and dispatch rule as vc_softmax_xent_f32.
+ *   vc_kl_rows_fb_f32: free bits, row_kl[n] = sum_l max(free_bits, kl[n,l]) with kl[n,l] the per-dimension summand of
+ *     vc_kl_rows_f32 (its -0.5 included); row_kl_raw[n] = sum_l kl[n,l]; row_floored[n] = #{l: kl[n,l] <= free_bits}.
+ *   vc_latent_bwd_fb_f32: vc_latent_bwd_f32 whose KL gradient is exactly 0 for the dimensions with kl[n,l] <= free_bits (the
+ *     same f32 value and comparison as the forward entry's).
+ *   vc_objective_stats_f32: out2 = {mean_n row_kl_raw, sum_n row_floored / (N * L)}.
+ *   vc_loss_finalize_kl_f32: vc_loss_finalize_f32 with lower_bound = rec + ann * kl_coef * KL (kl_coef = beta / 10).
+ * ---------------------------------------------------------------------------------- */
+int vc_softmax_xent_smooth_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld, const float* den,
+                               float gscale, float eps, float* row_loss, int write_grad);
+int vc_kl_rows_fb_f32(void* stream, int N, int L, int mode, const float* mean, const float* std_, const float* mu_p,
+                      float free_bits, float* row_kl, float* row_kl_raw, int32_t* row_floored);
+int vc_latent_bwd_fb_f32(void* stream, int S, int N, int L, int mode, int out_logstd, const float* dz, const float* eps,
+                         const float* mean, const float* std_, const float* mu_p, const float* ann, float kl_scale,
+                         float free_bits, float* dmean, float* dstd);
+int vc_objective_stats_f32(void* stream, int N, int L, const float* row_kl_raw, const int32_t* row_floored, float* out2);
+int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const float* ce_den, const float* reg_sumsq, float reg_scale,
+                            const float* kl_sum, float inv_n, const float* ann, float kl_coef, float* out4);
+
+/* ------------------------------------------------------------------------------------
  * Small data-movement ops.
  *   colsum       out[c] (+)= sum_r x[r,c]                (bias gradients)
  *   dropout      y = x*mask/keep                          (tf.nn.dropout, decoder.py:85-87, rnn_model.py:45-46)
@@ -263,6 +288,11 @@ int vc_sumsq_partial_f32(void* stream, const float* x, long n, float* partial);
 int vc_clip_finalize_f32(void* stream, const float* partial, int n_partial, float clip, float* out_norm_scale);
 int vc_step_update(void* stream, int32_t* step, float* scalars, float lr, float cnn_lr, float beta1, float beta2,
                    float ann_param, int ann_on, int decay_steps);
+/* vc_step_update with the cyclical KL schedule (additive in ABI 4) in scalars[1] instead of the tanh one:
+ * min(1, (step mod cycle_steps) / (cycle_ramp * cycle_steps)) while step < cycles * cycle_steps or cycles == 0, 1 afterwards
+ * (step = the counter before the increment); every other scalar and the counter as vc_step_update leaves them. */
+int vc_step_update_cyclical(void* stream, int32_t* step, float* scalars, float lr, float cnn_lr, float beta1, float beta2,
+                            int decay_steps, int cycle_steps, float cycle_ramp, int cycles);
 int vc_adam_f32(void* stream, float* p, const float* g, float* m, float* v, long n, const float* lr_t, const float* scale,
                 float beta1, float beta2, float eps, float l2);
 /* The same update that also leaves sum(p_new^2) per workgroup in sumsq_partial[0 .. vc_adam_blocks(n)) (summed by vc_reduce_sum_f32):

@@ -24,7 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-from vae_captioning_amd import session, spec, synth  # noqa: E402
+from vae_captioning_amd import objective, session, spec, synth  # noqa: E402
 from vae_captioning_amd.ops import optimizers  # noqa: E402
 from vae_captioning_amd.utils.parameters import Parameters  # noqa: E402
 from vae_captioning_amd.vae_model.decoder import Decoder  # noqa: E402
@@ -200,6 +200,15 @@ def main(params):
         if params.fine_tune:
             optimize_cnn, _ = optimizers.cnn_optimizer(None, params)
         gs = 0  # host mirror of global_step (it restarts at 0 on --restore, Q11): no device sync on non-print steps
+        # --word_drop: decoder input words replaced by <UNK> on the host, before the upload (the embedding-gradient index is built from
+        # the replaced ids; nothing on the device changes); training batches only
+        drop_rng = np.random.default_rng([params.seed, 7919, rank]) if params.word_drop > 0 else None
+        unk = objective.unk_id(cap_dict.word2idx, params.vocab_size)
+
+        def say_objective():   # --kl_free_bits: what the floor does, beside the losses
+            if cap.free_bits > 0:
+                o = tr.objective_stats()
+                say("Free bits: kl_raw: {} floored_share: {}".format(o["kl_raw"], o["floored_share"]))
         for e in range(params.num_epochs):
             if real is not None:
                 it = real.next_batch(use_obj_vectors=spec.uses_ci(params), num_captions=params.num_captions)
@@ -210,6 +219,8 @@ def main(params):
             for batch in it:
                 if batch["cap_dec"].shape[0] != params.batch_size * params.num_captions:
                     continue  # ragged last batch: shapes are static on device
+                if drop_rng is not None:
+                    batch = dict(batch, cap_dec=objective.word_dropout(batch["cap_dec"], batch["lengths"], params.word_drop, unk, drop_rng))
                 tr.set_batch(batch)
                 # ---- one sess.run([kld, rec_loss, lower_bound, optimize, optimize_cnn, annealing]) ----
                 feats = None
@@ -231,8 +242,11 @@ def main(params):
                     say("Epoch: {} Iteration: {} VLB: {} Rec Loss: {}".format(e, gs - 1, lb, rl))
                     if not params.no_encoder:
                         say("Annealing coefficient:{} KLD: {}".format(ann, kl))
+                        say_objective()
             kl, rl, lb, ann = tr.losses()
             say("Epoch: {} Iteration: {} VLB: {} Rec Loss: {}".format(e, int(global_step.item()), lb, rl))
+            if not params.no_encoder:
+                say_objective()
             # validate(): rec_loss of the training graph on held-out batches (main.py:262-284)
             val = []
             held_out = coco_batches(coco_val, params) if coco_val is not None else SyntheticBatches(params, 4, params.seed + 99991 + rank).next_batch()

@@ -400,6 +400,252 @@ __global__ void loss_finalize_kernel(const float* ce_num, const float* ce_den, c
     out[3] = a;
 }
 
+// =======================================================================================
+// Training objective options (DESIGN.md "Training objective options"): label smoothing, free bits, KL weight.  Every kernel
+// below is a NEW one beside the plain form above -- with an option off the engine launches the plain entry, unchanged.
+// =======================================================================================
+
+// max and sum of two per-thread values in ONE pass through LDS (block_max + block_sum of common.h with their barriers shared)
+__device__ __forceinline__ void block_max_sum(float& mx, float& sm, float* sh /* 8 floats */) {
+    mx = wave_max(mx);
+    sm = wave_sum(sm);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh[w] = mx; sh[4 + w] = sm; }
+    __syncthreads();
+    mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    sm = ((sh[4] + sh[5]) + sh[6]) + sh[7];   // fixed order -> deterministic
+}
+
+// Label-smoothed masked cross-entropy: target (1 - eps) * onehot + eps / V over the V real columns.
+//   row_loss = mask * (lse(x) - (1 - eps) * x[label] - (eps / V) * sum_{v < V} x[v])
+//   dlogits[v] = mask * (gscale / den) * (softmax[v] - (1 - eps) * [v == label] - eps / V)   (v < V)
+// The columns of the row-pitch padding (V <= v < ld) do not exist: they are kept out of sum x (the plain kernel's -inf marker
+// would poison it) and their gradient is written as exactly 0 (dense_bwd_w contracts over the padded pitch).
+// Same traffic as the plain kernel: each logit read once and written once; sum x rides in the max's block reduction.
+template <bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void xent_smooth_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                              int V, long ld, const float* __restrict__ den, float gscale,
+                                                              float eps, float* __restrict__ row_loss) {
+    __shared__ float sh[8];
+    const long row = blockIdx.x;
+    float4* p = reinterpret_cast<float4*>(logits + row * ld);
+    const int V4 = (V + 3) >> 2;
+    const int label = labels[row];
+    float4 x[XENT_MAXQ];
+    // Straight-line loads: a thread past the row's last quad re-reads that quad (a valid address; its lanes are masked below), so all
+    // twelve 16-byte loads are in flight at once -- with the load inside `if (i < V4)` and the padding handled by branches each
+    // load waited for the one before it and was split into a 12-byte and a 4-byte one (24 serialised round trips per thread).
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
+    float mx = -INFINITY, sx = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {
+        const int i = threadIdx.x + q * 256, c = i * 4;
+        // columns >= V (the pitch padding, and every lane of a thread past the row) do not exist: 0 in sum x, -inf for max and exp
+        const bool v0 = c < V, v1 = c + 1 < V, v2 = c + 2 < V, v3 = c + 3 < V;
+        sx += ((v0 ? x[q].x : 0.f) + (v1 ? x[q].y : 0.f)) + ((v2 ? x[q].z : 0.f) + (v3 ? x[q].w : 0.f));
+        x[q].x = v0 ? x[q].x : -INFINITY; x[q].y = v1 ? x[q].y : -INFINITY;
+        x[q].z = v2 ? x[q].z : -INFINITY; x[q].w = v3 ? x[q].w : -INFINITY;
+        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
+    }
+    block_max_sum(mx, sx, sh);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {   // (exp(-inf) = 0: the masked lanes add nothing)
+        x[q].x = __expf(x[q].x - mx); x[q].y = __expf(x[q].y - mx);
+        x[q].z = __expf(x[q].z - mx); x[q].w = __expf(x[q].w - mx);
+        s += (x[q].x + x[q].y) + (x[q].z + x[q].w);
+    }
+    s = block_sum<256>(s, sh);
+    const bool live = label != 0;
+    const float ev = eps / (float)V;
+    if (threadIdx.x == 0) {
+        float l = 0.f;
+        if (live && label > 0 && label < V) l = __logf(s) + mx - (1.f - eps) * logits[row * ld + label] - ev * sx;
+        row_loss[row] = l;
+    }
+    if (WRITE_GRAD) {
+        __syncthreads();  // thread 0 has read logits[label] before anyone overwrites it
+        const float k = live ? gscale / den[0] : 0.f;
+        const float inv = k / s, ke = k * ev, kl = k * (1.f - eps);
+        // A scale-and-store with a branch-free patch of the label's column.  lq: which of this thread's quads holds the label, -1 in
+        // every other thread.
+        const bool own = label > 0 && label < V && (int)threadIdx.x == ((label >> 2) & 255);
+        const int lq = own ? (label >> 10) : -1, lc = label & 3;
+        const float a0 = lc == 0 ? kl : 0.f, a1 = lc == 1 ? kl : 0.f, a2 = lc == 2 ? kl : 0.f, a3 = lc == 3 ? kl : 0.f;
+#pragma unroll
+        for (int q = 0; q < XENT_MAXQ; ++q) {
+            const int i = threadIdx.x + q * 256;
+            if (i < V4) {
+                const float m = q == lq ? 1.f : 0.f;
+                p[i] = make_float4((x[q].x * inv - ke) - m * a0, (x[q].y * inv - ke) - m * a1, (x[q].z * inv - ke) - m * a2, (x[q].w * inv - ke) - m * a3);
+            }
+        }
+        // the last quad's padding columns hold exp(-inf) * inv - ke = -ke: the thread that stored them makes them exactly 0
+        float* r = logits + row * ld;
+        if ((int)threadIdx.x == ((V4 - 1) & 255))
+            for (int c = V; c < V4 * 4; ++c) r[c] = 0.f;
+        const int L4 = (int)(ld >> 2);  // quads of the pitch past the last real column: zeros as well
+        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
+    }
+}
+
+// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
+template <bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void xent_smooth_mem_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                              int V, long ld, const float* __restrict__ den, float gscale,
+                                                              float eps, float* __restrict__ row_loss) {
+    __shared__ float sh[4];
+    const long row = blockIdx.x;
+    float* p = logits + row * ld;
+    const int label = labels[row];
+    float mx = -INFINITY, sx = 0.f;
+    for (int c = threadIdx.x; c < V; c += 256) {
+        const float v = p[c];
+        mx = fmaxf(mx, v);
+        sx += v;
+    }
+    mx = block_max<256>(mx, sh);
+    sx = block_sum<256>(sx, sh);
+    float s = 0.f;
+    for (int c = threadIdx.x; c < V; c += 256) s += __expf(p[c] - mx);
+    s = block_sum<256>(s, sh);
+    const bool live = label != 0;
+    const float ev = eps / (float)V;
+    if (threadIdx.x == 0) {
+        float l = 0.f;
+        if (live && label > 0 && label < V) l = __logf(s) + mx - (1.f - eps) * p[label] - ev * sx;
+        row_loss[row] = l;
+    }
+    if (WRITE_GRAD) {
+        __syncthreads();
+        const float k = live ? gscale / den[0] : 0.f;
+        const float inv = k / s, ke = k * ev, kl = k * (1.f - eps);
+        for (int c = threadIdx.x; c < V; c += 256) {
+            float d = __expf(p[c] - mx) * inv - ke;
+            if (c == label) d -= kl;
+            p[c] = d;
+        }
+        for (long c = V + threadIdx.x; c < ld; c += 256) p[c] = 0.f;
+    }
+}
+
+// Per-dimension KL kl[n,l]: the summand of kl_rows_kernel with its -0.5.  Free bits compare this f32 value with the floor in
+// the forward AND in the backward kernel, so both evaluate it through this one function with contraction off: the two kernels
+// then agree on every element whatever the code around the call looks like.
+__device__ __forceinline__ float kl_elem(int mode, float m, float sd, float mup) {
+#pragma clang fp contract(off)
+    if (mode == 0) return -0.5f * (1.f + logf(sd * sd + 1e-5f) - m * m - sd * sd);
+    const float d = m - mup;
+    return -0.5f * (0.5f + logf(sd + 1e-5f) - logf(VC_AG_SIGMA + 1e-5f) - (d * d + sd * sd) / (2.f * VC_AG_SIGMA * VC_AG_SIGMA + 1e-7f));
+}
+
+// Free bits (Kingma et al. 2016), per dimension and row: row_kl[n] = sum_l max(fb, kl[n,l]); beside it the unclamped sum and the
+// number of dimensions held at the floor (those with kl <= fb).  One wave per row, four rows per workgroup, like kl_rows_kernel.
+__global__ __launch_bounds__(256) void kl_rows_fb_kernel(const float* __restrict__ mean, const float* __restrict__ std_,
+                                                         const float* __restrict__ mu_p, int N, int L, int mode, float fb,
+                                                         float* __restrict__ row_kl, float* __restrict__ row_kl_raw,
+                                                         int32_t* __restrict__ row_floored) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const int lane = threadIdx.x & 63;
+    float s = 0.f, raw = 0.f;
+    int nf = 0;
+    for (int l = lane; l < L; l += 64) {
+        const long j = (long)row * L + l;
+        const float kl = kl_elem(mode, mean[j], std_[j], mode ? mu_p[j] : 0.f);
+        raw += kl;
+        if (kl > fb) {
+            s += kl;
+        } else {
+            s += fb;
+            ++nf;
+        }
+    }
+    s = wave_sum(s);
+    raw = wave_sum(raw);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nf += __shfl_xor(nf, o, 64);
+    if (lane == 0) {
+        row_kl[row] = s;
+        row_kl_raw[row] = raw;
+        row_floored[row] = nf;
+    }
+}
+
+// latent_bwd_kernel under free bits: a dimension held at the floor (kl <= fb, the forward kernel's comparison) gets no KL
+// gradient -- its dmean / dstd are the sums over the samples alone; every other element is latent_bwd_kernel's.
+__global__ __launch_bounds__(256) void latent_bwd_fb_kernel(const float* __restrict__ dz, const float* __restrict__ eps,
+                                                            const float* __restrict__ mean, const float* __restrict__ std_,
+                                                            const float* __restrict__ mu_p, const float* __restrict__ ann,
+                                                            float kl_scale, float fb, int S, long NL, int mode, int out_logstd,
+                                                            float* __restrict__ dmean, float* __restrict__ dstd) {
+    const float w = (ann ? ann[0] : 1.f) * kl_scale;
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < NL; j += (long)gridDim.x * 256) {
+        float dm = S ? 0.f : dmean[j], ds = S ? 0.f : dstd[j];
+        int s = 0;
+        for (; s + 8 <= S; s += 8) {   // (latent_bwd_kernel's loop: the same sums in the same order)
+            float g[8], e[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { g[k] = dz[(long)(s + k) * NL + j]; e[k] = eps[(long)(s + k) * NL + j]; }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { dm += g[k]; ds += g[k] * e[k]; }
+        }
+        for (; s < S; ++s) {
+            const float g = dz[(long)s * NL + j];
+            dm += g;
+            ds += g * eps[(long)s * NL + j];
+        }
+        const float m = mean[j], sd = std_[j];
+        const float mup = mode ? mu_p[j] : 0.f;
+        if (kl_elem(mode, m, sd, mup) > fb) {
+            if (mode == 0) {
+                dm += w * m;
+                ds -= w * (sd / (sd * sd + 1e-5f) - sd);
+            } else {
+                const float den = 2.f * VC_AG_SIGMA * VC_AG_SIGMA + 1e-7f;
+                dm += w * (m - mup) / den;
+                ds -= 0.5f * w * (1.f / (sd + 1e-5f) - 2.f * sd / den);
+            }
+        }
+        dmean[j] = dm;
+        dstd[j] = out_logstd ? ds * sd : ds;
+    }
+}
+
+// Batch means of what kl_rows_fb_kernel leaves per row: out[0] = mean unclamped KL per row, out[1] = share of the N * L
+// dimensions held at the floor.  One workgroup (N rows: a few thousand at most), fixed summation order.
+__global__ __launch_bounds__(256) void objective_stats_kernel(const float* __restrict__ row_kl_raw, const int32_t* __restrict__ row_floored,
+                                                              int N, int L, float* __restrict__ out) {
+    __shared__ float sh[4];
+    float a = 0.f, b = 0.f;
+    for (int n = threadIdx.x; n < N; n += 256) {
+        a += row_kl_raw[n];
+        b += (float)row_floored[n];
+    }
+    a = block_sum<256>(a, sh);
+    b = block_sum<256>(b, sh);
+    if (threadIdx.x == 0) {
+        out[0] = a / (float)N;
+        out[1] = b / ((float)N * (float)L);
+    }
+}
+
+// loss_finalize_kernel with the KL coefficient as an argument: out[2] = rec + ann * kl_coef * kld (kl_coef = beta / 10).
+__global__ void loss_finalize_kl_kernel(const float* ce_num, const float* ce_den, const float* reg, float reg_scale,
+                                        const float* kl_sum, float inv_n, const float* ann, float kl_coef, float* out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float rec = ce_num[0] / ce_den[0];
+    if (reg) rec += reg[0] * reg_scale;
+    const float a = ann ? ann[0] : 1.f;
+    const float kld = kl_sum ? kl_sum[0] * inv_n : 0.f;
+    out[0] = rec;
+    out[1] = kld;
+    out[2] = kl_sum ? rec + a * kl_coef * kld : rec;
+    out[3] = a;
+}
+
 }  // namespace vc
 
 using namespace vc;
@@ -510,6 +756,64 @@ extern "C" int vc_heads_mix_bwd_f32(void* stream, int N, int K, int L, const flo
                                     const int32_t* idx, const float* dmean, const float* dstd, float* dheads) {
     VC_CHECK_ARG(heads && dmean && dstd && dheads && (c_i || idx) && N > 0 && K > 0 && L > 0, "bad argument");
     hipLaunchKernelGGL(heads_mix_bwd_kernel, dim3(grid_for((long)N * K * L)), dim3(256), 0, (hipStream_t)stream, heads, c_i, idx, dmean, dstd, N, K, L, dheads);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- training objective options (each beside its plain entry above; the dispatch rule of the smoothed form is vc_softmax_xent_f32's)
+extern "C" int vc_softmax_xent_smooth_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
+                                          const float* den, float gscale, float eps, float* row_loss, int write_grad) {
+    VC_CHECK_ARG(logits && labels && row_loss && rows >= 0 && V > 0 && ld >= V, "bad argument");
+    VC_CHECK_ARG(!write_grad || den, "den required for the gradient");
+    VC_CHECK_ARG(eps >= 0.f && eps < 1.f, "eps must be in [0, 1)");
+    if (rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
+    dim3 g((unsigned)rows), b(256);
+    if (reg) {
+        if (write_grad) hipLaunchKernelGGL(xent_smooth_reg_kernel<true>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
+        else hipLaunchKernelGGL(xent_smooth_reg_kernel<false>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
+    } else {
+        if (write_grad) hipLaunchKernelGGL(xent_smooth_mem_kernel<true>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
+        else hipLaunchKernelGGL(xent_smooth_mem_kernel<false>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
+    }
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_kl_rows_fb_f32(void* stream, int N, int L, int mode, const float* mean, const float* std_, const float* mu_p,
+                                 float free_bits, float* row_kl, float* row_kl_raw, int32_t* row_floored) {
+    VC_CHECK_ARG(mean && std_ && row_kl && row_kl_raw && row_floored && N > 0 && L > 0 && (mode == 0 || (mode == 1 && mu_p)), "bad argument");
+    hipLaunchKernelGGL(kl_rows_fb_kernel, dim3(cdiv(N, 4)), dim3(256), 0, (hipStream_t)stream, mean, std_, mu_p, N, L, mode, free_bits,
+                       row_kl, row_kl_raw, row_floored);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_latent_bwd_fb_f32(void* stream, int S, int N, int L, int mode, int out_logstd, const float* dz, const float* eps,
+                                    const float* mean, const float* std_, const float* mu_p, const float* ann, float kl_scale,
+                                    float free_bits, float* dmean, float* dstd) {
+    VC_CHECK_ARG(mean && std_ && dmean && dstd && S >= 0 && (S == 0 || (dz && eps)) && N > 0 && L > 0, "bad argument");
+    VC_CHECK_ARG(mode == 0 || (mode == 1 && mu_p), "mu_p required for the AG prior");
+    const long NL = (long)N * L;
+    hipLaunchKernelGGL(latent_bwd_fb_kernel, dim3(grid_for(NL)), dim3(256), 0, (hipStream_t)stream, dz, eps, mean, std_, mu_p, ann,
+                       kl_scale, free_bits, S, NL, mode, out_logstd, dmean, dstd);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_objective_stats_f32(void* stream, int N, int L, const float* row_kl_raw, const int32_t* row_floored, float* out2) {
+    VC_CHECK_ARG(row_kl_raw && row_floored && out2 && N > 0 && L > 0, "bad argument");
+    hipLaunchKernelGGL(objective_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_kl_raw, row_floored, N, L, out2);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const float* ce_den, const float* reg_sumsq, float reg_scale,
+                                       const float* kl_sum, float inv_n, const float* ann, float kl_coef, float* out4) {
+    VC_CHECK_ARG(ce_num && ce_den && out4, "null pointer");
+    hipLaunchKernelGGL(loss_finalize_kl_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ce_num, ce_den, reg_sumsq, reg_scale, kl_sum, inv_n,
+                       ann, kl_coef, out4);
     VC_LAUNCH_CHECK();
     return 0;
 }

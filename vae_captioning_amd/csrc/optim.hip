@@ -74,6 +74,17 @@ __global__ void step_update_kernel(int32_t* step, float* s, float lr, float cnn_
     step[0] = gs + 1;
 }
 
+// Cyclical KL annealing (Fu et al. 2019), launched BEHIND step_update_kernel (which has already incremented step): overwrites s[1] only,
+//   ann = min(1, (gs mod P) / (R * P))  while gs < M * P or M == 0,  1 afterwards      (gs = the step counter before this step)
+// computed from the device counter like the tanh schedule, so a captured step keeps advancing it.
+__global__ void cyclical_ann_kernel(const int32_t* step, float* s, int period, float ramp, int cycles) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int gs = step[0] - 1;
+    float a = 1.f;
+    if (cycles == 0 || (long)gs < (long)cycles * period) a = fminf(1.f, (float)(gs % period) / (ramp * (float)period));
+    s[1] = a;
+}
+
 // tf.train.AdamOptimizer.apply_gradients (ops/optimizers.py:37-40,72-75; TF-sem.):
 //   g' = g*scale (+ l2*p);  m = b1*m + (1-b1)*g';  v = b2*v + (1-b2)*g'^2;  p -= lr_t*m/(sqrt(v)+eps)
 // SUMSQ: also leaves sum(p_new^2) of the block in sumsq_partial[blockIdx.x] -- the regulariser's loss term of the NEXT step
@@ -208,6 +219,18 @@ extern "C" int vc_step_update(void* stream, int32_t* step, float* scalars, float
                               float ann_param, int ann_on, int decay_steps) {
     VC_CHECK_ARG(step && scalars, "null pointer");
     hipLaunchKernelGGL(step_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step, scalars, lr, cnn_lr, beta1, beta2, ann_param, ann_on, decay_steps);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// vc_step_update with the cyclical KL schedule in scalars[1]: step_update_kernel itself (tanh schedule off) writes every other scalar
+// and increments the counter, then cyclical_ann_kernel overwrites scalars[1] -- s[0], s[2..4] are vc_step_update's to the bit.
+extern "C" int vc_step_update_cyclical(void* stream, int32_t* step, float* scalars, float lr, float cnn_lr, float beta1, float beta2,
+                                       int decay_steps, int cycle_steps, float cycle_ramp, int cycles) {
+    VC_CHECK_ARG(step && scalars, "null pointer");
+    VC_CHECK_ARG(cycle_steps > 0 && cycle_ramp > 0.f && cycle_ramp <= 1.f && cycles >= 0, "cycle_steps > 0, cycle_ramp in (0, 1], cycles >= 0");
+    hipLaunchKernelGGL(step_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step, scalars, lr, cnn_lr, beta1, beta2, 0.f, 0, decay_steps);
+    hipLaunchKernelGGL(cyclical_ann_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step, scalars, cycle_steps, cycle_ramp, cycles);
     VC_LAUNCH_CHECK();
     return 0;
 }

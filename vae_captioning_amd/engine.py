@@ -226,6 +226,15 @@ class CaptionEngine(object):
             self.c_means = torch.from_numpy(init_clusters(K_CL, p.latent_size)).to(device)
         self.ann_on = int((not p.fine_tune) and (not p.restore) and p.ann_param > 1)  # main.py:163-170
         self.decay_steps = int(p.num_ex_per_epoch / (p.batch_size * world + 0.001) * p.num_epochs_per_decay)  # ops/optimizers.py:24-25, global batch
+        # Training objective options (DESIGN.md "Training objective options").  Each one off = the plain library entry on the same data
+        # as before; on = the entry of csrc/loss.hip / optim.hip that stands beside it.  The KL options need the encoder's KL term.
+        self.free_bits = float(getattr(p, "kl_free_bits", 0.0)) if self.enc else 0.0          # > 0: vc_kl_rows_fb_f32 / vc_latent_bwd_fb_f32
+        self.kl_weight = float(getattr(p, "kl_weight", 1.0)) if self.enc else 1.0             # != 1: kl_scale * beta, vc_loss_finalize_kl_f32
+        self.label_smoothing = float(getattr(p, "label_smoothing", 0.0))                      # > 0: vc_softmax_xent_smooth_f32 (training forward only)
+        self.kl_cycle = (int(getattr(p, "kl_cycle_steps", 0)), float(getattr(p, "kl_cycle_ramp", 0.5)), int(getattr(p, "kl_cycles", 0))) if self.enc else (0, 0.5, 0)  # P > 0: vc_step_update_cyclical
+        if self.kl_cycle[0] > 0:
+            self.ann_on = 0   # the cyclical schedule owns the coefficient (also under --restore / --fine_tune: Q10 is about the tanh one)
+        self.ostat = torch.zeros(2, **f32) if self.free_bits > 0 else None   # vc_objective_stats_f32: mean unclamped KL, floored share
 
     def _reduce_scatter(self, out, inp):
         """sum-reduce-scatter of inp [world*n, L] into out [n, L] (RCCL; backends without the primitive,
@@ -617,7 +626,9 @@ class CaptionEngine(object):
         self.feats = feats
         if not self.inject:
             self._noise()
-        if train:  # global_step / annealing / lr schedules advance only on optimiser steps
+        if train and self.kl_cycle[0] > 0:  # cyclical KL annealing: the coefficient from the device step counter, like the tanh one
+            lib.vc_step_update_cyclical(st, P(self.step), P(self.scal), p.learning_rate, p.cnn_lr, 0.8, 0.999, self.decay_steps, *self.kl_cycle)
+        elif train:  # global_step / annealing / lr schedules advance only on optimiser steps
             lib.vc_step_update(st, P(self.step), P(self.scal), p.learning_rate, p.cnn_lr, 0.8, 0.999, float(p.ann_param), self.ann_on, self.decay_steps)
         ann = self.scal[1:2]
         # imf_emb on the B image rows, then tile x nc (identical values to tiling first, main.py:84-94)
@@ -713,7 +724,12 @@ class CaptionEngine(object):
         else:
             lib.vc_latent_sample_f32(st, Sm, N, L, P(mean), P(std), P(self.buf["eps"]), P(z))
         row_kl = self._b("row_kl", (N,))
-        lib.vc_kl_rows_f32(st, N, L, mode, P(mean), P(std), P(mu_p), P(row_kl))
+        if self.free_bits > 0:  # free bits: sum_l max(lambda, kl[n,l]); the same pass leaves the unclamped sums and the floored counts
+            raw, nfl = self._b("row_kl_raw", (N,)), self._b("row_floored", (N,), torch.int32)
+            lib.vc_kl_rows_fb_f32(st, N, L, mode, P(mean), P(std), P(mu_p), self.free_bits, P(row_kl), P(raw), P(nfl))
+            lib.vc_objective_stats_f32(st, N, L, P(raw), P(nfl), P(self.ostat))
+        else:
+            lib.vc_kl_rows_f32(st, N, L, mode, P(mean), P(std), P(mu_p), P(row_kl))
         lib.vc_reduce_sum_f32(st, P(row_kl), N, 1.0, self.red.data_ptr() + 8, 0)
         self.kl_sum = self.red.data_ptr() + 8
         return z
@@ -769,8 +785,12 @@ class CaptionEngine(object):
         Ng = N * self.world
         gscale = dp.scales(N, self.world, vector_loss)[0]
         row_loss = self._b("row_loss", (T * N,))
-        self._timed("hbm_softmax_xent", 8.0 * T * N * V,  # logits read once, d(logits) written in place
-                    lambda: lib.vc_softmax_xent_f32(st, P(logits), P(labels), T * N, V, _round(V, 4), P(den), gscale, P(row_loss), 1 if train else 0))
+        if train and self.label_smoothing > 0:  # (validation, train=False, keeps the plain loss: comparable between runs)
+            self._timed("hbm_softmax_xent", 8.0 * T * N * V,
+                        lambda: lib.vc_softmax_xent_smooth_f32(st, P(logits), P(labels), T * N, V, _round(V, 4), P(den), gscale, self.label_smoothing, P(row_loss), 1))
+        else:
+            self._timed("hbm_softmax_xent", 8.0 * T * N * V,  # logits read once, d(logits) written in place
+                        lambda: lib.vc_softmax_xent_f32(st, P(logits), P(labels), T * N, V, _round(V, 4), P(den), gscale, P(row_loss), 1 if train else 0))
         lib.vc_reduce_sum_f32(st, P(row_loss), T * N, 1.0, P(self.red), 0)
         # Data-parallel training step: ce_num and kl_sum are needed for REPORTING only (the gradient's scales are the global count
         # and row number), so they ride in the tail of the gradient all-reduce (pack_tail) and the losses are finalised behind it
@@ -791,8 +811,12 @@ class CaptionEngine(object):
             self.red[0:1].copy_(r2[0:1])
             self.red[2:3].copy_(r2[1:2])
         reg = self.red.data_ptr() + 12 if self.reg_scale else None
-        lib.vc_loss_finalize_f32(st, P(self.red), self.red.data_ptr() + 4, reg, float(self.reg_scale), kl_sum, 1.0 / Ng,
-                                 P(ann) if self.enc else None, P(self.out))
+        if self.kl_weight != 1.0:  # lower_bound = rec + ann * beta * kld / 10 (kld itself stays the unweighted mean KL)
+            lib.vc_loss_finalize_kl_f32(st, P(self.red), self.red.data_ptr() + 4, reg, float(self.reg_scale), kl_sum, 1.0 / Ng,
+                                        P(ann) if self.enc else None, self.kl_weight / 10.0, P(self.out))
+        else:
+            lib.vc_loss_finalize_f32(st, P(self.red), self.red.data_ptr() + 4, reg, float(self.reg_scale), kl_sum, 1.0 / Ng,
+                                     P(ann) if self.enc else None, P(self.out))
 
     # ---------------------------------------------------------------- backward
     def backward(self, want_dfeatures=False):
@@ -868,10 +892,19 @@ class CaptionEngine(object):
                 self.rscatter_fn(dms.view(-1), pin.view(-1))
                 Sb = 0
             _, kl_n, kl_ag, _ = dp.scales(N, self.world, p.prior == "AG")
+            if self.kl_weight != 1.0:  # the KL term's gradient times beta: a host constant folded into kl_scale
+                kl_n, kl_ag = kl_n * self.kl_weight, kl_ag * self.kl_weight
             hT = self.buf["hs_e"][Te]
             dhT = self._b("dH_e", (N, He))
+
+            def latent_bwd(mode, out_logstd, mu_p, kl_scale):
+                a = (st, Sb, N, L, mode, out_logstd, P(dz), P(self.buf["eps"]), P(mean), P(std), mu_p, P(ann), kl_scale)
+                if self.free_bits > 0:  # no KL gradient for the dimensions the forward pass held at the floor
+                    lib.vc_latent_bwd_fb_f32(*a, self.free_bits, P(dmean), P(dstd))
+                else:
+                    lib.vc_latent_bwd_f32(*a, P(dmean), P(dstd))
             if p.prior == "Normal":
-                lib.vc_latent_bwd_f32(st, Sb, N, L, 0, 1, P(dz), P(self.buf["eps"]), P(mean), P(std), None, P(ann), kl_n, P(dmean), P(dstd))
+                latent_bwd(0, 1, None, kl_n)
                 side(lambda: (self.dense_bwd_w(hT, N, He, L, dmean, "encoder/dense/kernel", "encoder/dense/bias"),
                               self.dense_bwd_w(hT, N, He, L, dstd, "encoder/dense_1/kernel", "encoder/dense_1/bias")))
                 self.gemm(0, 1, N, He, L, dmean, L, S.param("encoder/dense/kernel"), L, dhT, He)
@@ -879,9 +912,9 @@ class CaptionEngine(object):
             else:
                 gmm = p.prior == "GMM"
                 if gmm:
-                    lib.vc_latent_bwd_f32(st, Sb, N, L, 0, 0, P(dz), P(self.buf["eps"]), P(mean), P(std), None, P(ann), kl_n, P(dmean), P(dstd))
+                    latent_bwd(0, 0, None, kl_n)
                 else:
-                    lib.vc_latent_bwd_f32(st, Sb, N, L, 1, 0, P(dz), P(self.buf["eps"]), P(mean), P(std), P(self.buf["mu_p"]), P(ann), kl_ag, P(dmean), P(dstd))
+                    latent_bwd(1, 0, P(self.buf["mu_p"]), kl_ag)
                 heads = self.buf["heads"]
                 dheads = self._b("dheads", (N, 2 * K_CL * L))
                 lib.vc_heads_mix_bwd_f32(st, N, K_CL, L, P(heads), None if gmm else P(self.buf["c_v"]), P(self.buf["gmm_idx"]) if gmm else None,
@@ -999,6 +1032,14 @@ class CaptionEngine(object):
         o = self.out.detach().cpu().numpy()
         self._release_retired()
         return float(o[1]), float(o[0]), float(o[2]), float(o[3])
+
+    def objective_stats(self):
+        """Free bits (--kl_free_bits > 0): {"kl_raw": mean unclamped KL per caption row, "floored_share": share of the N * L latent
+        dimensions held at the floor} of the last forward pass over this rank's rows; None when free bits are off."""
+        if self.ostat is None:
+            return None
+        o = self.ostat.detach().cpu().numpy()
+        return {"kl_raw": float(o[0]), "floored_share": float(o[1])}
 
 
 def embedding_grad_index(ids, vocab, chunk=32):

@@ -793,6 +793,9 @@ class Trainer(object):
     def losses(self):
         return self.cap.losses()
 
+    def objective_stats(self):
+        return self.cap.objective_stats()
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         """Every trainable variable of the reference graph (main.py:186-191).  The reference builds the VGG16 variables

@@ -29,6 +29,8 @@ _DEFAULTS = dict(
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
     bound_draws=0, marginal_draws=20, constraints=None, cbs_width=0,
     no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
+    # training objective options (every one off by default: the reference's objective)
+    kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -57,7 +59,12 @@ _FLAGS = [
     ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
     ("--no_repeat_ngram", "no_repeat_ngram", int, None), ("--min_len", "min_len", int, None),
     ("--repetition_penalty", "repetition_penalty", float, None), ("--banned_words", "banned_words", str, None),
+    ("--kl_free_bits", "kl_free_bits", float, None), ("--kl_weight", "kl_weight", float, None),
+    ("--kl_cycle_steps", "kl_cycle_steps", int, None), ("--kl_cycle_ramp", "kl_cycle_ramp", float, None),
+    ("--kl_cycles", "kl_cycles", int, None), ("--label_smoothing", "label_smoothing", float, None),
+    ("--word_drop", "word_drop", float, None),
 ]
+_KL_FLAGS = ("kl_free_bits", "kl_weight", "kl_cycle_steps", "kl_cycle_ramp", "kl_cycles")
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
          "--captions_json": "COCO captions json (with --features_pickle: in-memory real-data path)",
@@ -98,6 +105,17 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                                  "(negative) by this (1..10; default 1.0 = off)",
          "--banned_words": "decoding controls: JSON file with a list of words (vocabulary strings or integer token ids, at most 256) that "
                            "no caption may hold; not with --sample_gen marginal_greedy / marginal_beam, like the three flags above",
+         "--kl_free_bits": "training objective: KL floor in nats per latent dimension and caption row (free bits: a dimension whose KL "
+                           "is at or below it is held at the floor and gets no KL gradient; >= 0; default 0 = off)",
+         "--kl_weight": "training objective: weight beta of the KL term in the lower bound and its gradient (> 0; default 1.0)",
+         "--kl_cycle_steps": "training objective: period P of cyclical KL annealing in steps, annealing = min(1, (step mod P) / "
+                             "(ramp * P)); also under --restore / --fine_tune; not with --ann_param > 1 (>= 0; default 0 = off)",
+         "--kl_cycle_ramp": "--kl_cycle_steps: share of each period over which the coefficient rises from 0 to 1 (in (0, 1]; default 0.5)",
+         "--kl_cycles": "--kl_cycle_steps: number of periods, after which the coefficient stays 1 (>= 0; default 0 = forever)",
+         "--label_smoothing": "training objective: the reconstruction target is (1 - eps) * onehot + eps / vocabulary (in [0, 1); "
+                              "default 0 = off; validation losses stay unsmoothed)",
+         "--word_drop": "training: each decoder input word behind <BOS> is replaced by <UNK> with this probability (in [0, 1); "
+                        "default 0 = off; seeded by --seed; never in validation or inference)",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
@@ -184,6 +202,25 @@ class Parameters(object):
             ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
         if not (0.0 < self.top_p <= 1.0):
             ap.error("--top_p must be in (0, 1] (got %r)" % self.top_p)
+        if not (0.0 <= self.kl_free_bits < float("inf")):
+            ap.error("--kl_free_bits must be finite and >= 0 (0 = off; got %r)" % self.kl_free_bits)
+        if not (0.0 < self.kl_weight < float("inf")):
+            ap.error("--kl_weight must be finite and > 0 (got %r)" % self.kl_weight)
+        if not (0.0 <= self.label_smoothing < 1.0):
+            ap.error("--label_smoothing must be in [0, 1) (0 = off; got %r)" % self.label_smoothing)
+        if self.kl_cycle_steps < 0:
+            ap.error("--kl_cycle_steps must be >= 0 (0 = off; got %d)" % self.kl_cycle_steps)
+        if not (0.0 < self.kl_cycle_ramp <= 1.0):
+            ap.error("--kl_cycle_ramp must be in (0, 1] (got %r)" % self.kl_cycle_ramp)
+        if self.kl_cycles < 0:
+            ap.error("--kl_cycles must be >= 0 (0 = forever; got %d)" % self.kl_cycles)
+        if not (0.0 <= self.word_drop < 1.0):
+            ap.error("--word_drop must be in [0, 1) (0 = off; got %r)" % self.word_drop)
+        if self.kl_cycle_steps > 0 and self.ann_param > 1:
+            ap.error("--kl_cycle_steps and --ann_param > 1 are two schedules for the one annealing coefficient: give one of them")
+        if self.no_encoder and any(args[k] is not None for k in _KL_FLAGS):
+            ap.error("--kl_free_bits / --kl_weight / --kl_cycle_steps / --kl_cycle_ramp / --kl_cycles shape the KL term, and "
+                     "--no_encoder has none")
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.synthetic:
