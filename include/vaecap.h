@@ -73,6 +73,9 @@ int vc_trace_pop(void);
  * gradients (ops/optimizers.py:13,51).
  * Small outputs with long K are split along K into `ws` (vc_gemm_workspace_bytes) and
  * reduced in a fixed order (deterministic).
+ * M == 0 or N == 0: nothing to do, returns 0.  K == 0 is the zero product (BLAS semantics): C = epilogue(0), i.e.
+ * bias (or 0), + C with VC_GEMM_ACCUMULATE, ReLU'd with VC_GEMM_RELU; A and B are not read and may be NULL;
+ * vc_gemm_workspace_bytes(M, N, 0) == 0.  Both precisions.
  * ---------------------------------------------------------------------------------- */
 #define VC_GEMM_RELU 1
 #define VC_GEMM_ACCUMULATE 2

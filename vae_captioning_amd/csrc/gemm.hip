@@ -247,6 +247,7 @@ static GemmPlan plan_gemm(int M, int N, int K) {
     int kchunk = cdiv(cdiv(K, splits), 32) * 32;
     if (kchunk < 32) kchunk = 32;
     p.splits = cdiv(K, kchunk);
+    if (p.splits < 1) p.splits = 1;  // K == 0: one launch over an empty K range (the kernels skip their loops), C = epilogue(0)
     p.kchunk = kchunk;
     p.main_m = p.tiles_m; p.tail_splits = 1; p.tail_kchunk = 0;
     if (p.big && p.splits == 1) {
@@ -324,9 +325,10 @@ static BxPlan plan_bx256(int M, int N, int K) {
         if (eff > beff + 1e-9) { beff = eff; best = s; }
     }
     if (t * best < 200) return p;   // under one round: the 128 x 128 plan spreads the work better
-    p.splits = best;
     p.kchunk = cdiv(cdiv(K, best), 32) * 32;
+    if (p.kchunk < 32) p.kchunk = 32;   // K == 0 (a chunk of 0 would divide by zero below): one split over an empty K range
     p.splits = cdiv(K, p.kchunk);
+    if (p.splits < 1) p.splits = 1;
     p.use = true;
     return p;
 }
@@ -444,7 +446,9 @@ static int gemm_impl(int prec, const char* fn, void* stream, int ta, int tb, int
     using namespace vc;
     VC_GEMM_ARG(M >= 0 && N >= 0 && K >= 0, "negative dimension");
     if (M == 0 || N == 0) return 0;
-    VC_GEMM_ARG(A && B && C, "null operand");
+    // K == 0 is the zero product: C = epilogue(0).  A and B are never read then (an empty tensor's pointer may be null); the planners
+    // give one split over an empty K range, and the kernels skip their loops when k_begin >= k_end.
+    VC_GEMM_ARG(C && (K == 0 || (A && B)), "null operand");
     VC_GEMM_ARG(lda >= (ta ? M : K) && ldb >= (tb ? K : N) && ldc >= N, "leading dimension too small");
     hipStream_t st = (hipStream_t)stream;
     auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
