@@ -143,25 +143,21 @@ class Generator(object):
         im_id = [img_path.split("/")[-1]]
         feature_vector, image = self._get_features(img_path)
         c_v = self._c_v_generator(image) if self.params.use_c_v else None
-        if self.gen_method == "beam_search":
-            return decoder.beam_search(None, im_id, feature_vector, None, c_v, beam_size=int(beam_size))
-        if self.gen_method in ("greedy", "sample"):
-            sent, _ = decoder.online_inference(None, im_id, feature_vector, None, c_v=c_v)
-            return sent
-        if self.gen_method == "diverse":
-            return decoder.diverse_inference(None, im_id, feature_vector, None, c_v, draws=diverse_draws)
-        if self.gen_method in ("marginal_greedy", "marginal_beam"):
-            return decoder.marginal_inference(None, im_id, feature_vector, None, c_v, method=self.gen_method, draws=marginal_draws,
-                                              beam_size=int(beam_size))
-        if self.gen_method == "constrained_beam":
+        mode, own = self.gen_method, {}   # own: what this call gives the mode in place of its params defaults
+        if mode not in ("greedy", "beam_search", "sample", "diverse", "marginal_greedy", "marginal_beam", "constrained_beam", "stochastic_beam"):
+            raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam or stochastic_beam")
+        if mode in ("beam_search", "marginal_greedy", "marginal_beam", "stochastic_beam"):
+            own["beam_size"] = int(beam_size)
+        if mode == "diverse":
+            own["draws"] = diverse_draws
+        if mode in ("marginal_greedy", "marginal_beam"):
+            own.update(method=mode, draws=marginal_draws)
+        if mode == "constrained_beam":
             from vae_captioning_amd.constraints import parse_must_include
             w2i = self.data_dict.word2idx
             decoder.constraints = parse_must_include(must_include or "", w2i, self.data_dict.vocab_size, w2i["<BOS>"], w2i["<EOS>"])
             print(decoder.constraints.summary())
-            return decoder.constrained_beam_search(None, im_id, feature_vector, None, c_v)
-        if self.gen_method == "stochastic_beam":
-            return decoder.stochastic_beam_search(None, im_id, feature_vector, None, c_v, beam_size=int(beam_size))
-        raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam or stochastic_beam")
+        return decoder.decode(mode, im_id, feature_vector, c_v, **own)
 
 
 if __name__ == "__main__":

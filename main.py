@@ -27,7 +27,7 @@ sys.path.insert(0, ROOT)
 from vae_captioning_amd import objective, session, spec, synth  # noqa: E402
 from vae_captioning_amd.ops import optimizers  # noqa: E402
 from vae_captioning_amd.utils.parameters import Parameters  # noqa: E402
-from vae_captioning_amd.vae_model.decoder import Decoder  # noqa: E402
+from vae_captioning_amd.vae_model.decoder import DIVERSE_FILE_MODES, Decoder  # noqa: E402
 from vae_captioning_amd.vae_model.encoder import Encoder  # noqa: E402
 
 
@@ -291,26 +291,16 @@ def main(params):
             ids = ["synthetic_%06d" % (it * params.batch_size + i) for i in range(params.batch_size)]
             pics = b["images"] if params.fine_tune else b["features"]
             c_v = b.get("c_v")
+            sent = decoder.decode(params.sample_gen, ids, pics, c_v)
             if params.sample_gen == "diverse":   # every distinct caption of every image, best first
-                sent = decoder.diverse_inference(None, ids, pics, None, c_v)
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (x%d)" % (t, n) for t, n in zip(r["captions"], r["counts"]))))
             elif params.sample_gen == "diverse_beam":   # group beam search: the groups' captions merged, best first
-                sent = decoder.diverse_beam_search(None, ids, pics, None, c_v)
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (groups %s)" % (t, ",".join(map(str, g))) for t, g in zip(r["captions"], r["groups"]))))
             elif params.sample_gen == "stochastic_beam":   # --beam_size distinct captions sampled without replacement, with their weights
-                sent = decoder.stochastic_beam_search(None, ids, pics, None, c_v)
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (logp %.3f, w %.3g)" % (t, lp, w) for t, lp, w in zip(r["captions"], r["logprob"], r["norm_weight"]))))
-            elif params.sample_gen in ("marginal_greedy", "marginal_beam"):   # search under the mixture of --marginal_draws latent draws
-                sent = decoder.marginal_inference(None, ids, pics, None, c_v)
-            elif params.sample_gen == "constrained_beam":   # beam search whose captions mention the words of --constraints
-                sent = decoder.constrained_beam_search(None, ids, pics, None, c_v)
-            elif params.sample_gen == "beam_search":
-                sent = decoder.beam_search(None, ids, pics, None, c_v, beam_size=params.beam_size)
-            else:
-                sent, _ = decoder.online_inference(None, ids, pics, None, c_v=c_v)
             captions_gen += sent
             if params.eval_captions:   # the batch's own captions (one per image, by construction) are its "human" references
                 from vae_captioning_amd.ops.inference import decoded_ids, human_captions
@@ -326,7 +316,7 @@ def main(params):
         if rank == 0:
             with open("./val_{}.json".format(params.gen_name), "w") as wj:
                 json.dump(captions_gen, wj)
-            if params.sample_gen in ("diverse", "diverse_beam", "stochastic_beam"):   # the full per-image lists under the name ops/inference.py gives them
+            if params.sample_gen in DIVERSE_FILE_MODES:   # the full per-image lists under the name ops/inference.py gives them
                 with open("./val_{}_diverse.json".format(params.gen_name), "w") as wj:
                     json.dump(captions_gen, wj)
             if params.score_draws:

@@ -1,10 +1,12 @@
-"""Launch-trace recorder for VggEngine (tests/test_gpu_vgg_trace.py): what the engine asks of the library and of the stream
-structure during one forward + backward, in program order, without anything that depends on addresses.
+"""Launch-trace recorder (tests/test_gpu_vgg_trace.py, tests/test_gpu_decode_trace.py): what an engine or a generator asks of the library,
+of the stream structure and of its captured graphs, in program order, without anything that depends on addresses.
 
 Every vc_* call whose first argument is a stream becomes [entry name, stream ordinal, [arguments]]: scalars as passed, a pointer only
 as 0 (null) / 1.  Stream ordering becomes ["wait_stream", waiter, waited], ["wait_event", waiter, event] and ["record", event, stream];
-streams are 0 = the caller's, 1 / 2 = the engine's two side streams, events are numbered in order of first appearance.  Host-only
-queries (*_supported, *_preferred, *_workspace_bytes, *_words) are passed through unrecorded."""
+graphs become ["capture_begin"], ["capture_end"] and ["replay", graph].  Stream ordinals come from the map the caller gives (VggEngine:
+0 = the caller's, 1 / 2 = the engine's two side streams); a stream outside it, and every event and graph, is numbered in order of first
+appearance (a graph appears when its capture begins).  Host-only queries (*_supported, *_preferred, *_workspace_bytes, *_words) are
+passed through unrecorded."""
 import contextlib
 
 import numpy as np
@@ -51,19 +53,31 @@ class RecordingLib(object):
 
 
 @contextlib.contextmanager
-def recording(eng, log):
-    """Route eng's library calls and torch's stream-ordering calls into `log` while the caller holds rec.on True."""
-    handles = {torch.cuda.current_stream().cuda_stream: 0}
-    for i, s in ((1, eng._side), (2, eng._side2)):
-        if s is not None:
-            handles[s.cuda_stream] = i
-    events = {}
-    ordinal = lambda h: handles[int(h or 0)]
+def recording(objs, log, streams=None):
+    """Route the library calls of `objs` (everything whose .lib to swap: an engine, its generator) and torch's stream-ordering and
+    graph calls into `log` while the caller holds rec.on True.  streams: {stream handle: ordinal} of the streams known beforehand."""
+    handles = dict(streams if streams is not None else {torch.cuda.current_stream().cuda_stream: 0})
+    events, graphs = {}, {}
+
+    def ordinal(h):
+        h = int(h or 0)
+        if h not in handles:
+            handles[h] = max(handles.values(), default=-1) + 1
+        return handles[h]
+
     so = lambda s: ordinal(s.cuda_stream)
-    ev = lambda e: events.setdefault(id(e), len(events))
-    rec = RecordingLib(eng.lib, log, ordinal)
-    keep = []   # (events stay alive while their id() is a key)
+    keep = []   # (events and graphs stay alive while their id() is a key)
+
+    def number(table, obj):
+        if id(obj) not in table:
+            keep.append(obj)
+            table[id(obj)] = len(table)
+        return table[id(obj)]
+
+    rec = RecordingLib(objs[0].lib, log, ordinal)
+    Graph = torch.cuda.CUDAGraph
     orig = (torch.cuda.Stream.wait_stream, torch.cuda.Stream.wait_event, torch.cuda.Event.record)
+    orig_graph = (Graph.capture_begin, Graph.capture_end, Graph.replay)
 
     def wait_stream(self, other):
         on = rec.on
@@ -77,23 +91,43 @@ def recording(eng, log):
 
     def wait_event(self, event):
         if rec.on:
-            keep.append(event)
-            log.append(["wait_event", so(self), ev(event)])
+            log.append(["wait_event", so(self), number(events, event)])
         return orig[1](self, event)
 
     def record(self, stream=None):
         if rec.on:
-            keep.append(self)
-            log.append(["record", ev(self), so(stream if stream is not None else torch.cuda.current_stream())])
+            log.append(["record", number(events, self), so(stream if stream is not None else torch.cuda.current_stream())])
         return orig[2](self) if stream is None else orig[2](self, stream)
 
-    real, eng.lib = eng.lib, rec
+    def capture_begin(self, *a, **k):
+        if rec.on:
+            number(graphs, self)
+            log.append(["capture_begin"])
+        return orig_graph[0](self, *a, **k)
+
+    def capture_end(self):
+        if rec.on:
+            log.append(["capture_end"])
+        return orig_graph[1](self)
+
+    def replay(self):
+        if rec.on:
+            log.append(["replay", number(graphs, self)])
+        return orig_graph[2](self)
+
+    real = [o.lib for o in objs]
+    assert all(r is real[0] for r in real)
+    for o in objs:
+        o.lib = rec
     torch.cuda.Stream.wait_stream, torch.cuda.Stream.wait_event, torch.cuda.Event.record = wait_stream, wait_event, record
+    Graph.capture_begin, Graph.capture_end, Graph.replay = capture_begin, capture_end, replay
     try:
         yield rec
     finally:
         torch.cuda.Stream.wait_stream, torch.cuda.Stream.wait_event, torch.cuda.Event.record = orig
-        eng.lib = real
+        Graph.capture_begin, Graph.capture_end, Graph.replay = orig_graph
+        for o, r in zip(objs, real):
+            o.lib = r
 
 
 def trace_case(lib, case, setenv):
@@ -114,7 +148,11 @@ def trace_case(lib, case, setenv):
     img = torch.from_numpy(rng.integers(0, 256, size=(B, 224, 224, 3)).astype(np.float32)).cuda()
     dfc2 = torch.from_numpy(rng.normal(size=(B, 4096)).astype(np.float32)).cuda()
     log = []
-    with recording(eng, log) as rec:
+    streams = {torch.cuda.current_stream().cuda_stream: 0}
+    for i, s in ((1, eng._side), (2, eng._side2)):
+        if s is not None:
+            streams[s.cuda_stream] = i
+    with recording([eng], log, streams) as rec:
         for step in range(2):
             rec.on = step == 1
             eng.forward(img)

@@ -21,6 +21,9 @@ import torch
 from . import spec
 from .abi import ptr as P
 from .controls import MAX_BANNED, active as active_controls
+from .decode_host import (CBS_MAX_SETS, CBS_MAX_WORDS, DIVERSE_MAX_DRAWS, SCORE_MAX_TOKENS, FieldLayout, beam_fields, beams_from_host,  # noqa: F401 (re-exported)
+                          check_constraints, check_truncation, diverse_fields, diverse_from_host, marginal_greedy_from_host, merge_groups,
+                          rerank_by_marginal, sbs_from_host, sbs_weights, select_bank)
 from .engine import K_CL, _stream
 
 # vae_model/decoder.py:56 -- category ids absent from MSCOCO (obj_vectors/category_index.pickle)
@@ -39,202 +42,39 @@ def _phase(name, t0):
     return t
 
 
-def beams_from_host(ints, dbls, io, B, n, L, last):
-    """The kept beams of B images from a slice's result buffers (host copies): per image the list of (sentence, score), descending.
-    ints: the int32 fields at the offsets `io` (pcount / ccount [B], p_len / c_len / c_slot [B, n], sent0 / sent1 [B, n, L],
-    c_sent [B, n + 1, L]); dbls: p_score [B, n] then c_score [B, n]; last: which of sent0 / sent1 the last round wrote.
-    vae_model/decoder.py:295-320: the complete captions if an image has any, else its live beams -- never mixed -- sorted by
-    TopN.extract(sort=True), i.e. list.sort(reverse=True) on the heap array: descending score, equal scores in array order.
-    Python lists come from whole buffers (one tolist each; slicing lists is ~5x cheaper than a numpy view + tolist per beam), and of
-    the two sentence stores only what the slice needs: the pool of complete captions, the live beams, or both."""
-    M = B * n
-    small, sc = ints[:io["sent0"]].tolist(), dbls.tolist()
-    pc, cc = small[io["pcount"]:io["pcount"] + B], small[io["ccount"]:io["ccount"] + B]
-    pl, cl, csl = small[io["p_len"]:io["p_len"] + M], small[io["c_len"]:io["c_len"] + M], small[io["c_slot"]:io["c_slot"] + M]
-    o = io["sent%d" % last]
-    pf = None if all(cc) else ints[o:o + M * L].tolist()
-    cf = ints[io["c_sent"]:io["c_sent"] + B * (n + 1) * L].tolist() if any(cc) else None
-    res = []
-    for b in range(B):
-        r0 = b * n
-        if cc[b]:
-            k_, s_ = cc[b], sc[M + r0:M + r0 + cc[b]]
-            rows = [(b * (n + 1) + csl[r0 + j]) * L for j in range(k_)]
-            ln, src = cl[r0:r0 + k_], cf
-        else:
-            k_, s_ = pc[b], sc[r0:r0 + pc[b]]
-            rows = [(r0 + j) * L for j in range(k_)]
-            ln, src = pl[r0:r0 + k_], pf
-        order = sorted(range(k_), key=s_.__getitem__, reverse=True) if k_ > 1 else range(k_)
-        res.append([(src[rows[j]:rows[j] + ln[j]], s_[j]) for j in order])
-    return res
+def _cut(a, sl, axis=0):
+    """A pass's share a[sl] along `axis` of an optional array (c_v [B, 90]; eps [K, S, B, L], uniforms [K, T, B]: axis 2); None stays None."""
+    return None if a is None else a[(slice(None),) * axis + (sl,)]
 
 
-class FieldLayout(object):
-    """Named fields packed back to back in ONE flat buffer (no padding): fields = [(name, size), ...] in buffer order, off[name] = where
-    a field starts, total = the buffer's length, views(buf) = {name: its slice of buf}.  The device fills the fields, one copy brings
-    the buffer back, the host reads by offset."""
-    def __init__(self, fields):
-        self.fields, self.off, self.total = list(fields), {}, 0
-        for name, n in self.fields:
-            self.off[name], self.total = self.total, self.total + n
+class _BeamSlice(object):
+    """The TopN state of B images x n beams, sentences of <= L tokens (vae_model/decoder.py:238-247), in persistent buffers of the generator.
+    What the host reads lives in TWO flat buffers (ibuf: beam_fields; dbuf: float64 p_score, c_score, p_logprob, c_logprob [B, n], then
+    `extra`): two copies into pinned memory bring it back, no gathering launches.  sent: the stores that alternate with the round's parity."""
+    def __init__(self, gen, tag, B, n, L, extra=()):
+        M, i32 = B * n, torch.int32
+        self.B, self.n, self.L = B, n, L
+        self.lay = FieldLayout(beam_fields(B, n, L))
+        self.dlay = FieldLayout([(k_, M) for k_ in ("p_score", "c_score", "p_logprob", "c_logprob")] + list(extra))
+        self.ibuf, self.dbuf = gen._b(tag + "ibuf", (self.lay.total,), i32), gen._b(tag + "dbuf", (self.dlay.total,), torch.float64)
+        self.i, self.d = self.lay.views(self.ibuf), self.dlay.views(self.dbuf)
+        self.sent = [self.i["sent0"], self.i["sent1"]]
+        self.c_free, self.parent, self.tok = gen._b(tag + "c_free", (B,), i32), gen._b(tag + "parent", (M,), i32), gen._b(tag + "tok", (M,), i32)
+        self.tensors = [self.ibuf, self.dbuf, self.c_free, self.parent, self.tok]
+        self.scores = self.dbuf[:self.dlay.off["p_logprob"]]   # (the host reads the scores only)
 
-    def views(self, buf):
-        return {name: buf[self.off[name]:self.off[name] + n] for name, n in self.fields}
+    def init(self, lib, bos, H, c, h, c2, h2):
+        """One launch: partial = [Beam([bos], state b, 0.0, 0.0)], every row of c2, h2 [B*n, H] = its image's row of c, h; parent = identity"""
+        i, d = self.i, self.d
+        lib.vc_beam_init(_stream(), self.B, self.n, self.L, int(bos), H, P(c), P(h), P(c2), P(h2), P(i["pcount"]), P(i["ccount"]), P(d["p_score"]),
+                         P(d["p_logprob"]), P(i["p_len"]), P(self.sent[0]), P(self.sent[1]), P(d["c_score"]), P(d["c_logprob"]), P(i["c_len"]),
+                         P(i["c_slot"]), P(self.c_free), P(i["c_sent"]), P(self.parent), P(self.tok))
 
-
-def beam_fields(B, n, L):
-    """(name, size) of the int32 result buffer of a beam-search slice of B images x n beams, sentences of <= L tokens, in buffer order
-    (what beams_from_host reads).  The float64 buffer holds p_score, c_score, p_logprob, c_logprob, [B, n] each."""
-    M = B * n
-    return [("pcount", B), ("ccount", B), ("p_len", M), ("c_len", M), ("c_slot", M), ("sent0", M * L), ("sent1", M * L), ("c_sent", B * (n + 1) * L)]
-
-
-DIVERSE_MAX_DRAWS = 256   # vc_diverse_rank: one workgroup of 256 lanes per image, one lane per draw
-
-
-def diverse_fields(B, K, L):
-    """(name, size) of the int32 result buffer of a diverse-captioning pass over B images x K draws, candidates of <= L tokens, in
-    buffer order (rows r = b*K + k).  The float64 buffer holds score [B, K] (rank order) then logprob [B*K] (row order)."""
-    M = B * K
-    return [("n_distinct", B), ("rep", M), ("count", M), ("ended", M), ("len", M), ("seq", M * L)]
-
-
-def diverse_from_host(ints, dbls, io, B, K, L, n_best=None, candidates=False):
-    """Per image the ranked distinct captions [(tokens, score, count), ...] of a pass from its result buffers (host copies).
-    ints: the int32 fields of diverse_fields at the offsets `io`: n_distinct [B]; rep / count [B, K] in rank order (rep = the draw whose
-    tokens represent the entry); ended / len [B*K] and seq [B*K, L] per candidate row.  dbls: score [B, K] in rank order, then logprob
-    [B*K] per row.  n_best: keep the first n_best entries of each image (None: all).  candidates=True also returns per image the K
-    candidates (tokens, logprob, ended) in draw order."""
-    M = B * K
-    small = ints[:io["seq"]].tolist()
-    nd = small[io["n_distinct"]:io["n_distinct"] + B]
-    rep, cnt = small[io["rep"]:io["rep"] + M], small[io["count"]:io["count"] + M]
-    ln, en = small[io["len"]:io["len"] + M], small[io["ended"]:io["ended"] + M]
-    seq = ints[io["seq"]:io["seq"] + M * L].tolist()
-    sc = dbls[:M].tolist()
-    res = []
-    for b in range(B):
-        n = nd[b] if n_best is None else min(nd[b], int(n_best))
-        out = []
-        for j in range(n):
-            r = b * K + rep[b * K + j]
-            out.append((seq[r * L:r * L + ln[r]], sc[b * K + j], cnt[b * K + j]))
-        res.append(out)
-    if not candidates:
-        return res
-    lp = dbls[M:2 * M].tolist()
-    cands = [[(seq[r * L:r * L + ln[r]], lp[r], bool(en[r])) for r in range(b * K, (b + 1) * K)] for b in range(B)]
-    return res, cands
-
-
-SCORE_MAX_TOKENS = 256   # score(): tokens scored per caption (human captions may be longer than gen_max_len)
-
-
-def rerank_by_marginal(entries, marginals, eos, len_norm_f):
-    """diverse(rerank="marginal"): entries [(tokens, score, count), ...] in likelihood order and their marginals ->
-    [(tokens, marginal / (1 + n)**len_norm_f, count, marginal), ...]: <EOS>-ended before cut captions, then the new score descending;
-    exact ties keep the likelihood order (a stable sort)."""
-    new = [(t, m / (1 + len(t)) ** len_norm_f, n, m) for (t, _, n), m in zip(entries, marginals)]
-    return sorted(new, key=lambda x: (not (len(x[0]) > 0 and x[0][-1] == eos), -x[1]))
-
-
-def sbs_weights(logprobs, kappa):
-    """Importance weights of a stochastic beam search's captions (Kool et al. 2019, section 4.2), float64: with phi their
-    log-probabilities and kappa the (n+1)-th largest perturbed score, q_i = P(perturbed_i > kappa) = -expm1(-exp(phi_i - kappa)) (kappa =
-    -inf: 1), w_i = exp(phi_i) / q_i, norm_i = w_i / sum_j w_j.  Returns (w, norm)."""
-    phi = np.asarray(logprobs, np.float64)
-    with np.errstate(over="ignore"):
-        q = -np.expm1(-np.exp(phi - float(kappa)))
-    w = np.exp(phi) / q
-    return w, w / w.sum()
-
-
-def merge_groups(groups):
-    """diverse_beam_search's per-image result (a list of G lists of (tokens, score)) as ONE ranked list of distinct captions:
-    [(tokens, score, [groups that produced it]), ...], equal token sequences merged under their best score, score descending (ties
-    keep the order of first appearance: group by group, each best first)."""
-    best, order = {}, []
-    for g, beams in enumerate(groups):
-        for toks, score in beams:
-            key = tuple(toks)
-            if key not in best:
-                best[key] = [list(toks), score, [g]]
-                order.append(key)
-            else:
-                ent = best[key]
-                ent[1] = max(ent[1], score)
-                if g not in ent[2]:
-                    ent[2].append(g)
-    return sorted((tuple(best[k]) for k in order), key=lambda x: -x[1])
-
-
-def check_truncation(top_k, top_p, method="sample"):
-    """(top_k, top_p) of truncated sampling as (int, float); ValueError for values outside top_k >= 0, 0 < top_p <= 1 and for a
-    truncation asked of a greedy decode (it has no draw to truncate).  (0, 1.0) = off."""
-    if isinstance(top_k, bool) or int(top_k) != top_k or int(top_k) < 0:
-        raise ValueError("top_k must be an integer >= 0 (0 = off; got %r)" % (top_k,))
-    top_p = float(top_p)
-    if not (0.0 < top_p <= 1.0):
-        raise ValueError("top_p must be in (0, 1] (1 = off; got %r)" % (top_p,))
-    if top_p < 1.0 and float(np.float32(top_p)) >= 1.0:
-        raise ValueError("top_p = %r is 1 in float32: pass 1.0 for no nucleus cut" % (top_p,))
-    if method != "sample" and (int(top_k) != 0 or top_p != 1.0):
-        raise ValueError("top_k / top_p truncate the draw of method='sample'; method=%r has none" % (method,))
-    return int(top_k), top_p
-
-
-CBS_MAX_SETS, CBS_MAX_WORDS = 3, 4   # constrained beam search: constraints per image, words per constraint (vc_beam_update_constrained)
-
-
-def check_constraints(constraints, B, V, bos, eos, beam_size):
-    """constrained_beam_search's `constraints` (per image a list of at most 3 lists of 1..4 token ids) as the call's table:
-    (C, Wc, cons [B, C, Wc] int32 padded with -1, NW = the largest number of constraint words of an image).  C and Wc are the call's
-    largest; an image with fewer sets has all -1 sets behind its own.  ValueError for more than 3 sets, a set of more than 4 words or of
-    none, overlapping sets, ids outside [0, V), a set holding bos or eos, or beam_size << C > 16."""
-    if len(constraints) != B:
-        raise ValueError("constrained_beam_search: %d constraint lists for %d images" % (len(constraints), B))
-    w = int(beam_size)
-    C = Wc = NW = 0
-    for b, sets in enumerate(constraints):
-        if len(sets) > CBS_MAX_SETS:
-            raise ValueError("constrained_beam_search: image %d has %d constraints (at most %d)" % (b, len(sets), CBS_MAX_SETS))
-        seen = set()
-        for st in sets:
-            st = list(st)
-            if not 1 <= len(st) <= CBS_MAX_WORDS:
-                raise ValueError("constrained_beam_search: image %d has a constraint of %d words (1..%d)" % (b, len(st), CBS_MAX_WORDS))
-            for v in st:
-                if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < V:
-                    raise ValueError("constrained_beam_search: image %d: word id %r outside [0, %d)" % (b, v, V))
-                if int(v) in (int(bos), int(eos)):
-                    raise ValueError("constrained_beam_search: image %d: a constraint holds <BOS> or <EOS> (%d)" % (b, int(v)))
-                if int(v) in seen:
-                    raise ValueError("constrained_beam_search: image %d: word %d appears twice in its constraints (sets must be disjoint)" % (b, int(v)))
-                seen.add(int(v))
-            Wc = max(Wc, len(st))
-        C, NW = max(C, len(sets)), max(NW, len(seen))
-    if w < 1 or (w << C) > 16:
-        raise ValueError("constrained_beam_search: beam_size << constraints must be 1..16, got %d << %d" % (w, C))
-    cons = np.full((B, C, max(Wc, 1)), -1, np.int32)
-    for b, sets in enumerate(constraints):
-        for j, st in enumerate(sets):
-            cons[b, j, :len(st)] = [int(v) for v in st]
-    return C, max(Wc, 1), cons, NW
-
-
-def select_bank(banks, full, eos):
-    """constrained_beam_search's default result from an image's per-state lists of (sentence, score): the submasks of `full` (the
-    image's accepting state) with more satisfied constraints first, then the smaller mask; the first bank with a complete caption
-    gives the result, else the first with live beams.  -> (beams, state)."""
-    order = sorted((s for s in range(full + 1) if s & ~full == 0), key=lambda s: (-bin(s).count("1"), s))
-    for s in order:   # (a bank's list is its complete captions if it has any -- they end in <EOS> -- else its live beams, which never do)
-        if banks[s] and banks[s][0][0][-1] == eos:
-            return banks[s], s
-    for s in order:
-        if banks[s]:
-            return banks[s], s
-    return [], 0
+    def update_args(self, parity):
+        """the state pointers that end vc_beam_update's (_groups', _constrained's) arguments in a round that reads sent[parity]"""
+        i, d = self.i, self.d
+        return (P(i["pcount"]), P(i["ccount"]), P(d["p_score"]), P(d["p_logprob"]), P(i["p_len"]), P(self.sent[parity]), P(self.sent[1 - parity]),
+                P(d["c_score"]), P(d["c_logprob"]), P(i["c_len"]), P(i["c_slot"]), P(self.c_free), P(i["c_sent"]), P(self.parent), P(self.tok))
 
 
 class CaptionGenerator(object):
@@ -369,6 +209,7 @@ class CaptionGenerator(object):
                     lib.vc_fill_f32(st, P(mean), mean.numel(), 0.0)
                 lib.vc_fill_f32(st, P(std), std.numel(), float(p.std))
                 lib.vc_latent_sample_f32(st, 1, B * Sm, L, P(mean), P(std), P(epsd), P(z))  # decoder.py:72-74
+                # (not _z_step: here z is row n_init - 1 of X, inside the ONE sequence call below -- a step of its own would be another launch)
                 e.gemm(0, 0, B, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, im.X[n_init - 1], E, S.param("decoder/net/z_rnn/bias"), tag=tg)
             im.lstm(st)
 
@@ -376,6 +217,32 @@ class CaptionGenerator(object):
                               tensors=[im.feats, im.X, im.cv, epsd, mean, std, z, im.act, im.cs, im.hs, im.lens] + ([pmd] if have_pm else []))
         self._replay_or_capture(key, launches)
         return im.cs[n_init], im.hs[n_init]
+
+    def _z_step(self, tag, rows):
+        """The z step of `rows` decoder rows (decoder.py:111): persistent z [rows, S, L], Xz, act1 (None without z) and the state pair cs1 / hs1
+        [2, rows, H] -- the caller tiles or gathers the image states into [0] and fills z with its own latent kernel -- the workspace
+        request, and run(st, tg): the z_rnn product and the ONE LSTM step from [0] to [1]."""
+        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        E, Hd, L, Sm = p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples
+        zs = types.SimpleNamespace(z=None, Xz=None, act1=None, ones=self._ones_for(rows))
+        if e.enc:
+            zs.z, zs.Xz, zs.act1 = self._b(tag + "z", (rows, Sm, L)), self._b(tag + "Xz", (1, rows, E)), self._b(tag + "act1", (1, rows, 4 * Hd))
+        zs.cs1, zs.hs1 = self._b(tag + "cs1", (2, rows, Hd)), self._b(tag + "hs1", (2, rows, Hd))
+        e._need_ws(lib.vc_lstm_seq_workspace_bytes(1, rows, E, Hd))
+
+        def run(st, tg):
+            e.gemm(0, 0, rows, E, Sm * L, zs.z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, zs.Xz[0], E, S.param("decoder/net/z_rnn/bias"), tag=tg)
+            lib.vc_lstm_seq_fwd_f32(st, 1, rows, E, Hd, P(zs.Xz), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")),
+                                    P(zs.ones), P(zs.act1), P(zs.cs1), P(zs.hs1), P(e.ws), e.ws_bytes, e.lstm_flags)
+
+        zs.run = run
+        return zs
+
+    def _xproj_for(self, rows, rounds):
+        """_project_vocab's table for a decode of rows x rounds word lookups, or None when they are fewer than the V rows of the one product
+        that makes it (or H is no multiple of 4: the gather moves float4s).  VC_DECODE_XPROJ=0: never (A/B runs)."""
+        pays = rows * rounds >= self.e.V and self.p.decoder_hidden % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0"
+        return self._project_vocab() if pays else None
 
     # ------------------------------------------------------------------ one decoder step
     def _round_bufs(self, tag, M):
@@ -564,32 +431,50 @@ class CaptionGenerator(object):
                                         P(done) if done is not None else None, ctl.no_repeat_ngram, ctl.min_len, int(eos),
                                         ctl.repetition_penalty, P(table) if n else None, n)
 
+    def _candidates(self, tag, rows, max_len):
+        """The candidate a round's pick keeps per row (the history the controls read) in persistent buffers: seq [rows, max_len], len, ended
+        [rows] int32, logprob [rows] float64.  (diverse() keeps the same four inside its result buffers.)"""
+        i32 = torch.int32
+        return types.SimpleNamespace(seq=self._b(tag + "seq", (rows, max_len), i32), len=self._b(tag + "len", (rows,), i32),
+                                     ended=self._b(tag + "ended", (rows,), i32), logprob=self._b(tag + "lp", (rows,), torch.float64))
+
+    def _pick(self, logits, rows, cand, tok, eos, temp=1.0, u=None, u_ld=1, rnd=None, top_k=0, top_p=1.0):
+        """A round's pick from its logits [rows, V] into tok and the rows' candidates: the argmax (u None) or the inverse-CDF draw at u
+        [.., u_ld] (row `rnd` of it, a device counter, or row 0) from softmax(logits / temp), truncated to top_k / top_p when asked."""
+        V, c = self.e.V, cand
+        if top_k != 0 or top_p != 1.0:
+            self.lib.vc_decode_pick_trunc_f32(_stream(), P(logits), rows, V, V, temp, top_k, top_p, P(u), u_ld, P(rnd), int(eos), P(tok), P(c.ended),
+                                              P(c.seq), c.seq.shape[1], P(c.len), P(c.logprob), None)
+        else:
+            self.lib.vc_decode_pick_f32(_stream(), P(logits), rows, V, V, temp, P(u), u_ld, P(rnd), int(eos), P(tok), P(c.ended), P(c.seq), c.seq.shape[1],
+                                        P(c.len), P(c.logprob))
+
     def _greedy_controls(self, ctl, features, c_v, eps, bos, eos, max_len, check_every):
-        """greedy() under decoding controls: the rounds keep a candidate per row (diverse()'s bookkeeping: seq, len, ended), which is
-        the history the controls read, and pick with vc_decode_pick_f32 (argmax) -- still hipGraph chunks of check_every rounds."""
-        lib, e = self.lib, self.e
+        """greedy() under decoding controls: the rounds keep a candidate per row, which is the history the controls read, and pick with
+        vc_decode_pick_f32 (argmax) -- still hipGraph chunks of check_every rounds."""
+        lib = self.lib
         c0, h0 = self.init_state(features, c_v, eps)
-        B, V, i32 = int(c0.shape[0]), e.V, torch.int32
+        B = int(c0.shape[0])
         tag = "gc%d_%d_" % (B, max_len)
-        seq, ln, ended = self._b(tag + "seq", (B, max_len), i32), self._b(tag + "len", (B,), i32), self._b(tag + "ended", (B,), i32)
-        tok, logprob, pending = self._b(tag + "tok", (B,), i32), self._b(tag + "lp", (B,), torch.float64), self._b(tag + "pending", (1,))
+        cand = self._candidates(tag, B, max_len)
+        tok, pending = self._b(tag + "tok", (B,), torch.int32), self._b(tag + "pending", (1,))
         table = self._controls_table(tag, ctl)
         sets, state = self._round_state(tag, B, c0, h0)
 
         def reset():
-            tok.fill_(bos); ended.zero_(); ln.zero_(); logprob.zero_()
+            tok.fill_(bos); cand.ended.zero_(); cand.len.zero_(); cand.logprob.zero_()
 
         def one(r, timed):
             src, dst = sets(r)
             logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
-            self._apply_controls(ctl, table, logits, B, seq, max_len, 0, ln, ended, eos)
-            lib.vc_decode_pick_f32(_stream(), P(logits), B, V, V, 1.0, None, 1, None, int(eos), P(tok), P(ended), P(seq), max_len, P(ln), P(logprob))
-            lib.vc_decode_round_end_i32(_stream(), P(ended), B, P(pending), None)
+            self._apply_controls(ctl, table, logits, B, cand.seq, max_len, 0, cand.len, cand.ended, eos)
+            self._pick(logits, B, cand, tok, eos)
+            lib.vc_decode_round_end_i32(_stream(), P(cand.ended), B, P(pending), None)
 
         K = self._chunk_rounds(check_every)
-        self._run_chunks(("greedy_controls", B, K, max_len, int(eos)) + ctl.key(), [seq, ln, ended, tok, logprob, pending, table] + state,
+        self._run_chunks(("greedy_controls", B, K, max_len, int(eos)) + ctl.key(), [cand.seq, cand.len, cand.ended, tok, cand.logprob, pending, table] + state,
                          one, reset, K, max_len, check_every, pending)
-        rows, lens = seq.cpu().numpy(), ln.cpu().numpy()
+        rows, lens = cand.seq.cpu().numpy(), cand.len.cpu().numpy()
         return [rows[b, :lens[b]].tolist() for b in range(B)]
 
     # ------------------------------------------------------------------ greedy (online_inference)
@@ -612,9 +497,8 @@ class CaptionGenerator(object):
         controls"): every round's logits are processed from the row's words so far before the argmax.  None or a no-op value: this path."""
         lib, e = self.lib, self.e
         max_len = max_len or self.p.gen_max_len
-        ctl = active_controls(controls)
+        ctl = self._checked_controls(controls, eos, max_len)
         if ctl is not None:
-            ctl.check(e.V, eos, max_len)
             return self._greedy_controls(ctl, features, c_v, eps, bos, eos, int(max_len), check_every)
         c0, h0 = self.init_state(features, c_v, eps)
         B, V = c0.shape[0], e.V
@@ -649,9 +533,7 @@ class CaptionGenerator(object):
         rows' candidates are then always kept, and an untruncated draw is vc_decode_pick_f32's (vc_multinomial_rows_f32's token)."""
         top_k, top_p = check_truncation(top_k, top_p)
         max_len = max_len or self.p.gen_max_len
-        ctl = active_controls(controls)
-        if ctl is not None:
-            ctl.check(self.e.V, eos, max_len)
+        ctl = self._checked_controls(controls, eos, max_len)
         c, h = self.init_state(features, c_v, eps)
         B = c.shape[0]
         tok = torch.full((B,), bos, dtype=torch.int32, device=self.e.dev)
@@ -660,27 +542,21 @@ class CaptionGenerator(object):
         ud = self._dev(uniforms, np.float32) if uniforms is not None else None
         steps = 0
         trunc = top_k != 0 or top_p != 1.0
-        if trunc or ctl is not None:   # the entry keeps a candidate per row (diverse()'s bookkeeping): scratch here, the ids are what sample() returns
-            i32 = torch.int32
-            t_done, t_len, t_seq = self._b("st_done", (B,), i32), self._b("st_len", (B,), i32), self._b("st_seq", (B, max_len), i32)
-            t_lp = self._b("st_lp", (B,), torch.float64)
-            t_done.zero_(); t_len.zero_(); t_lp.zero_()
+        if trunc or ctl is not None:   # the pick keeps a candidate per row: scratch here, the ids are what sample() returns
+            cand = self._candidates("st_", B, max_len)
+            cand.ended.zero_(); cand.len.zero_(); cand.logprob.zero_()
             table = self._controls_table("st_", ctl) if ctl is not None else None
         for it in range(max_len):
             logits, c, h = self.step(tok, c, h, want="logits")
             if ctl is not None:
-                self._apply_controls(ctl, table, logits, B, t_seq, max_len, 0, t_len, t_done, eos)
+                self._apply_controls(ctl, table, logits, B, cand.seq, max_len, 0, cand.len, cand.ended, eos)
             if ud is not None:
                 u = ud[it]
             else:
                 self.lib.vc_philox_uniform_f32(_stream(), P(u), B, self.e.seed * 1000003 + 29, (16 + it) << 32, P(self.e.step))
             tok = ids[it]
-            if trunc:
-                self.lib.vc_decode_pick_trunc_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), top_k, top_p, P(u), 1,
-                                                  None, int(eos), P(tok), P(t_done), P(t_seq), max_len, P(t_len), P(t_lp), None)
-            elif ctl is not None:
-                self.lib.vc_decode_pick_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), 1, None, int(eos), P(tok),
-                                            P(t_done), P(t_seq), max_len, P(t_len), P(t_lp))
+            if trunc or ctl is not None:
+                self._pick(logits, B, cand, tok, eos, float(self.p.temperature), u, 1, None, top_k, top_p)
             else:
                 self.lib.vc_multinomial_rows_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), P(tok))
             steps = it + 1
@@ -694,25 +570,18 @@ class CaptionGenerator(object):
         eps[k][:, None]) would give it: imf_emb, cv_emb and the LSTM steps before the z step run on the B image rows; their state is
         tiled to B*K rows and only the draws (vc_diverse_latent_f32: no [rows*S, L] mean / std tensors), the z_rnn product and the z
         step run on B*K rows.  eps: [K, S, B, L] or None (Philox on device).  One hipGraph from the second call of a shape on."""
-        e, p, lib, S = self.e, self.p, self.lib, self.e.store
+        e, p, lib = self.e, self.p, self.lib
         B = int(features.shape[0])
         M = B * K
-        E, Hd, L, Sm = p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples
+        Hd, L, Sm = p.decoder_hidden, p.latent_size, p.gen_z_samples
         n_pre = e.n_init_d - int(e.enc)   # steps that depend on the image only
         tag = "dvi%d_%d_" % (B, K)
         im = self._image_rows(tag, n_pre, features, c_v, M)
         pmd, cs0, hs0 = im.pmd, im.cs, im.hs
-        epsd = z = Xz = act1 = None
-        if e.enc:
-            z, Xz = self._b(tag + "z", (M, Sm, L)), self._b(tag + "Xz", (1, M, E))
-            if eps is not None:
-                epsd = self._b(tag + "eps", (M, Sm, L))
-                self._load(epsd, np.transpose(np.asarray(eps, np.float32), (2, 0, 1, 3)))   # [K, S, B, L] -> rows b*K + k
-            act1 = self._b(tag + "act1", (1, M, 4 * Hd))
-        cs1, hs1 = self._b(tag + "cs1", (2, M, Hd)), self._b(tag + "hs1", (2, M, Hd))
-        ones = self._ones_for(M)
-        e._need_ws(lib.vc_lstm_seq_workspace_bytes(1, M, E, Hd))
-        W, bias = S.param(spec.DEC_CELL + "kernel"), S.param(spec.DEC_CELL + "bias")
+        zs = self._z_step(tag, M)
+        cs1, hs1, epsd = zs.cs1, zs.hs1, None
+        if e.enc and eps is not None:
+            epsd = self._load(self._b(tag + "eps", (M, Sm, L)), np.transpose(np.asarray(eps, np.float32), (2, 0, 1, 3)))   # [K, S, B, L] -> rows b*K + k
 
         def launches(timed):
             st, tg = _stream(), ("gemm" if timed else None)
@@ -722,13 +591,11 @@ class CaptionGenerator(object):
             lib.vc_tile_rows_f32(st, P(cs0[n_pre]), B, K, Hd, P(dst[0]))
             lib.vc_tile_rows_f32(st, P(hs0[n_pre]), B, K, Hd, P(dst[1]))
             if e.enc:   # decoder.py:72-74 and 111, per draw
-                lib.vc_diverse_latent_f32(st, M, K, Sm, L, P(pmd) if pmd is not None else None, float(p.std), P(epsd) if epsd is not None else None,
-                                          e.seed * 1000003 + 17, 6 << 32, P(e.step), P(z))
-                e.gemm(0, 0, M, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, Xz[0], E, S.param("decoder/net/z_rnn/bias"), tag=tg)
-                lib.vc_lstm_seq_fwd_f32(st, 1, M, E, Hd, P(Xz), P(W), P(bias), P(ones), P(act1), P(cs1), P(hs1), P(e.ws), e.ws_bytes, e.lstm_flags)
+                lib.vc_diverse_latent_f32(st, M, K, Sm, L, P(pmd), float(p.std), P(epsd), e.seed * 1000003 + 17, 6 << 32, P(e.step), P(zs.z))
+                zs.run(st, tg)
 
         key = self._graph_key("dvinit", B, K, eps is None, pmd is not None, float(p.std), e.lstm_flags, e.seed,
-                              tensors=[im.feats, im.X, im.cv, epsd, z, Xz, pmd, im.act, act1, cs0, hs0, cs1, hs1, im.lens, ones])
+                              tensors=[im.feats, im.X, im.cv, epsd, zs.z, zs.Xz, pmd, im.act, zs.act1, cs0, hs0, cs1, hs1, im.lens, zs.ones])
         self._replay_or_capture(key, launches)
         return cs1[1], hs1[1]
 
@@ -738,13 +605,14 @@ class CaptionGenerator(object):
         results in two flat buffers brought back by two copies into pinned memory."""
         lib, e, p = self.lib, self.e, self.p
         c0, h0 = self._diverse_init(features, c_v, eps, K)
-        M, V = int(c0.shape[0]), e.V
+        M = int(c0.shape[0])
         B = M // K
         i32 = torch.int32
         tag = "dv%d_%d_%d_" % (B, K, max_len)
         lay, dlay = FieldLayout(diverse_fields(B, K, max_len)), FieldLayout([("score", M), ("logprob", M)])
         ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), torch.float64)
         f, (score, logprob) = lay.views(ibuf), dlay.views(dbuf).values()
+        cand = types.SimpleNamespace(seq=f["seq"].view(M, max_len), len=f["len"], ended=f["ended"], logprob=logprob)
         tok, rnd, pending = self._b(tag + "tok", (M,), i32), self._b(tag + "round", (1,), i32), self._b(tag + "pending", (1,))
         ud = None
         if method == "sample":
@@ -754,11 +622,10 @@ class CaptionGenerator(object):
             else:
                 lib.vc_philox_uniform_f32(_stream(), P(ud), ud.numel(), e.seed * 1000003 + 29, 7 << 32, P(e.step))
         temp = float(p.temperature) if method == "sample" else 1.0
-        trunc = top_k != 0 or top_p != 1.0
         table = self._controls_table(tag, ctl) if ctl is not None else None
 
         def reset():
-            tok.fill_(bos); f["ended"].zero_(); f["len"].zero_(); logprob.zero_(); rnd.zero_()
+            tok.fill_(bos); cand.ended.zero_(); cand.len.zero_(); cand.logprob.zero_(); rnd.zero_()
 
         sets, state = self._round_state(tag, M, c0, h0)
 
@@ -766,19 +633,14 @@ class CaptionGenerator(object):
             src, dst = sets(r)
             logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
             if ctl is not None:   # the candidates so far are the histories
-                self._apply_controls(ctl, table, logits, M, f["seq"], max_len, 0, f["len"], f["ended"], eos)
-            if trunc:
-                lib.vc_decode_pick_trunc_f32(_stream(), P(logits), M, V, V, temp, top_k, top_p, P(ud), max_len, P(rnd), int(eos), P(tok),
-                                             P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob), None)
-            else:
-                lib.vc_decode_pick_f32(_stream(), P(logits), M, V, V, temp, P(ud) if ud is not None else None, max_len, P(rnd), int(eos), P(tok),
-                                       P(f["ended"]), P(f["seq"]), max_len, P(f["len"]), P(logprob))
-            lib.vc_decode_round_end_i32(_stream(), P(f["ended"]), M, P(pending), P(rnd))
+                self._apply_controls(ctl, table, logits, M, cand.seq, max_len, 0, cand.len, cand.ended, eos)
+            self._pick(logits, M, cand, tok, eos, temp, ud, max_len, rnd, top_k, top_p)
+            lib.vc_decode_round_end_i32(_stream(), P(cand.ended), M, P(pending), P(rnd))
 
         Kc = self._chunk_rounds(check_every)
         self._run_chunks(("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p) + (ctl.key() if ctl is not None else ()),   # (a captured chunk bakes the truncation and the controls)
                          [tok, rnd, pending, ibuf, dbuf, ud] + ([table] if ctl is not None else []) + state, one, reset, Kc, max_len, check_every, pending)
-        lib.vc_diverse_rank(_stream(), M, B, K, max_len, P(f["seq"]), P(f["len"]), P(f["ended"]), P(logprob), float(len_norm_f),
+        lib.vc_diverse_rank(_stream(), M, B, K, max_len, P(cand.seq), P(cand.len), P(cand.ended), P(logprob), float(len_norm_f),
                             P(f["n_distinct"]), P(f["rep"]), P(f["count"]), P(score))
         res, cands = diverse_from_host(*self._to_host(tag, ibuf, dbuf), lay.off, B, K, max_len, n_best if rerank != "marginal" else None, candidates=True)
         if rerank != "marginal":
@@ -886,9 +748,7 @@ class CaptionGenerator(object):
         K, B = int(draws), int(features.shape[0])
         self._check_draws(K, eps, B)
         caps = self._caption_lists(captions, B, bos)
-        if c_v is not None:
-            c_v = np.asarray(c_v)
-        eps = np.asarray(eps) if eps is not None else None
+        c_v, eps = (np.asarray(a) if a is not None else None for a in (c_v, eps))
         res = []
         for g0, g1, rows, steps in self._passes(caps, K, self.score_rows):
             sl = slice(g0, g1)
@@ -896,7 +756,7 @@ class CaptionGenerator(object):
                 lp, marg = np.zeros((rows // K, K), np.float64), np.zeros((rows // K,), np.float64)
             else:
                 self._t_score = _phase("", 0.0)
-                c0, h0 = self._diverse_init(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None, K)
+                c0, h0 = self._diverse_init(features[sl], _cut(c_v, sl), _cut(eps, sl, 2), K)
                 lp, marg = self._score_states(c0, h0, K, caps[sl], bos)
             o = 0
             for b in range(g0, g1):
@@ -1039,8 +899,7 @@ class CaptionGenerator(object):
         for g0, g1, rows, _ in self._passes(caps, 1, self.bound_rows):
             if rows:
                 sl = slice(g0, g1)
-                mean, std, _, _ = self._encode_pass(features[sl], c_v[sl] if c_v is not None else None, caps[sl],
-                                                 gmm_idx[o:o + rows] if gmm_idx is not None else None)
+                mean, std, _, _ = self._encode_pass(features[sl], _cut(c_v, sl), caps[sl], _cut(gmm_idx, slice(o, o + rows)))
                 mean, std = mean.cpu().numpy(), std.cpu().numpy()
             j = 0
             for b in range(g0, g1):
@@ -1053,8 +912,8 @@ class CaptionGenerator(object):
         """One pass of bound() over the C > 0 captions of B images: float64 host arrays logprob, logw [C, K], out [C, 5] (elbo, iwae, rec,
         kl_mc, ess) and kl [C] from ONE copy-back, plus with return_latents (mean, std [C, L], z [C, K, S, L]) as float32 host arrays.
         eps: [K, S, C, L] or None (Philox on device)."""
-        e, p, lib, S = self.e, self.p, self.lib, self.e.store
-        B, E, Hd, L, Sm = int(features.shape[0]), p.embed_size, p.decoder_hidden, p.latent_size, p.gen_z_samples
+        e, p, lib = self.e, self.p, self.lib
+        Hd, L, Sm = p.decoder_hidden, p.latent_size, p.gen_z_samples
         t_ph = _phase("", 0.0)
         mean, std, img, h_img = self._encode_pass(features, c_v, caps, gmm_idx)
         t_ph = _phase("bound: encoder", t_ph)
@@ -1063,9 +922,8 @@ class CaptionGenerator(object):
         n_pre = e.n_init_d - 1   # the decoder's steps that depend on the image only
         tag = "bd_"
         im = self._image_rows(tag, n_pre, features, c_v, N)
-        z, Xz, act1 = self._b("bd_z", (N, Sm, L)), self._b("bd_Xz", (1, N, E)), self._b("bd_act1", (1, N, 4 * Hd))
-        cs1, hs1 = self._b("bd_cs1", (2, N, Hd)), self._b("bd_hs1", (2, N, Hd))
-        epsd = None
+        zs = self._z_step(tag, N)
+        z, cs1, hs1, epsd = zs.z, zs.cs1, zs.hs1, None
         if eps is not None:
             epsd = self._load(self._b("bd_eps", (N, Sm, L)), np.transpose(np.asarray(eps, np.float32), (2, 0, 1, 3)))   # [K, S, C, L] -> rows c*K + k
         rowimg = self._b(tag + "rowimg", (N,), torch.int32)
@@ -1073,7 +931,6 @@ class CaptionGenerator(object):
         dlay = FieldLayout([("logprob", N), ("logw", N), ("out", 5 * C), ("kl", C)])
         dbuf = self._b(tag + "dbuf", (dlay.total,), torch.float64)
         logprob, logw, out, kl = dlay.views(dbuf).values()
-        e._need_ws(lib.vc_lstm_seq_workspace_bytes(1, N, E, Hd))
         st = _stream()
         im.embed("gemm")
         im.lstm(st)
@@ -1081,9 +938,7 @@ class CaptionGenerator(object):
         pm_args = (P(im.pmd), P(img)) if im.pmd is not None else (None, None)
         lib.vc_posterior_latent_f32(st, N, K, Sm, L, P(mean), P(std), pm_args[0], pm_args[1], float(p.std), P(epsd), e.seed * 1000003 + 17,
                                     8 << 32, P(e.step), P(z), P(logw))
-        e.gemm(0, 0, N, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, Xz[0], E, S.param("decoder/net/z_rnn/bias"))
-        lib.vc_lstm_seq_fwd_f32(st, 1, N, E, Hd, P(Xz), P(S.param(spec.DEC_CELL + "kernel")), P(S.param(spec.DEC_CELL + "bias")),
-                                P(self._ones_for(N)), P(act1), P(cs1), P(hs1), P(e.ws), e.ws_bytes, e.lstm_flags)
+        zs.run(st, "gemm")
         self._t_score = _phase("bound: posterior draws, z step", t_ph)
         tf = self._teacher_force(cs1[1], hs1[1], K, caps, bos, own_rows=True)
         lib.vc_bound_reduce_f64(st, P(tf.lp), tf.T, C, K, P(tf.clen), P(logw), P(logprob), P(out))
@@ -1118,9 +973,8 @@ class CaptionGenerator(object):
             n = rows // K
             if n:
                 sl = slice(g0, g1)
-                lp, lw, out, kl, lat = self._bound_pass(features[sl], c_v[sl] if c_v is not None else None, caps[sl],
-                                                        gmm_idx[o:o + n] if gmm_idx is not None else None,
-                                                        eps[:, :, o:o + n] if eps is not None else None, K, bos, return_latents)
+                own = slice(o, o + n)   # (gmm_idx and eps are per caption)
+                lp, lw, out, kl, lat = self._bound_pass(features[sl], _cut(c_v, sl), caps[sl], _cut(gmm_idx, own), _cut(eps, own, 2), K, bos, return_latents)
             j = 0
             for b in range(g0, g1):
                 recs = []
@@ -1168,20 +1022,14 @@ class CaptionGenerator(object):
             raise ValueError("rerank must be 'likelihood' or 'marginal' (got %r)" % (rerank,))
         top_k, top_p = check_truncation(top_k, top_p, method)
         max_len = int(max_len or self.p.gen_max_len)
-        ctl = active_controls(controls)
-        if ctl is not None:
-            ctl.check(self.e.V, eos, max_len)
+        ctl = self._checked_controls(controls, eos, max_len)
         if uniforms is not None and tuple(np.shape(uniforms)) != (K, max_len, B):
             raise ValueError("uniforms must be [draws, max_len, images] = %s" % ((K, max_len, B),))
-        if c_v is not None:
-            c_v = np.asarray(c_v)
-        G = max(1, self.diverse_rows // K)
+        c_v, eps, uniforms = (np.asarray(a) if a is not None else None for a in (c_v, eps, uniforms))
         res, cands = [], []
-        for g0 in range(0, B, G):
-            sl = slice(g0, min(B, g0 + G))
-            r, c = self._diverse_pass(features[sl], c_v[sl] if c_v is not None else None, np.asarray(eps)[:, :, sl] if eps is not None else None,
-                                      K, method, bos, eos, max_len, len_norm_f, n_best,
-                                      np.asarray(uniforms)[:, :, sl] if uniforms is not None else None, check_every, rerank, top_k, top_p, ctl)
+        for sl in self._marginal_passes(B, K):
+            r, c = self._diverse_pass(features[sl], _cut(c_v, sl), _cut(eps, sl, 2), K, method, bos, eos, max_len, len_norm_f, n_best,
+                                      _cut(uniforms, sl, 2), check_every, rerank, top_k, top_p, ctl)
             res += r
             cands += c
         self.last_candidates = cands
@@ -1194,8 +1042,8 @@ class CaptionGenerator(object):
         return self._b(tag + "mixws", (nbytes // 4,), torch.int32), nbytes
 
     def _marginal_passes(self, B, rows_per_image):
-        """diverse()'s cut for marginal decoding: slices of images whose rows together stay within diverse_rows; an image that exceeds
-        the cap alone gets a pass of its own"""
+        """The passes of diverse() and of marginal decoding: slices of images whose rows together stay within diverse_rows; an image that
+        exceeds the cap alone gets a pass of its own"""
         G = max(1, self.diverse_rows // rows_per_image)
         return [slice(g0, min(B, g0 + G)) for g0 in range(0, B, G)]
 
@@ -1231,12 +1079,7 @@ class CaptionGenerator(object):
         Kc = self._chunk_rounds(check_every)
         steps = self._run_chunks(("marginal_greedy", B, K, Kc, max_len, int(eos)), [tok_rows, tok, tv, stat, pending, ibuf, dbuf, ws] + state,
                                  one, reset, Kc, max_len, check_every, pending)
-        ints, dbls = self._to_host(tag, ibuf, dbuf)
-        lw = dbls[(steps % 2) * M:(steps % 2 + 1) * M].reshape(B, K).copy()   # the buffer the last round wrote
-        mx = lw.max(axis=1)
-        marg = mx + np.log(np.exp(lw - mx[:, None]).sum(axis=1)) - np.log(K)
-        ln, seq = ints[lay.off["len"]:lay.off["len"] + B].tolist(), ints[lay.off["seq"]:].tolist()
-        return [{"tokens": seq[b * max_len:b * max_len + ln[b]], "marginal": float(marg[b]), "logprob": lw[b]} for b in range(B)]
+        return marginal_greedy_from_host(*self._to_host(tag, ibuf, dbuf), lay.off, B, K, max_len, steps)
 
     def marginal_greedy(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, max_len=None, check_every=4):
         """Greedy decoding under the K-draw mixture p(y | I) ~ 1/K sum_k p(y | z_k, I) (DESIGN.md "Marginal decoding"): per image
@@ -1252,12 +1095,10 @@ class CaptionGenerator(object):
         K, B = int(draws), int(features.shape[0])
         self._check_draws(K, eps, B)
         max_len = int(max_len or self.p.gen_max_len)
-        c_v = np.asarray(c_v) if c_v is not None else None
-        eps = np.asarray(eps) if eps is not None else None
+        c_v, eps = (np.asarray(a) if a is not None else None for a in (c_v, eps))
         res = []
         for sl in self._marginal_passes(B, K):
-            res += self._marginal_greedy_pass(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None,
-                                              K, bos, eos, max_len, check_every)
+            res += self._marginal_greedy_pass(features[sl], _cut(c_v, sl), _cut(eps, sl, 2), K, bos, eos, max_len, check_every)
         return res
 
     def _marginal_beam_pass(self, features, c_v, eps, K, n, bos, eos, max_len, len_norm_f, check_every):
@@ -1269,21 +1110,15 @@ class CaptionGenerator(object):
         B = BK // K
         G = B * n
         M = G * K
-        i32, f64 = torch.int32, torch.float64
+        i32 = torch.int32
         tok0 = self._b("mb_tok0_%d" % BK, (BK,), i32)
         tok0.fill_(bos)
         _, c1, h1 = self.step(tok0, c0, h0, want="state", bufs=self._round_bufs("mb0_%d_" % BK, BK))   # decoder.py:230-236: the state only
         L, rounds = max_len + 2, max_len - 1
-        xproj = self._project_vocab() if (M * rounds >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
+        xproj = self._xproj_for(M, rounds)
         tag = "mb%d_%d_%d_%d_" % (B, K, n, L)
-        lay = FieldLayout(beam_fields(B, n, L))
-        dlay = FieldLayout([(k_, G) for k_ in ("p_score", "c_score", "p_logprob", "c_logprob")] + [("logw0", M), ("logw1", M)])
-        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), f64)
-        iv, dv = lay.views(ibuf), dlay.views(dbuf)
-        pcount, ccount, p_len, c_len, c_slot = (iv[k_] for k_ in ("pcount", "ccount", "p_len", "c_len", "c_slot"))
-        sent, c_sent = [iv["sent0"], iv["sent1"]], iv["c_sent"]
-        p_score, c_score, p_logprob, c_logprob, logw = dv["p_score"], dv["c_score"], dv["p_logprob"], dv["c_logprob"], [dv["logw0"], dv["logw1"]]
-        c_free, parent, tok = self._b(tag + "c_free", (B,), i32), self._b(tag + "parent", (G,), i32), self._b(tag + "tok", (G,), i32)
+        bs = _BeamSlice(self, tag, B, n, L, extra=[("logw0", M), ("logw1", M)])
+        logw, pcount = [bs.d["logw0"], bs.d["logw1"]], bs.i["pcount"]
         parent_rows, tok_rows, rows0 = self._b(tag + "parent_rows", (M,), i32), self._b(tag + "tok_rows", (M,), i32), self._b(tag + "rows0", (M,), i32)
         rows0.copy_(torch.arange(M, dtype=i32, device=e.dev))
         tv, ti, stat = self._b(tag + "tv", (G, n)), self._b(tag + "ti", (G, n), i32), self._b(tag + "stat", (M, 2))
@@ -1293,9 +1128,7 @@ class CaptionGenerator(object):
         self._pack_wh(M)
 
         def reset():   # vc_beam_init with H = K * Hd: group b*n + j starts from the K states of image b, i.e. row (b*n + j)*K + k from row b*K + k
-            lib.vc_beam_init(_stream(), B, n, L, int(bos), K * Hd, P(c1), P(h1), P(bufs["c2"]), P(bufs["h2"]), P(pcount), P(ccount), P(p_score),
-                             P(p_logprob), P(p_len), P(sent[0]), P(sent[1]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent),
-                             P(parent), P(tok))
+            bs.init(lib, bos, K * Hd, c1, h1, bufs["c2"], bufs["h2"])
             parent_rows.copy_(rows0); tok_rows.fill_(bos); logw[0].zero_(); logw[1].zero_()
 
         def one(it, timed):
@@ -1303,9 +1136,8 @@ class CaptionGenerator(object):
             lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent_rows), M, Hd, P(cg), P(hg), P(xproj), P(tok_rows), V, 4 * Hd, P(bufs["gact"]))
             logits, _, _ = self.step(tok_rows, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
             lib.vc_mixture_topk_f32(s_, P(logits), G, K, V, V, P(logw[par]), n, P(tv), P(ti), P(stat), P(ws), ws_bytes)
-            lib.vc_beam_update(s_, B, n, L, int(eos), float(len_norm_f), P(tv), P(ti), P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len),
-                               P(sent[par]), P(sent[1 - par]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
-            lib.vc_mixture_advance_f32(s_, P(logits), V, V, P(stat), G, K, P(parent), P(tok), P(logw[par]), P(logw[1 - par]), P(parent_rows),
+            lib.vc_beam_update(s_, B, n, L, int(eos), float(len_norm_f), P(tv), P(ti), *bs.update_args(par))
+            lib.vc_mixture_advance_f32(s_, P(logits), V, V, P(stat), G, K, P(bs.parent), P(bs.tok), P(logw[par]), P(logw[1 - par]), P(parent_rows),
                                        P(tok_rows), int(eos), None, None, 0, None)
 
         def count_alive(steps, k):
@@ -1315,12 +1147,11 @@ class CaptionGenerator(object):
         steps = 0
         if rounds > 0:
             steps = self._run_chunks(("marginal_beam", B, K, n, L, Kc, int(eos), float(len_norm_f)),
-                                     [ibuf, dbuf, c_free, parent, tok, parent_rows, tok_rows, tv, ti, stat, cg, hg, alive, ws, xproj, self._ones_for(M)]
+                                     bs.tensors + [parent_rows, tok_rows, tv, ti, stat, cg, hg, alive, ws, xproj, self._ones_for(M)]
                                      + list(bufs.values()), one, reset, Kc, rounds, check_every, alive, count_alive)
         else:
             reset()
-        ints, dbls = self._to_host(tag, ibuf, dbuf[:dlay.off["p_logprob"]])   # (the host reads the scores only)
-        return beams_from_host(ints, dbls, lay.off, B, n, L, steps & 1)
+        return beams_from_host(*self._to_host(tag, bs.ibuf, bs.scores), bs.lay.off, B, n, L, steps & 1)
 
     def marginal_beam_search(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, beam_size=2, max_len=None, len_norm_f=0.7,
                              check_every=4):
@@ -1337,12 +1168,10 @@ class CaptionGenerator(object):
         if not 1 <= n <= min(16, self.e.V):
             raise ValueError("marginal_beam_search: beam_size must be 1..16 and at most the vocabulary (got %d)" % n)
         max_len = int(max_len or self.p.gen_max_len)
-        c_v = np.asarray(c_v) if c_v is not None else None
-        eps = np.asarray(eps) if eps is not None else None
+        c_v, eps = (np.asarray(a) if a is not None else None for a in (c_v, eps))
         res = []
         for sl in self._marginal_passes(B, n * K):
-            res += self._marginal_beam_pass(features[sl], c_v[sl] if c_v is not None else None, eps[:, :, sl] if eps is not None else None,
-                                            K, n, bos, eos, max_len, len_norm_f, check_every)
+            res += self._marginal_beam_pass(features[sl], _cut(c_v, sl), _cut(eps, sl, 2), K, n, bos, eos, max_len, len_norm_f, check_every)
         return res
 
     # ------------------------------------------------------------------ beam search
@@ -1360,7 +1189,7 @@ class CaptionGenerator(object):
         lib, e = self.lib, self.e
         B, Hd, V = int(c.shape[0]), self.p.decoder_hidden, e.V
         M = B * n
-        i32, f64 = torch.int32, torch.float64
+        i32 = torch.int32
         tag = "bm%d_%d_%dof%d_" % (n, L, k, nparts)
         kc = n
         if groups is not None:
@@ -1371,26 +1200,13 @@ class CaptionGenerator(object):
             C, Wc, kc, table = cons
             S = 1 << C
             tag = "bmc%d_%d_%d_" % (C, Wc, kc) + tag
-        pt = types.SimpleNamespace(B=B, k=k)
-        # everything the host reads at the end lives in TWO flat buffers (int32 fields, float64 scores): two copies into pinned memory
-        # bring a slice's results back, with no gathering launches in between
-        lay, dlay = FieldLayout(beam_fields(B, n, L)), FieldLayout([(k_, M) for k_ in ("p_score", "c_score", "p_logprob", "c_logprob")])
-        ibuf, dbuf = self._b(tag + "ibuf", (lay.total,), i32), self._b(tag + "dbuf", (dlay.total,), f64)
-        iv = lay.views(ibuf)
-        pcount, ccount, p_len, c_len, c_slot = (iv[k_] for k_ in ("pcount", "ccount", "p_len", "c_len", "c_slot"))
-        sent, c_sent = [iv["sent0"].view(M, L), iv["sent1"].view(M, L)], iv["c_sent"].view(B * (n + 1), L)
-        p_score, c_score, p_logprob, c_logprob = dlay.views(dbuf).values()
-        c_free = self._b(tag + "c_free", (B,), i32)
-        parent, tok = self._b(tag + "parent", (M,), i32), self._b(tag + "tok", (M,), i32)
+        bs = _BeamSlice(self, tag, B, n, L)
+        pt = types.SimpleNamespace(B=B, k=k, tag=tag, state=bs)
+        pcount, p_len, sent, tok = bs.i["pcount"], bs.i["p_len"], bs.sent, bs.tok
         tv, ti = self._b(tag + "tv", (M, kc)), self._b(tag + "ti", (M, kc), i32)
         bufs = self._round_bufs(tag, M)
-        # re-initialised per call: partial = [Beam([bos], state b, 0.0, 0.0)], and every row starts from its image's state (the [B, Hd]
-        # state expanded to the M rows, parent = identity) -- one launch
-        lib.vc_beam_init(_stream(), B, n, L, int(bos), Hd, P(c), P(h), P(bufs["c2"]), P(bufs["h2"]), P(pcount), P(ccount), P(p_score),
-                         P(p_logprob), P(p_len), P(sent[0]), P(sent[1]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent),
-                         P(parent), P(tok))
-        cg, hg = self._b(tag + "cg", (M, Hd)), self._b(tag + "hg", (M, Hd))
-        alive = self._b(tag + "alive", (1,))
+        bs.init(lib, bos, Hd, c, h, bufs["c2"], bufs["h2"])   # re-initialised per call
+        cg, hg, alive = self._b(tag + "cg", (M, Hd)), self._b(tag + "hg", (M, Hd)), self._b(tag + "alive", (1,))
         cons_t = probs_t = None
         if cons is not None:   # only bank 0 starts with a beam; the constraint table of THIS call into the buffer the rounds read
             pcount.view(B // S, S)[:, 1:] = 0
@@ -1399,38 +1215,23 @@ class CaptionGenerator(object):
                 cons_t.copy_(torch.from_numpy(np.ascontiguousarray(table, dtype=np.int32)), non_blocking=True)
         ban_t = self._controls_table(tag, ctl) if ctl is not None else None
 
-        def controlled(it, timed):   # the round's logits, processed in place from the live beams' sentences
-            logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
-            self._apply_controls(ctl, ban_t, logits, M, sent[it & 1], L, 1, p_len, None, eos)
-            return logits
-
         def one(it, timed):
             s_ = _stream()
             # every new beam continues its parent's state and feeds its last word: three row moves, one launch
-            lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent), M, Hd, P(cg), P(hg), P(xproj), P(tok), V, 4 * Hd, P(bufs["gact"]))
-            if ctl is not None:   # (None: the launches below, exactly)
-                logits = controlled(it, timed)
-                if cons is not None:
-                    lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs_t), V)
-                    lib.vc_topk_rows_f32(s_, P(probs_t), M, V, V, kc, P(tv), P(ti))
-                elif fused:
-                    lib.vc_softmax_topk_rows_f32(s_, P(logits), M, V, V, kc, P(tv), P(ti))
-                else:
-                    probs = torch.empty_like(logits)
-                    lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs), V)
-                    lib.vc_topk_rows_f32(s_, P(probs), M, V, V, kc, P(tv), P(ti))
-            elif cons is not None:   # the two calls for every kc: the bookkeeping reads the forced words' probabilities from the rows
-                logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
+            lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(bs.parent), M, Hd, P(cg), P(hg), P(xproj), P(tok), V, 4 * Hd, P(bufs["gact"]))
+            logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
+            if ctl is not None:   # the logits processed in place from the live beams' sentences
+                self._apply_controls(ctl, ban_t, logits, M, sent[it & 1], L, 1, p_len, None, eos)
+            if cons is not None:   # the two calls for every kc: the bookkeeping reads the forced words' probabilities from the rows
                 lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs_t), V)
                 lib.vc_topk_rows_f32(s_, P(probs_t), M, V, V, kc, P(tv), P(ti))
             elif fused:   # softmax + top-k in one read of the logits (vc_softmax_topk_rows_f32: bit-identical to the two calls)
-                logits, _, _ = self.step(tok, cg, hg, want="logits", bufs=bufs, timed=timed, projected=xproj is not None)
                 lib.vc_softmax_topk_rows_f32(s_, P(logits), M, V, V, kc, P(tv), P(ti))
             else:
-                probs, _, _ = self.step(tok, cg, hg, bufs=bufs, timed=timed, projected=xproj is not None)
+                probs = torch.empty_like(logits)
+                lib.vc_softmax_rows_f32(s_, P(logits), M, V, V, P(probs), V)
                 lib.vc_topk_rows_f32(s_, P(probs), M, V, V, kc, P(tv), P(ti))
-            state = (P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len), P(sent[it & 1]), P(sent[1 - (it & 1)]), P(c_score), P(c_logprob),
-                     P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
+            state = bs.update_args(it & 1)
             if cons is not None:   # the S banks of an image inside one wave; a beam may move to the bank of one more constraint
                 lib.vc_beam_update_constrained(s_, B // S, C, Wc, n, kc, L, int(eos), float(len_norm_f), P(cons_t) if C else None, P(tv), P(ti),
                                                P(probs_t), V, V, *state)
@@ -1452,10 +1253,9 @@ class CaptionGenerator(object):
         if ctl is not None:
             kind = kind + ctl.key()
         pt.key_fn = lambda: self._graph_key(*kind, B, n, L, K, int(eos), float(len_norm_f),
-                                            tensors=[pcount, ccount, p_score, p_logprob, p_len, sent[0], sent[1], c_score, c_logprob, c_len, c_slot,
-                                                     c_free, c_sent, parent, tok, tv, ti, cg, hg, alive, xproj, self._ones_for(M), cons_t, probs_t] + ([ban_t] if ctl is not None else []) + list(bufs.values()))
+                                            tensors=bs.tensors + [tv, ti, cg, hg, alive, xproj, self._ones_for(M), cons_t, probs_t]
+                                            + ([ban_t] if ctl is not None else []) + list(bufs.values()))
         pt.graph = self._graphs.get(pt.key_fn()) if fused else None
-        pt.tag, pt.ibuf, pt.scores, pt.ioff = tag, ibuf, dbuf[:dlay.off["p_logprob"]], lay.off   # (the host reads the scores only)
         pt.it, pt.last, pt.done, pt.pending = 0, 0, rounds <= 0, []
         return pt
 
@@ -1529,7 +1329,7 @@ class CaptionGenerator(object):
         return [select_bank(banks[b], full[b], int(eos)) for b in range(B)]
 
     def _checked_controls(self, controls, eos, max_len, constraints=None):
-        """`controls` of a beam search as an active, checked DecodeControls, or None (ValueError before any launch)"""
+        """`controls` of a decoding call as an active, checked DecodeControls, or None (ValueError before any launch)"""
         ctl = active_controls(controls)
         if ctl is not None:
             ctl.check(self.e.V, eos, max_len or self.p.gen_max_len, constraints)
@@ -1562,7 +1362,7 @@ class CaptionGenerator(object):
         if cons is not None:   # (its round writes the probabilities to a persistent buffer: every kc can be captured)
             fused = True
         # the words' input projections from a table (rows x rounds of lookups against ONE product over the vocabulary)
-        xproj = self._project_vocab() if (B * n * rounds >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
+        xproj = self._xproj_for(B * n, rounds)
         # Rounds run as hipGraph replays of K rounds each (nine launches per round otherwise): every buffer of a slice is persistent and
         # the sentence buffers alternate with the round's parity, so a chunk that starts at an even round is the same graph every time.
         # The FIRST call of a shape runs eagerly and captures the chunks at its end (a capture executes nothing); later calls replay
@@ -1625,11 +1425,11 @@ class CaptionGenerator(object):
             main.wait_stream(s)
         t_ph = _phase("rounds", t_ph)
         # results: two asynchronous copies per slice into pinned memory, one wait
-        hosts = [self._to_host(pt.tag, pt.ibuf, pt.scores, wait=pt is parts[-1]) for pt in parts]
+        hosts = [self._to_host(pt.tag, pt.state.ibuf, pt.state.scores, wait=pt is parts[-1]) for pt in parts]
         t_ph = _phase("results: copies to pinned memory", t_ph)
         res = []
         for pt, (ints, dbls) in zip(parts, hosts):
-            res += beams_from_host(ints, dbls, pt.ioff, pt.B, n, L, pt.last)
+            res += beams_from_host(ints, dbls, pt.state.lay.off, pt.B, n, L, pt.last)
         t_ph = _phase("results to host lists", t_ph)
         if fused and rounds > K:
             for pt in parts:
@@ -1693,7 +1493,7 @@ class CaptionGenerator(object):
         else:
             seed_, base_ = int(seed), 0
         seed_ &= (1 << 64) - 1
-        xproj = self._project_vocab() if (M * max_len >= V and Hd % 4 == 0 and os.environ.get("VC_DECODE_XPROJ", "1") != "0") else None
+        xproj = self._xproj_for(M, max_len)
         self._pack_wh(M)
         ban_t = self._controls_table(tag, ctl) if ctl is not None else None
         trace = getattr(self, "sbs_trace", None)   # (tests: a list here receives every eager round's logits as a host array)
@@ -1723,18 +1523,4 @@ class CaptionGenerator(object):
         steps = self._run_chunks(("sbs", B, n, L, K, kc, int(bos), int(eos), gd is None, seed_) + (ctl.key() if ctl is not None else ()),
                                  [ibuf, dbuf, parent, tok, ck, cl, ci, rnd, base, pending, cg, hg, xproj, gd, c0, h0, self._ones_for(M)]
                                  + ([ban_t] if ctl is not None else []) + list(bufs.values()), one, reset, K, max_len, check_every, pending)
-        ints, dbls = self._to_host(tag, ibuf, dbuf)
-        cnt, ln = ints[lay.off["count"]:lay.off["count"] + B].tolist(), ints[lay.off["len"]:lay.off["len"] + M].tolist()
-        o = lay.off["sent%d" % (steps & 1)]
-        words = ints[o:o + M * L].tolist()
-        ph, Gs, kap = dbls[:M].tolist(), dbls[M:2 * M].tolist(), dbls[2 * M:2 * M + B].tolist()
-        res = []
-        for b in range(B):
-            rows = range(b * n, b * n + cnt[b])
-            w, nw = sbs_weights([ph[r] for r in rows], kap[b])
-            caps = []
-            for j, r in enumerate(rows):
-                s = words[r * L + 1:r * L + ln[r]]
-                caps.append((s, ph[r], Gs[r], bool(s) and s[-1] == eos, float(w[j]), float(nw[j])))
-            res.append({"kappa": kap[b], "captions": caps})
-        return res
+        return sbs_from_host(*self._to_host(tag, ibuf, dbuf), lay.off, B, n, L, steps, int(eos))

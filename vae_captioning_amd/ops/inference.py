@@ -52,19 +52,11 @@ def _cluster_rows(c_v, wanted):
 
 
 def _decode(decoder, params, sess, placeholder, ids, images, c_v, allow_beam):
-    if allow_beam and params.sample_gen == "diverse":
-        return decoder.diverse_inference(sess, ids, images, placeholder, c_v)
-    if allow_beam and params.sample_gen == "diverse_beam":
-        return decoder.diverse_beam_search(sess, ids, images, placeholder, c_v)
-    if allow_beam and params.sample_gen == "stochastic_beam":
-        return decoder.stochastic_beam_search(sess, ids, images, placeholder, c_v)
-    if allow_beam and params.sample_gen in ("marginal_greedy", "marginal_beam"):
-        return decoder.marginal_inference(sess, ids, images, placeholder, c_v)
-    if allow_beam and params.sample_gen == "constrained_beam":
-        return decoder.constrained_beam_search(sess, ids, images, placeholder, c_v)
-    if allow_beam and params.sample_gen == "beam_search":
-        return decoder.beam_search(sess, ids, images, placeholder, c_v, beam_size=params.beam_size)
-    return decoder.online_inference(sess, ids, images, placeholder, c_v=c_v)[0]
+    """Decoder.decode in the mode of params.sample_gen; allow_beam=False (the test set): online_inference, whatever the mode.  (Called
+    unbound: `decoder` may be any object with the reference's methods, so the beam width is given here.)"""
+    from ..vae_model.decoder import Decoder
+    mode = params.sample_gen if allow_beam else "greedy"
+    return Decoder.decode(decoder, mode, ids, images, c_v, sess, placeholder, **({"beam_size": params.beam_size} if mode == "beam_search" else {}))
 
 
 def human_captions(captions, lengths):
@@ -228,7 +220,8 @@ def inference(params, decoder, val_gen, test_gen, image_f_inputs=None, saver=Non
         store_scores(params, scores)
     if n_bound:
         store_bounds(params, bounds, getattr(decoder, "bound_stats", None))
-    if params.sample_gen in ("diverse", "diverse_beam", "stochastic_beam"):
+    from ..vae_model.decoder import DIVERSE_FILE_MODES
+    if params.sample_gen in DIVERSE_FILE_MODES:
         _store("./val_{}_diverse.json".format(params.gen_name), records)
         records = [{"image_id": r["image_id"], "caption": r["caption"]} for r in records]
     _store("./val_{}.json".format(params.gen_name), records)

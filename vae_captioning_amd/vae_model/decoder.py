@@ -4,7 +4,14 @@ by engine.CaptionEngine and generate.CaptionGenerator (all images and beams batc
 import numpy as np
 
 from .. import session, spec
+from ..decode_host import merge_groups, rerank_by_marginal
 from ..generate import CaptionGenerator
+
+
+DECODE_METHODS = {"greedy": "online_inference", "sample": "online_inference", "beam_search": "beam_search", "diverse": "diverse_inference",
+                  "diverse_beam": "diverse_beam_search", "stochastic_beam": "stochastic_beam_search", "marginal_greedy": "marginal_inference",
+                  "marginal_beam": "marginal_inference", "constrained_beam": "constrained_beam_search"}   # decode mode -> the method that runs it
+DIVERSE_FILE_MODES = ("diverse", "diverse_beam", "stochastic_beam")   # their full per-image lists are also written to val_{gen_name}_diverse.json
 
 
 class Decoder(object):
@@ -69,21 +76,54 @@ class Decoder(object):
             return tr.vgg.forward(torch.from_numpy(a).cuda())
         return a.reshape(a.shape[0], -1)
 
+    def _call(self, c_v, stop_word="<EOS>"):
+        """(bos, eos, use_cv) of a generation call: the two token ids and the cluster vectors the model takes (None when it takes none)"""
+        w2i = self.data_dict.word2idx
+        return w2i["<BOS>"], w2i[stop_word], (c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None)
+
+    def _text(self, tokens, skip):
+        """token ids as a caption's text, without the ids in `skip` (<BOS>, <EOS>)"""
+        return " ".join(self.data_dict.idx2word[t] for t in tokens if t not in skip)
+
+    def _ranked_record(self, pid, entries, skip, counts, extra=(), rerank="likelihood"):
+        """diverse_inference's record of an image's ranked entries (tokens, score, .., [the re-ranking's own value]), `extra` items after it"""
+        texts = [self._text(e[0], skip) for e in entries]
+        rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts, "scores": [float(e[1]) for e in entries], "counts": counts}
+        rec.update(extra)
+        if rerank in ("consensus", "marginal"):
+            rec[rerank] = [float(e[3]) for e in entries]
+        return rec
+
+    def _rerank(self):
+        """params.diverse_rerank: "likelihood", "consensus" (RuntimeError without an attached consensus index) or "marginal" """
+        mode = getattr(self.params, "diverse_rerank", "likelihood")
+        if mode == "consensus" and self.consensus_index is None:
+            raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
+                               "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
+        return mode
+
+    def decode(self, mode, picture_ids, in_pictures, c_v=None, sess=None, placeholder=None, **overrides):
+        """The cap_list of a batch in decode mode `mode` (params.sample_gen, gen_caption's gen_method) from the mode's method (DECODE_METHODS),
+        which gets `overrides` (draws=, beam_size=, ...) in place of its params defaults; beam_search's width defaults to params.beam_size.
+        "greedy", "sample" and, as in the reference, any other name: online_inference, which decodes as params.sample_gen says (so does
+        marginal_inference unless method= is given).  sess / placeholder: the reference's arguments, passed through."""
+        name = DECODE_METHODS.get(mode, "online_inference")
+        if name == "online_inference":
+            return self.online_inference(sess, picture_ids, in_pictures, placeholder, c_v=c_v)[0]
+        if mode == "beam_search" and "beam_size" not in overrides:
+            overrides["beam_size"] = self.params.beam_size
+        return getattr(self, name)(sess, picture_ids, in_pictures, placeholder, c_v, **overrides)
+
     def online_inference(self, sess, picture_ids, in_pictures, image_f_inputs, stop_word="<EOS>", c_v=None):
         """decoder.py:145-201.  Returns (cap_list, cap_raw)."""
         self.last_token_ids = None
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx[stop_word]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v, stop_word)
         if self.params.sample_gen == "sample":  # tf.multinomial(logits / temperature): same distribution, own Philox stream
             raw = self._gen().sample(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len,
                                      top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
         else:
             raw = self._gen().greedy(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len, controls=self.controls)
-        cap_list = []
-        for pid, toks in zip(picture_ids, raw):
-            words = [d.idx2word[t] for t in toks if t not in (bos, eos)]
-            cap_list.append({"image_id": pid, "caption": " ".join(words)})
+        cap_list = [{"image_id": pid, "caption": self._text(toks, (bos, eos))} for pid, toks in zip(picture_ids, raw)]
         self.last_token_ids = [[list(toks)] for toks in raw]
         return cap_list, raw
 
@@ -91,14 +131,12 @@ class Decoder(object):
                     len_norm_f=0.7):
         """decoder.py:203-320.  Returns cap_list."""
         self.last_token_ids = None
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         res = self._gen().beam_search(self._features(in_pictures), use_cv, None, bos, eos, beam_size,
                                       self.params.gen_max_len, len_norm_f, controls=self.controls)
         cap_list = []
         for pid, beams in zip(picture_ids, res):
-            texts = [" ".join(d.idx2word[t] for t in s if t not in (bos, eos)) for s, _ in beams]
+            texts = [self._text(s, (bos, eos)) for s, _ in beams]
             cap_list.append({"image_id": pid, "caption": texts if ret_beams else texts[0]})
         self.last_token_ids = [[list(s) for s, _ in (beams if ret_beams else beams[:1])] for beams in res]
         return cap_list
@@ -115,32 +153,18 @@ class Decoder(object):
         over ALL draws of the image (generate.py: diverse(rerank="marginal")); "scores" are those scores and the records gain "marginal"
         (aligned with "captions")."""
         self.last_token_ids = None
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         draws = int(draws if draws is not None else self.params.diverse_draws)
         method = method if method is not None else self.params.diverse_method
-        consensus = getattr(self.params, "diverse_rerank", "likelihood") == "consensus"
-        marginal = getattr(self.params, "diverse_rerank", "likelihood") == "marginal"
-        if consensus and self.consensus_index is None:
-            raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
-                               "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
+        rerank = self._rerank()
+        consensus, marginal = rerank == "consensus", rerank == "marginal"
         feats = self._features(in_pictures)
         res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus else n_best,
                                   max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood",
                                   top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
         if consensus:
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
-        cap_list = []
-        for pid, entries in zip(picture_ids, res):
-            texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
-            rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
-                   "scores": [float(e[1]) for e in entries], "counts": [int(e[2]) for e in entries]}
-            if consensus:
-                rec["consensus"] = [float(e[3]) for e in entries]
-            if marginal:
-                rec["marginal"] = [float(e[3]) for e in entries]
-            cap_list.append(rec)
+        cap_list = [self._ranked_record(pid, entries, (bos, eos), [int(e[2]) for e in entries], rerank=rerank) for pid, entries in zip(picture_ids, res)]
         self.last_token_ids = [[list(e[0]) for e in entries] for entries in res]
         return cap_list
 
@@ -151,11 +175,8 @@ class Decoder(object):
         per live beam of the round's earlier groups that has just taken it.  Equal captions of different groups are merged under
         their best score and ranked.  Returns cap_list in diverse_inference's record shape: per image {"image_id", "caption": the
         best text, "captions": [texts], "scores": [...], "counts": [groups that produced the caption], "groups": [[group ids]]}."""
-        from ..generate import merge_groups
         self.last_token_ids = None
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         total = int(beam_size if beam_size is not None else self.params.beam_size)
         G = int(groups if groups is not None else self.params.beam_groups)
         lam = float(diversity if diversity is not None else self.params.beam_diversity)
@@ -164,15 +185,10 @@ class Decoder(object):
         res = self._gen().diverse_beam_search(self._features(in_pictures), use_cv, None, bos, eos, groups=G, group_size=total // G,
                                               diversity=lam, max_len=self.params.gen_max_len, len_norm_f=len_norm_f,
                                               controls=self.controls)
-        cap_list, token_ids = [], []
-        for pid, per_group in zip(picture_ids, res):
-            entries = merge_groups(per_group)
-            token_ids.append([list(e[0]) for e in entries])
-            texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
-            cap_list.append({"image_id": pid, "caption": texts[0] if texts else "", "captions": texts,
-                             "scores": [float(e[1]) for e in entries], "counts": [len(e[2]) for e in entries],
-                             "groups": [[int(g) for g in e[2]] for e in entries]})
-        self.last_token_ids = token_ids
+        merged = [merge_groups(per_group) for per_group in res]
+        cap_list = [self._ranked_record(pid, entries, (bos, eos), [len(e[2]) for e in entries], {"groups": [[int(g) for g in e[2]] for e in entries]})
+                    for pid, entries in zip(picture_ids, merged)]
+        self.last_token_ids = [[list(e[0]) for e in entries] for entries in merged]
         return cap_list
 
     def stochastic_beam_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, beam_size=None, len_norm_f=0.7):
@@ -183,17 +199,11 @@ class Decoder(object):
         distinct), "logprob", "perturbed", "weight", "norm_weight" (aligned with "captions"), "kappa"}.  params.diverse_rerank ==
         "consensus" re-ranks by the attached consensus index and adds "consensus"; "marginal" adds "marginal" (one latent draw per
         image: the caption's logprob, so the order is the likelihood order)."""
-        from ..generate import rerank_by_marginal
         self.last_token_ids = None
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         n = int(beam_size if beam_size is not None else self.params.beam_size)
-        consensus = getattr(self.params, "diverse_rerank", "likelihood") == "consensus"
-        marginal = getattr(self.params, "diverse_rerank", "likelihood") == "marginal"
-        if consensus and self.consensus_index is None:
-            raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
-                               "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
+        rerank = self._rerank()
+        consensus, marginal = rerank == "consensus", rerank == "marginal"
         feats = self._features(in_pictures)
         res = self._gen().stochastic_beam_search(feats, use_cv, None, bos, eos, beam_size=n, max_len=self.params.gen_max_len,
                                                  len_norm_f=len_norm_f, controls=self.controls)
@@ -203,22 +213,15 @@ class Decoder(object):
             ranked.append([(list(c[0]), c[1] / (1 + len(c[0])) ** len_norm_f, 1) for c in caps])
         if consensus:
             ranked = self.consensus_index.rerank(feats, ranked)
+        by_words = [{tuple(c[0]): c for c in r["captions"]} for r in res]
         if marginal:
-            ranked = [rerank_by_marginal(entries, [by[tuple(e[0])][1] for e in entries], eos, len_norm_f)
-                      for entries, by in zip(ranked, [{tuple(c[0]): c for c in r["captions"]} for r in res])]
+            ranked = [rerank_by_marginal(entries, [by[tuple(e[0])][1] for e in entries], eos, len_norm_f) for entries, by in zip(ranked, by_words)]
         cap_list = []
-        for pid, entries, r in zip(picture_ids, ranked, res):
-            by = {tuple(c[0]): c for c in r["captions"]}
+        for pid, entries, r, by in zip(picture_ids, ranked, res, by_words):
             own = [by[tuple(e[0])] for e in entries]
-            texts = [" ".join(d.idx2word[t] for t in e[0] if t not in (bos, eos)) for e in entries]
-            rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts, "scores": [float(e[1]) for e in entries],
-                   "counts": [1] * len(entries), "logprob": [float(c[1]) for c in own], "perturbed": [float(c[2]) for c in own],
-                   "weight": [float(c[4]) for c in own], "norm_weight": [float(c[5]) for c in own], "kappa": float(r["kappa"])}
-            if consensus:
-                rec["consensus"] = [float(e[3]) for e in entries]
-            if marginal:
-                rec["marginal"] = [float(e[3]) for e in entries]
-            cap_list.append(rec)
+            extra = {"logprob": [float(c[1]) for c in own], "perturbed": [float(c[2]) for c in own], "weight": [float(c[4]) for c in own],
+                     "norm_weight": [float(c[5]) for c in own], "kappa": float(r["kappa"])}
+            cap_list.append(self._ranked_record(pid, entries, (bos, eos), [1] * len(entries), extra, rerank))
         self.last_token_ids = [[list(e[0]) for e in entries] for entries in ranked]
         return cap_list
 
@@ -230,9 +233,7 @@ class Decoder(object):
         largest that fits, 16 >> the largest number of sets).  Returns cap_list: per image {"image_id", "caption", "constraints": the ids
         used, "satisfied": one bool per constraint, "score"} -- the best caption of the state with the most constraints met."""
         self.last_token_ids = None
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         if constraints is None:
             if self.constraints is None:
                 raise RuntimeError("constrained_beam_search needs constraints: pass them or attach decoder.constraints = "
@@ -246,7 +247,7 @@ class Decoder(object):
         for pid, sets, (beams, state) in zip(picture_ids, constraints, res):
             toks, score = (list(beams[0][0]), float(beams[0][1])) if beams else ([], float("-inf"))
             token_ids.append([toks])
-            cap_list.append({"image_id": pid, "caption": " ".join(d.idx2word[t] for t in toks if t not in (bos, eos)),
+            cap_list.append({"image_id": pid, "caption": self._text(toks, (bos, eos)),
                              "constraints": [[int(v) for v in st] for st in sets],
                              "satisfied": [bool((state >> j) & 1) for j in range(len(sets))], "score": score})
         self.last_token_ids = token_ids
@@ -262,9 +263,7 @@ class Decoder(object):
         if self.controls is not None and not self.controls.is_noop():
             raise ValueError("marginal_inference takes no decoding controls: renormalising every draw's distribution would break the "
                              "mode's identity with score()'s marginal")
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         method = method if method is not None else self.params.sample_gen
         K = int(draws if draws is not None else self.params.marginal_draws)
         feats = self._features(in_pictures)
@@ -282,7 +281,7 @@ class Decoder(object):
                 marg.append(sc * len(s) ** len_norm_f if (s and s[-1] == eos and len_norm_f > 0) else sc)
         else:
             raise ValueError("marginal_inference: method must be 'marginal_greedy' or 'marginal_beam' (got %r)" % (method,))
-        cap_list = [{"image_id": pid, "caption": " ".join(d.idx2word[t] for t in s if t not in (bos, eos)), "marginal": float(m), "draws": K}
+        cap_list = [{"image_id": pid, "caption": self._text(s, (bos, eos)), "marginal": float(m), "draws": K}
                     for pid, s, m in zip(picture_ids, toks, marg)]
         self.last_token_ids = [[list(s)] for s in toks]
         return cap_list
@@ -291,9 +290,7 @@ class Decoder(object):
         """Held-out likelihood of given captions (generate.py: score): captions[b] = token-id lists of image b (with or without <BOS>; the
         <EOS> counts when present), scored under `draws` (params.score_draws) prior draws.  Returns per image {"image_id", "captions":
         [{"tokens": n, "marginal": log 1/K sum_k p(caption | z_k, image), "logprob": mean over the draws of log p(caption | z_k, image)}]}."""
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
-        use_cv = c_v if (spec.uses_ci(self.params) and c_v is not None and len(c_v)) else None
+        bos, eos, use_cv = self._call(c_v)
         draws = int(draws if draws is not None else self.params.score_draws)
         res = self._gen().score(self._features(in_pictures), captions, use_cv, None, bos, eos, draws=draws)
         return [{"image_id": pid, "captions": [{"tokens": int(r["tokens"]), "marginal": float(r["marginal"]), "logprob": float(np.mean(r["logprob"]))}
@@ -307,10 +304,9 @@ class Decoder(object):
         as this decoder.  AG / GMM: an image with an empty cluster vector has no posterior; it is left out and counted in
         self.bound_stats["skipped_images"].  bound_stats also keeps running float64 sums of the posterior means and their squares per
         latent dimension over every caption scored ("mu_sum", "mu_sq", "captions"): what ops.inference.active_units reads."""
-        d = self.data_dict
-        bos, eos = d.word2idx["<BOS>"], d.word2idx["<EOS>"]
+        bos, eos, use_cv = self._call(c_v)
         p = self.params
-        use_cv = np.asarray(c_v, np.float32) if (spec.uses_ci(p) and c_v is not None and len(c_v)) else None
+        use_cv = np.asarray(use_cv, np.float32) if use_cv is not None else None
         draws = int(draws if draws is not None else p.bound_draws)
         feats = self._features(in_pictures)
         st = self.bound_stats
