@@ -411,6 +411,12 @@ int vc_conv3x3_wino4_preferred(int B, int H, int W, int Cin, int Cout);
 int vc_conv3x3_wino4_pack_f32(void* stream, int Cin, int Cout, const float* w, int transpose, float* wp);
 int vc_conv3x3_wino4_fwd_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp, const float* bias,
                              float* y, float* ypool, int relu);
+/* y == NULL (this entry, vc_conv3x3_wino4_fwd_f32 with ypool != NULL, and their vc_conv3x3_wino4v_* namesakes): the caller wants only
+ * the pooled tensor (and, here, the routing codes).  The kernel then has no full-size output path at all -- no hand-over through the
+ * LDS, no barrier in front of it, no stores -- and ypool / pool_bits are BIT-IDENTICAL to what the same call with a real y leaves (a
+ * training step reads nothing else of a pooled layer: the next layer and its weight gradient read ypool, MaxPoolGrad + ReluGrad the
+ * codes).  ypool (and pool_bits here) stay required; y == NULL without ypool is VC_EINVAL and launches nothing.  Calls over more
+ * images than one launch addresses are cut into image ranges as before. */
 int vc_conv3x3_wino4_fwd_pool_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp,
                                   const float* bias, float* y, float* ypool, uint32_t* pool_bits);
 size_t vc_conv3x3_wino4_mask_words(int B, int H, int W, int C);
@@ -435,6 +441,7 @@ int vc_conv3x3_wino4v_preferred(int B, int H, int W, int Cin, int Cout, int dgra
 size_t vc_conv3x3_wino4v_workspace_bytes(int B, int H, int W, int C);
 int vc_conv3x3_wino4v_fwd_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp, const float* bias,
                               float* y, float* ypool, int relu, float* vws, size_t vws_bytes);
+/* y == NULL: the pooled tensor and the routing codes only, as for vc_conv3x3_wino4_fwd_pool_f32 above (same contract, same bits). */
 int vc_conv3x3_wino4v_fwd_pool_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp, const float* bias,
                                    float* y, float* ypool, uint32_t* pool_bits, float* vws, size_t vws_bytes);
 int vc_conv3x3_wino4v_fwd_mask_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp, const float* bias,

@@ -41,5 +41,6 @@ for it in range(12):
     torch.cuda.synchronize()
     if it >= 2:
         tf.append(e[0].elapsed_time(e[1])); tb.append(e[1].elapsed_time(e[2]))
-print("VC_WINO4V=%s precision=%s images=%d: VGG16 forward %.3f ms (min %.3f)  backward %.3f ms (min %.3f)" % (
-    os.environ.get("VC_WINO4V", "default"), tr.precision, B, np.mean(tf), min(tf), np.mean(tb), min(tb)))
+print("VC_WINO4V=%s VC_POOL_STORE_Y=%s precision=%s images=%d: VGG16 forward %.3f ms (min %.3f)  backward %.3f ms (min %.3f)  peak device memory %.0f MB" % (
+    os.environ.get("VC_WINO4V", "default"), os.environ.get("VC_POOL_STORE_Y", "default"), tr.precision, B, np.mean(tf), min(tf), np.mean(tb), min(tb),
+    torch.cuda.max_memory_allocated() / 1e6))

@@ -141,8 +141,12 @@ __device__ __forceinline__ void w4_hstep(int k, const float* d, float* o, float*
 // what holds it at 46-57 % MFMA-busy; here the input transform is paid ONCE per input channel instead of once per 32-output-channel
 // tile (16 x on the 512-channel layers) and at HBM speed (V = 2.25 x the activation bytes, written + read once).
 enum { W4_SQUARE = 0, W4_LINEAR = 1, W4_VIN = 2 };
-template <int KIND, bool POOL, int MODE>
+// STORE = false (pooled forward only, a.out == null): the caller wants the pooled tensor and the routing codes and nothing reads the
+// full-size activation (the training step behind a pooled layer: trainer.py) -- the whole `out` path is compiled out: no hand-over
+// through the LDS, no barrier in front of it, no row stores.  Y, the fmaxf tree and code() are the same registers and instructions.
+template <int KIND, bool POOL, int MODE, bool STORE = true>
 __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(Wino4Args a) {
+    static_assert(STORE || (POOL && KIND == W4_FWD), "only the pooled forward has something else to leave");
     constexpr bool LT = MODE != W4_SQUARE, VIN = MODE == W4_VIN;
     constexpr int NPS = VIN ? 1 : LT ? 5 : 3;                          // patch slots per thread and phase
     constexpr int PBUF = LT ? W4L_PBUF : W4_PBUF, PLANE = LT ? W4L_PLANE : W4_PLANE;
@@ -583,7 +587,11 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(Wino4Args a) {
             }
             (void)ok;
         }
-    if constexpr (!LT) {
+    if constexpr (!STORE) {
+        // Nothing leaves at full size.  The barrier that opens the hand-over below orders "the partner wave has read this wave's partial
+        // outputs" before the wave writes into the exchange area again; here nobody writes into it after the exchange, so the only
+        // synchronisation the exchange needs is the barrier between its writes and its reads (in body() above).
+    } else if constexpr (!LT) {
         // Square blocks: the wave's 16 x 16 pixels x four channel quads leave through its 16 KB of the exchange area so that a store
         // instruction writes four 256-byte ROWS (lane = (quad, pixel of the row)) instead of 64 scattered 16-byte pieces -- the scattered
         // form cost 0.08 ms of conv1_2's 0.90 even with every store hitting the cache (W4_ABL=256).  slot(quad, y, x) = quad * 256 + 16 y +
@@ -777,13 +785,16 @@ static int wino4_attr() {
         auto set = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, WINO4_LDS_BYTES); };
         set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, false, false>));
         set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, true, false>));
+        set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, true, false, false>));
         set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_DGRAD, false, false>));
         auto setl = [&](const void* f) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, WINO4L_LDS_BYTES); };
         setl(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, false, true>));
         setl(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, true, true>));
+        setl(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, true, true, false>));
         setl(reinterpret_cast<const void*>(conv_wino4_kernel<W4_DGRAD, false, true>));
         set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, false, W4_VIN>));
         set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, true, W4_VIN>));
+        set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_FWD, true, W4_VIN, false>));
         set(reinterpret_cast<const void*>(conv_wino4_kernel<W4_DGRAD, false, W4_VIN>));
         return e == hipSuccess ? 0 : fail((int)e, "%s: hipFuncSetAttribute failed", "conv wino4 kernel");
     }();
@@ -795,6 +806,7 @@ static bool plan_wino4v(int B, int H, int W, int C, int N, Wino4Geom& g);
 static int wino4_launch(hipStream_t st, int kind, int nb, int H, int W, int C, int N, const float* x, const float* wp, float* out, const float* aux,
                         float* pool, unsigned* mask, int relu, unsigned* pbits = nullptr, float* vws = nullptr) {
     Wino4Args a;
+    if (!out && !(kind == W4_FWD && pool)) return fail(VC_EINVAL, "%s: no output pointer (only the pooled forward runs without one)", "conv wino4");
     if (!(vws ? plan_wino4v(nb, H, W, C, N, a.g) : plan_wino4(nb, H, W, C, N, a.g))) return fail(VC_EINVAL, "%s: unsupported shape (vc_conv3x3_wino4_supported / vc_conv3x3_wino4v_supported)", "conv wino4");
     int rc = wino4_attr();
     if (rc) return rc;
@@ -820,13 +832,16 @@ static int wino4_launch(hipStream_t st, int kind, int nb, int H, int W, int C, i
     a.per_chunk = cdiv(a.g.nblocks, W4_NBLK) * a.tg;
     if (vws) {
         if (kind == W4_DGRAD) hipLaunchKernelGGL((conv_wino4_kernel<W4_DGRAD, false, W4_VIN>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
+        else if (pool && !out) hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, true, W4_VIN, false>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
         else if (pool) hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, true, W4_VIN>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
         else hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, false, W4_VIN>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
     } else if (a.g.lt) {
         if (kind == W4_DGRAD) hipLaunchKernelGGL((conv_wino4_kernel<W4_DGRAD, false, true>), dim3(a.ntiles), dim3(256), WINO4L_LDS_BYTES, st, a);
+        else if (pool && !out) hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, true, true, false>), dim3(a.ntiles), dim3(256), WINO4L_LDS_BYTES, st, a);
         else if (pool) hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, true, true>), dim3(a.ntiles), dim3(256), WINO4L_LDS_BYTES, st, a);
         else hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, false, true>), dim3(a.ntiles), dim3(256), WINO4L_LDS_BYTES, st, a);
     } else if (kind == W4_DGRAD) hipLaunchKernelGGL((conv_wino4_kernel<W4_DGRAD, false, false>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
+    else if (pool && !out) hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, true, false, false>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
     else if (pool) hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, true, false>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
     else hipLaunchKernelGGL((conv_wino4_kernel<W4_FWD, false, false>), dim3(a.ntiles), dim3(256), WINO4_LDS_BYTES, st, a);
     return launch_status("conv wino4");
@@ -879,14 +894,14 @@ extern "C" int vc_conv3x3_wino4_pack_f32(void* stream, int Cin, int Cout, const 
 extern "C" int vc_conv3x3_wino4_fwd_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp,
                                         const float* bias, float* y, float* ypool, int relu) {
     using namespace vc;
-    VC_CHECK_ARG(x && wp && y, "null pointer");
+    VC_CHECK_ARG(x && wp && (y || ypool), "null pointer (y may be null only where ypool is given: the pooled tensor alone)");
     VC_CHECK_ARG(waligned16(x) && waligned16(wp) && waligned16(y) && waligned16(bias) && waligned16(ypool), "pointers must be 16-byte aligned");
     VC_CHECK_ARG(!ypool || !((H | W) & 1), "the fused max-pool needs even H and W");
     const int per = wino_images_per_launch(B, H, W, Cin, Cout);
     VC_CHECK_ARG(per > 0 && vc_conv3x3_wino4_supported(B, H, W, Cin, Cout, 0), "unsupported shape (vc_conv3x3_wino4_supported)");
     for (int b0 = 0; b0 < B; b0 += per) {   // image ranges of < 2 GiB
         const int nb = B - b0 < per ? B - b0 : per;
-        const int rc = wino4_launch((hipStream_t)stream, W4_FWD, nb, H, W, Cin, Cout, x + (size_t)b0 * H * W * Cin, wp, y + (size_t)b0 * H * W * Cout, bias,
+        const int rc = wino4_launch((hipStream_t)stream, W4_FWD, nb, H, W, Cin, Cout, x + (size_t)b0 * H * W * Cin, wp, y ? y + (size_t)b0 * H * W * Cout : nullptr, bias,
                                     ypool ? ypool + (size_t)b0 * (H / 2) * (W / 2) * Cout : nullptr, nullptr, relu);
         if (rc) return rc;
     }
@@ -896,7 +911,7 @@ extern "C" int vc_conv3x3_wino4_fwd_f32(void* stream, int B, int H, int W, int C
 extern "C" int vc_conv3x3_wino4_fwd_pool_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp,
                                              const float* bias, float* y, float* ypool, uint32_t* pool_bits) {
     using namespace vc;
-    VC_CHECK_ARG(x && wp && y && ypool && pool_bits, "null pointer");
+    VC_CHECK_ARG(x && wp && ypool && pool_bits, "null pointer (y alone may be null: the pooled tensor and the routing codes only)");
     VC_CHECK_ARG(waligned16(x) && waligned16(wp) && waligned16(y) && waligned16(bias) && waligned16(ypool), "pointers must be 16-byte aligned");
     VC_CHECK_ARG(!((H | W) & 1), "the fused max-pool needs even H and W");
     const int per = wino_images_per_launch(B, H, W, Cin, Cout);
@@ -904,7 +919,7 @@ extern "C" int vc_conv3x3_wino4_fwd_pool_f32(void* stream, int B, int H, int W, 
     for (int b0 = 0; b0 < B; b0 += per) {
         const int nb = B - b0 < per ? B - b0 : per;
         const size_t po = (size_t)b0 * (H / 2) * (W / 2) * Cout;
-        const int rc = wino4_launch((hipStream_t)stream, W4_FWD, nb, H, W, Cin, Cout, x + (size_t)b0 * H * W * Cin, wp, y + (size_t)b0 * H * W * Cout, bias,
+        const int rc = wino4_launch((hipStream_t)stream, W4_FWD, nb, H, W, Cin, Cout, x + (size_t)b0 * H * W * Cin, wp, y ? y + (size_t)b0 * H * W * Cout : nullptr, bias,
                                     ypool + po, nullptr, 1, pool_bits + po / 8);
         if (rc) return rc;
     }
@@ -979,7 +994,7 @@ extern "C" size_t vc_conv3x3_wino4v_workspace_bytes(int B, int H, int W, int C) 
 extern "C" int vc_conv3x3_wino4v_fwd_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp, const float* bias,
                                          float* y, float* ypool, int relu, float* vws, size_t vws_bytes) {
     using namespace vc;
-    VC_CHECK_ARG(x && wp && y, "null pointer");
+    VC_CHECK_ARG(x && wp && (y || ypool), "null pointer (y may be null only where ypool is given: the pooled tensor alone)");
     VC_CHECK_ARG(waligned16(x) && waligned16(wp) && waligned16(y) && waligned16(bias) && waligned16(ypool), "pointers must be 16-byte aligned");
     VC_CHECK_ARG(!ypool || !((H | W) & 1), "the fused max-pool needs even H and W");
     VC_CHECK_ARG(vc_conv3x3_wino4v_supported(B, H, W, Cin, Cout, 0), "unsupported shape (vc_conv3x3_wino4v_supported)");
@@ -989,7 +1004,7 @@ extern "C" int vc_conv3x3_wino4v_fwd_f32(void* stream, int B, int H, int W, int 
 extern "C" int vc_conv3x3_wino4v_fwd_pool_f32(void* stream, int B, int H, int W, int Cin, int Cout, const float* x, const float* wp, const float* bias,
                                               float* y, float* ypool, uint32_t* pool_bits, float* vws, size_t vws_bytes) {
     using namespace vc;
-    VC_CHECK_ARG(x && wp && y && ypool && pool_bits, "null pointer");
+    VC_CHECK_ARG(x && wp && ypool && pool_bits, "null pointer (y alone may be null: the pooled tensor and the routing codes only)");
     VC_CHECK_ARG(waligned16(x) && waligned16(wp) && waligned16(y) && waligned16(bias) && waligned16(ypool), "pointers must be 16-byte aligned");
     VC_CHECK_ARG(!((H | W) & 1), "the fused max-pool needs even H and W");
     VC_CHECK_ARG(vc_conv3x3_wino4v_supported(B, H, W, Cin, Cout, 0), "unsupported shape (vc_conv3x3_wino4v_supported)");

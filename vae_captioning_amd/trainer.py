@@ -31,6 +31,21 @@ def imagenet_weights(weight_file):
     return out
 
 
+class _EngineBuffers(dict):
+    """VggEngine.buf: name -> tensor.  Reading buf["y_<name>"] of a pooled layer whose full-size activation the last forward did
+    not store (VggEngine.pool_store_y) computes it then (VggEngine._materialise); `in` and .get() do not."""
+
+    def __init__(self, engine):
+        dict.__init__(self)
+        self._engine = engine
+
+    def __missing__(self, key):
+        t = self._engine._materialise(key)
+        if t is None:
+            raise KeyError(key)
+        return t
+
+
 class VggEngine(object):
     """utils/image_embeddings.py:26-238 on device: 13 x (conv3x3 + bias + ReLU), 5 max-pools,
     fc1 / fc2 (+ dropout), forward and backward, plus cnn_optimizer (ops/optimizers.py:49-82)."""
@@ -40,7 +55,9 @@ class VggEngine(object):
         self.lib = lib or abi.load()
         self.dev = device
         self.store = FlatStore(spec.vgg_variables(), device, tail=0, grad_backing=grad_backing)
-        self.buf = {}
+        self.buf = _EngineBuffers(self)
+        self._acts = []      # the last forward's (layer name, input tensor, H, W, Cin_eff, Cout, weights used): what backward() walks
+        self._dropped = {}   # pooled layer whose y_<name> the last forward did not store -> what _materialise needs to compute it
         self.ws = None
         self.ws_bytes = 0
         self.tail_ws = {}
@@ -57,11 +74,24 @@ class VggEngine(object):
         # Convolution dispatch: which kernel runs which layer, pass and launch is decided once per shape by vgg_plan.conv_plan (the rules are
         # in its docstring, the table of kernels in DESIGN.md section 4); forward / backward / _pack_weights execute the plan of self._plan
         self.use_conv1 = True
+        # False: a layer whose plan variant is "pool" gets no full-size activation -- y_<name> is not allocated, the pooled forward is
+        # called with y = NULL (csrc/conv_wino4.hip compiles the whole `out` path away) and the layer's "P" entry of self._acts carries
+        # None.  Nothing in a training step reads that tensor: the next layer and its weight gradient read p_<name>, MaxPoolGrad +
+        # ReluGrad the routing codes, the data gradient behind a pool has no ReLU source (1.57 GB of HBM writes and of device memory
+        # per 64-image step).  Whoever wants it afterwards (checkers, tools) reads buf["y_<name>"] or self.acts as before and gets it
+        # computed on demand from what the forward kept (_materialise): the step pays five bias copies of <= 2 KB for that.  An engine
+        # driven by hand stores every activation in its forward; the Trainer switches the store off (VC_POOL_STORE_Y=1 keeps it: A/B runs).
+        self.pool_store_y = True
         self.use_wino = os.environ.get("VC_CONV_WINO", "1") != "0"
         # conv4_x / conv5_x forward + data gradient on a once-transformed input (csrc/conv_wino4.hip MODE 2; bit-identical to the fused
         # kernel).  Measured inside the cfg4 step (profiles/r06_wino4v_step.md): the main kernels shrink by 15-25 % but the 24 transform
         # launches per step sit on the chains; f32 25.85-25.93 ms against 25.81-25.88 fused (nothing), split-bf16 mode 21.39 against
         # 21.66 (its shorter weight-gradient stream leaves the chains critical).  Default: on in the split-bf16 mode only; VC_WINO4V=1 / 0 forces.
+        # The FORWARD alone is another matter: it has no third stream beside its two chains, so what its kernels save comes off the step
+        # (profiles/pool_nostore_bench.md: 25.49-25.53 ms with MODE 2 on the forward of conv4_x / conv5_x only against 25.65-25.72 fused).
+        # wino4v_f32 is the f32 default: False for an engine driven by hand, "fwd" (forward launches only, vgg_plan.conv_plan) in the
+        # Trainer, on whose step that was measured; VC_WINO4V=fwd / 1 / 0 forces.
+        self.wino4v_f32 = False
         self._wino4v_env = os.environ.get("VC_WINO4V")
         self.vws = {}   # conv chain -> workspace of the transformed input
         # split-bf16 mode (this engine's precision): the direct weight gradient on the bf16 matrix pipe (csrc/conv_wgrad_bx.hip) replaces
@@ -110,6 +140,31 @@ class VggEngine(object):
                 if s is not None and s != cur:
                     s.wait_stream(cur)
         return t
+
+    @property
+    def acts(self):
+        """The last forward's (layer name, input tensor, H, W, Cin_eff, Cout, weights used) for whoever inspects it: like _acts, with
+        the input of a "P" entry that the forward did not store (pool_store_y) computed now (buf["y_<name>"])."""
+        out = []
+        for i, a in enumerate(self._acts):
+            if a[0] == "P" and a[1] is None:
+                a = (a[0], self.buf["y_" + self._acts[i - 1][0]]) + tuple(a[2:])
+            out.append(a)
+        return out
+
+    def _materialise(self, key):
+        """buf["y_<name>"] of a pooled layer whose full-size activation the last forward did not store: the plain F(4x4,3x3) forward
+        of that layer over the same image ranges, on its retained input, this step's packed weights and the bias as it was -- the
+        same accumulators and epilogue arithmetic as the pooled launch, so exactly the tensor a storing forward leaves.  Enqueued on
+        the caller's stream, which the forward joined with its side streams before it returned; dropped again by the next forward."""
+        name = key[2:] if key.startswith("y_") else None
+        if name not in self._dropped:
+            return None
+        x, H, W, cie, co, ranges, bias = self._dropped[name]
+        y = self._b(key, (x.shape[0], co // 4, H, W, 4))
+        for b0, nb in ranges:
+            self.lib.vc_conv3x3_wino4_fwd_f32(_stream(), nb, H, W, cie, co, P(x[b0:]), P(dict.__getitem__(self.buf, "vp_" + name)), P(bias), P(y[b0:]), None, 1)
+        return y
 
     def _need_ws(self, nbytes):
         if nbytes > self.ws_bytes:
@@ -185,7 +240,11 @@ class VggEngine(object):
 
     @property
     def use_wino4v(self):
-        return self._wino4v_env != "0" if self._wino4v_env is not None else self.precision == "bf16x3"
+        if self._wino4v_env == "fwd":   # (A/B runs: the forward launches only, the data gradient stays fused -- vgg_plan.conv_plan)
+            return "fwd"
+        if self._wino4v_env is not None:
+            return self._wino4v_env != "0"
+        return True if self.precision == "bf16x3" else self.wino4v_f32
 
     def _wino(self, family, entry, v, ch):
         """-> (the entry `entry` ("fwd_mask_f32", "dgrad_bits_f32" ...) of a Winograd family, its trailing arguments).  v: the launch
@@ -253,7 +312,10 @@ class VggEngine(object):
         if not c1:
             lib.vc_pad_dim_f32(st, P(S.param("cnn/conv1_1/weights")), 9, 3, 4, 64, P(w4))
         packed = self._pack_weights(plan)
-        self.acts = []  # (layer name, input tensor, H, W, Cin_eff, Cout, weights used)
+        self._acts = []  # (layer name, input tensor, H, W, Cin_eff, Cout, weights used)
+        for gone in self._dropped:   # (an activation somebody asked for after the previous forward is that forward's, not this one's)
+            self.buf.pop("y_" + gone, None)
+        self._dropped = {}
         # The conv / pool chain of one image is independent of every other image: with two streams the
         # batch is pushed through as two half-batch chains so that the tail of each kernel (its last partial
         # round of workgroups) overlaps the other chain's kernels.  Halves are contiguous slices of the leading (image) dimension.
@@ -266,7 +328,13 @@ class VggEngine(object):
             name, cie, co, pooled = L.name, L.cin_eff, L.cout, L.pooled
             wn, bn = spec.vgg_var_names(name)
             w = w4 if cie == 4 else S.param(wn)
-            y = self._b("y_" + name, (B, co // 4, H, W, 4))
+            # (the pooled F(4x4,3x3) forward of a training step leaves the pooled tensor and the routing codes only: pool_store_y)
+            drop_y = L.variant == "pool" and L.family == "wino4" and not self.pool_store_y
+            y = None if drop_y else self._b("y_" + name, (B, co // 4, H, W, 4))
+            if drop_y:   # what _materialise needs: the input (kept anyway), the launch ranges, and the bias as it is NOW (the optimiser moves it)
+                bias_now = self._b("bias_" + name, (co,))
+                bias_now.copy_(S.param(bn))
+                self._dropped[name] = (x, H, W, cie, co, [(b0, nb) for b0, nb, _ in halves], bias_now)
             yp = self._b("p_" + name, (B, co // 4, H // 2, W // 2, 4)) if pooled else None
             # pooled layer in training: the 2x2 max-pool is register math in the epilogue; it also leaves MaxPoolGrad's routing codes (4 bits
             # per pooled element), so the backward pass does not re-read the pre-pool activation
@@ -289,7 +357,7 @@ class VggEngine(object):
                         if L.variant == "mask":
                             out = (P(y[b0:]), 1, P(mk))
                         elif L.variant == "pool":
-                            out = (P(y[b0:]), P(yp[b0:]), P(pool_bits[b0 * (H // 2) * (W // 2) * (co // 8):]))
+                            out = (P(y[b0:]) if y is not None else None, P(yp[b0:]), P(pool_bits[b0 * (H // 2) * (W // 2) * (co // 8):]))
                         else:
                             out = (P(y[b0:]), P(yp[b0:]) if pooled else None, 1)
                         fn, va = self._wino(L.family, {"mask": "fwd_mask_f32", "pool": "fwd_pool_f32", "plain": "fwd_f32"}[L.variant], L.fwd_v, ch)
@@ -303,10 +371,10 @@ class VggEngine(object):
                         lib.vc_nhwc_to_c4_f32(sh, nb, H, W, co, P(yn), P(y[b0:]))
                         if pooled:   # (B * co / 4 planes of H x W four-channel pixels: the NHWC kernel on C4 data)
                             lib.vc_maxpool2x2_fwd_f32(sh, nb * (co // 4), H, W, 4, P(y[b0:]), P(yp[b0:]))
-            self.acts.append((name, x, H, W, cie, co, w))
+            self._acts.append((name, x, H, W, cie, co, w))
             x = y
             if pooled:
-                self.acts.append(("P", x, H, W, co, co, pool_bits))
+                self._acts.append(("P", x, H, W, co, co, pool_bits))
                 x = yp
                 H, W = H // 2, W // 2
         if side is not None:
@@ -396,8 +464,8 @@ class VggEngine(object):
             main.wait_event(self.packed_bwd)
         if split:
             side.wait_stream(main)
-        for li in range(len(self.acts) - 1, -1, -1):
-            name, x, H, W, ci, co, w = self.acts[li]
+        for li in range(len(self._acts) - 1, -1, -1):
+            name, x, H, W, ci, co, w = self._acts[li]
             if name == "P":
                 dx = self._b("dx_%d" % li, (B, co // 4, H, W, 4))
                 for b0, nb, strm in halves:
@@ -441,7 +509,7 @@ class VggEngine(object):
                 if after_layer is not None and after_layer[0] == name:
                     after_layer[1]()
             if li > 0:
-                prev_is_pool = self.acts[li - 1][0] == "P"
+                prev_is_pool = self._acts[li - 1][0] == "P"
                 dx = self._b("dx_%d" % li, (B, ci // 4, H, W, 4))
                 for ch, (b0, nb, strm) in enumerate(halves):
                     tws = self._chain_ws(ch, nb, plan.tail_ws_bytes[1])
@@ -457,7 +525,7 @@ class VggEngine(object):
                             continue
                         if L.dgrad == "bits":
                             # ReluGrad from the bits the previous layer's forward left (one 8-byte load per lane instead of sixteen 16-byte ones)
-                            relu = P(self.buf["mk_%s_%d" % (self.acts[li - 1][0], ch)])
+                            relu = P(self.buf["mk_%s_%d" % (self._acts[li - 1][0], ch)])
                         else:
                             relu = None if prev_is_pool else P(x[b0:])
                         fn, va = self._wino(L.dgrad_family, {"bits": "dgrad_bits_f32", "plain": "dgrad_f32"}[L.dgrad], L.dgrad_v, ch)
@@ -538,6 +606,8 @@ class Trainer(object):
         if self.fine:
             self.vgg = VggEngine(p, device, self.lib, grad_backing=self.gall[n_cap:], seed=seed, rank=rank)
             self.vgg.precision = self.precision
+            self.vgg.pool_store_y = os.environ.get("VC_POOL_STORE_Y", "0") == "1"   # (VggEngine.pool_store_y; 1: A/B runs, checkers that read y_<name>)
+            self.vgg.wino4v_f32 = "fwd"   # (VggEngine.wino4v_f32: the f32 forward of conv4_x / conv5_x on the once-transformed input)
             if self.vgg.wd:
                 self.cap.reg_scale = self.vgg.wd / 2.0  # l2_regularizer(wd)(w) = wd * sum(w^2)/2
         self.images = None

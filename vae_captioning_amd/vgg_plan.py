@@ -51,7 +51,8 @@ def conv_plan(lib, B, H, W, *, train, chains, precision, use_wino, use_conv1, wi
                  "gemm"; none when not training.  "bits" only where the layer below left a mask (so it is not pooled) in this family's
                  lane order, both passes launch over the same images (same batch per launch, same number of chains) and the shape fits
                  one launch.
-      wino4v     a wino4 launch takes the once-transformed input where wino4v and vc_conv3x3_wino4v_preferred for that launch.
+      wino4v     a wino4 launch takes the once-transformed input where wino4v and vc_conv3x3_wino4v_preferred for that launch
+                 (wino4v == "fwd": the forward launches only).
       wgrad      conv1_1: "conv1" under the forward's condition.  Cin % 64 == 0 and Cout % 64 == 0 with use_wino: "bx" (csrc/
                  conv_wgrad_bx.hip) in bf16x3 precision where wgrad_bx and supported, else "wino" (F(3x3,2x2), conv_wino_wgrad.hip)
                  where supported.  Else "gemm".
@@ -89,7 +90,7 @@ def conv_plan(lib, B, H, W, *, train, chains, precision, use_wino, use_conv1, wi
               and lib.vc_conv3x3_wino_single_launch_supported(fnb, h, w, co, co)):
             variant, words = "mask", lib.vc_conv3x3_wino4_mask_words(fnb, h, w, co)   # bits for conv1_2's F(4x4,3x3) data gradient
         fwd_v = bool(family == "wino4" and wino4v and lib.vc_conv3x3_wino4v_preferred(fnb, h, w, cie, co, 0))
-        dgrad_v = bool(dfam == "wino4" and wino4v and lib.vc_conv3x3_wino4v_preferred(bnb, h, w, cie, co, 1))
+        dgrad_v = bool(dfam == "wino4" and wino4v and wino4v != "fwd" and lib.vc_conv3x3_wino4v_preferred(bnb, h, w, cie, co, 1))
         fwd_vb = lib.vc_conv3x3_wino4v_workspace_bytes(fnb, h, w, cie) if fwd_v else 0
         dgrad_vb = lib.vc_conv3x3_wino4v_workspace_bytes(bnb, h, w, co) if dgrad_v else 0
         if li == 0:
