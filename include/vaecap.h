@@ -259,6 +259,21 @@ int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const float* ce_d
                             const float* kl_sum, float inv_n, const float* ann, float kl_coef, float* out4);
 
 /* ------------------------------------------------------------------------------------
+ * Self-critical training (additive in ABI 4; DESIGN.md "Self-critical training"): the policy-gradient loss of sampled captions.
+ * Rows are time-major [T, N] (rows % N == 0): row r belongs to caption n = r % N with advantage adv[n] (device, [N]).  A row is
+ * live when 0 < label < V.  With p = softmax(x) over the V real columns, lse = log sum exp x and H = lse - sum_v p_v x_v:
+ *   row_lp[r]  = live ? x[label] - lse : 0                (log-probability of the token taken)
+ *   row_ent[r] = live ? H : 0                              (beta > 0 only; may be NULL with beta == 0)
+ *   write_grad: logits[r, v] <- live * scale * (adv[n] * (p_v - [v == label]) + beta * p_v * ((x_v - lse) + H)) for v < V and
+ *   exactly 0 for the pitch padding V <= v < ld: the gradient of J = scale * sum_live (-adv[n] * log p(label) - beta * H).
+ * H is computed from x (never as log p_v): an underflowed p_v contributes exactly 0.  Same two kernels and dispatch rule as
+ * vc_softmax_xent_f32; beta == 0 runs them without the entropy arithmetic.
+ * ---------------------------------------------------------------------------------- */
+int vc_softmax_xent_policy_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
+                               const float* adv, int N, float scale, float beta,
+                               float* row_lp, float* row_ent, int write_grad);
+
+/* ------------------------------------------------------------------------------------
  * Small data-movement ops.
  *   colsum       out[c] (+)= sum_r x[r,c]                (bias gradients)
  *   dropout      y = x*mask/keep                          (tf.nn.dropout, decoder.py:85-87, rnn_model.py:45-46)

@@ -205,6 +205,28 @@ def main(params):
         drop_rng = np.random.default_rng([params.seed, 7919, rank]) if params.word_drop > 0 else None
         unk = objective.unk_id(cap_dict.word2idx, params.vocab_size)
 
+        if params.scst:   # self-critical training: every step below is a Trainer.scst_step (DESIGN.md "Self-critical training")
+            if world > 1:
+                raise SystemExit("--scst is single-GPU: not in a data-parallel run (WORLD_SIZE = %d)" % world)
+            if not params.restore:
+                say("Warning: --scst without --restore starts self-critical training from random weights; it is meant to "
+                    "fine-tune a cross-entropy-trained checkpoint")
+            from vae_captioning_amd.scst import CiderReward
+            if real is not None:
+                corpus = [real.caps[n] for n in real.names if real.caps[n]]
+            elif coco_train is not None:
+                from vae_captioning_amd.consensus import captions_from_generator
+                corpus = [c for c in captions_from_generator(coco_train) if c]
+            else:
+                corpus = training_index_data(params, None)[1]
+            bos, eos = cap_dict.word2idx["<BOS>"], cap_dict.word2idx["<EOS>"]
+            say("SCST: document frequencies from %d training images, baseline %s, entropy weight %g" % (len(corpus), params.scst_baseline, params.scst_entropy))
+            tr.enable_scst(CiderReward(cap, corpus, bos, eos, cap_dict.vocab_size), bos, eos, baseline=params.scst_baseline, beta=params.scst_entropy)
+
+        def say_scst(e, it):
+            s = tr.scst_stats
+            say("Epoch: {} Iteration: {} SCST: reward: {} baseline: {} sample_len: {} entropy: {}".format(e, it, s["reward"], s["baseline"], s["sample_len"], s["entropy"]))
+
         def say_objective():   # --kl_free_bits: what the floor does, beside the losses
             if cap.free_bits > 0:
                 o = tr.objective_stats()
@@ -221,6 +243,12 @@ def main(params):
                     continue  # ragged last batch: shapes are static on device
                 if drop_rng is not None:
                     batch = dict(batch, cap_dec=objective.word_dropout(batch["cap_dec"], batch["lengths"], params.word_drop, unk, drop_rng))
+                if params.scst:
+                    tr.scst_step(batch)
+                    gs += 1
+                    if (gs - 1) % 500 == 0:
+                        say_scst(e, gs - 1)
+                    continue
                 tr.set_batch(batch)
                 # ---- one sess.run([kld, rec_loss, lower_bound, optimize, optimize_cnn, annealing]) ----
                 feats = None
@@ -243,10 +271,14 @@ def main(params):
                     if not params.no_encoder:
                         say("Annealing coefficient:{} KLD: {}".format(ann, kl))
                         say_objective()
-            kl, rl, lb, ann = tr.losses()
-            say("Epoch: {} Iteration: {} VLB: {} Rec Loss: {}".format(e, int(global_step.item()), lb, rl))
-            if not params.no_encoder:
-                say_objective()
+            if params.scst:
+                if tr.scst_stats is not None:
+                    say_scst(e, int(global_step.item()))
+            else:
+                kl, rl, lb, ann = tr.losses()
+                say("Epoch: {} Iteration: {} VLB: {} Rec Loss: {}".format(e, int(global_step.item()), lb, rl))
+                if not params.no_encoder:
+                    say_objective()
             # validate(): rec_loss of the training graph on held-out batches (main.py:262-284)
             val = []
             held_out = coco_batches(coco_val, params) if coco_val is not None else SyntheticBatches(params, 4, params.seed + 99991 + rank).next_batch()

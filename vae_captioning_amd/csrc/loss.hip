@@ -646,6 +646,136 @@ __global__ void loss_finalize_kl_kernel(const float* ce_num, const float* ce_den
     out[3] = a;
 }
 
+// =======================================================================================
+// Self-critical training (DESIGN.md "Self-critical training"): the policy-gradient loss of SAMPLED captions.  Rows are time-major
+// [T, N]; row r belongs to caption n = r % N, whose advantage adv[n] weights the log-probability of every token it took:
+//   J = scale * sum over live rows ( -adv[n] * log p(label) - beta * H ),   H = lse - sum_v p_v x_v  (the row's entropy)
+//   row_lp = live * (x[label] - lse),  row_ent = live * H
+//   dlogits[v] = live * scale * ( adv[n] * (p_v - [v == label]) + beta * p_v * ((x_v - lse) + H) )   (v < V), exactly 0 for V <= v < ld
+// live = 0 < label < V.  The row is held as d_v = x_v - max (ENT) or exp(d_v) (plain): with H = log s - (sum_v e^d_v d_v) / s and
+// x_v - lse = d_v - log s nothing is ever the logarithm of a probability, so an underflowed p_v adds exactly 0.  ENT = false
+// (beta == 0) compiles the entropy arithmetic away: the kernel is then xent_smooth_reg_kernel's at eps = 0 with a per-row scale.
+// =======================================================================================
+template <bool WRITE_GRAD, bool ENT>
+__global__ __launch_bounds__(256) void xent_policy_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                              int V, long ld, const float* __restrict__ adv, int N, float scale,
+                                                              float beta, float* __restrict__ row_lp, float* __restrict__ row_ent) {
+    __shared__ float sh[4];
+    const long row = blockIdx.x;
+    float4* p = reinterpret_cast<float4*>(logits + row * ld);
+    const int V4 = (V + 3) >> 2;
+    const int label = labels[row];
+    float4 x[XENT_MAXQ];
+    // straight-line loads, as in xent_smooth_reg_kernel: a thread past the row's last quad re-reads that quad, its lanes are masked below
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {
+        const int c = ((int)threadIdx.x + q * 256) * 4;
+        // columns >= V (the pitch padding, and every lane of a thread past the row) do not exist: -inf for max and exp
+        x[q].x = c < V ? x[q].x : -INFINITY; x[q].y = c + 1 < V ? x[q].y : -INFINITY;
+        x[q].z = c + 2 < V ? x[q].z : -INFINITY; x[q].w = c + 3 < V ? x[q].w : -INFINITY;
+        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
+    }
+    mx = block_max<256>(mx, sh);
+    float s = 0.f, sd = 0.f;   // sum e^d, sum e^d * d
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {   // (exp(-inf) = 0: the masked lanes add nothing)
+        const float d0 = x[q].x - mx, d1 = x[q].y - mx, d2 = x[q].z - mx, d3 = x[q].w - mx;
+        const float e0 = __expf(d0), e1 = __expf(d1), e2 = __expf(d2), e3 = __expf(d3);
+        s += (e0 + e1) + (e2 + e3);
+        if (ENT) {   // a term whose e^d is 0 (masked: d = -inf; underflowed: d finite) is exactly 0, never 0 * -inf
+            sd += ((e0 > 0.f ? e0 * d0 : 0.f) + (e1 > 0.f ? e1 * d1 : 0.f)) + ((e2 > 0.f ? e2 * d2 : 0.f) + (e3 > 0.f ? e3 * d3 : 0.f));
+            x[q] = make_float4(d0, d1, d2, d3);
+        } else {
+            x[q] = make_float4(e0, e1, e2, e3);
+        }
+    }
+    s = block_sum<256>(s, sh);
+    if (ENT) sd = block_sum<256>(sd, sh);
+    const bool live = label > 0 && label < V;
+    const float logs = __logf(s);
+    const float H = ENT ? logs - sd / s : 0.f;
+    if (threadIdx.x == 0) {
+        row_lp[row] = live ? (logits[row * ld + label] - mx) - logs : 0.f;
+        if (ENT) row_ent[row] = live ? H : 0.f;
+    }
+    if (WRITE_GRAD) {
+        __syncthreads();  // thread 0 has read logits[label] before anyone overwrites it
+        const float ka = live ? scale * adv[row % N] : 0.f, kb = live ? scale * beta : 0.f;
+        const float inv = 1.f / s, hb = H - logs;
+        // branch-free patch of the label's column, as in xent_smooth_reg_kernel.  lq: which of this thread's quads holds the label
+        const bool own = live && (int)threadIdx.x == ((label >> 2) & 255);
+        const int lq = own ? (label >> 10) : -1, lc = label & 3;
+        const float a0 = lc == 0 ? ka : 0.f, a1 = lc == 1 ? ka : 0.f, a2 = lc == 2 ? ka : 0.f, a3 = lc == 3 ? ka : 0.f;
+#pragma unroll
+        for (int q = 0; q < XENT_MAXQ; ++q) {
+            const int i = threadIdx.x + q * 256;
+            if (i < V4) {
+                const float m = q == lq ? 1.f : 0.f;
+                float4 g;
+                if (ENT) {   // p_v * (ka + kb * ((d_v - log s) + H)); p_v == 0 -> exactly 0 (a masked lane's d is -inf)
+                    const float p0 = __expf(x[q].x) * inv, p1 = __expf(x[q].y) * inv, p2 = __expf(x[q].z) * inv, p3 = __expf(x[q].w) * inv;
+                    g.x = p0 > 0.f ? p0 * (ka + kb * (x[q].x + hb)) : 0.f; g.y = p1 > 0.f ? p1 * (ka + kb * (x[q].y + hb)) : 0.f;
+                    g.z = p2 > 0.f ? p2 * (ka + kb * (x[q].z + hb)) : 0.f; g.w = p3 > 0.f ? p3 * (ka + kb * (x[q].w + hb)) : 0.f;
+                } else {
+                    const float k = ka * inv;
+                    g = make_float4(x[q].x * k, x[q].y * k, x[q].z * k, x[q].w * k);
+                }
+                p[i] = make_float4(g.x - m * a0, g.y - m * a1, g.z - m * a2, g.w - m * a3);
+            }
+        }
+        // the last quad's padding columns and the quads of the pitch past it: exactly 0 (written by the thread that stored that quad)
+        float* r = logits + row * ld;
+        if ((int)threadIdx.x == ((V4 - 1) & 255))
+            for (int c = V; c < V4 * 4; ++c) r[c] = 0.f;
+        const int L4 = (int)(ld >> 2);
+        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
+    }
+}
+
+// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
+template <bool WRITE_GRAD, bool ENT>
+__global__ __launch_bounds__(256) void xent_policy_mem_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                              int V, long ld, const float* __restrict__ adv, int N, float scale,
+                                                              float beta, float* __restrict__ row_lp, float* __restrict__ row_ent) {
+    __shared__ float sh[4];
+    const long row = blockIdx.x;
+    float* p = logits + row * ld;
+    const int label = labels[row];
+    float mx = -INFINITY;
+    for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, p[c]);
+    mx = block_max<256>(mx, sh);
+    float s = 0.f, sd = 0.f;
+    for (int c = threadIdx.x; c < V; c += 256) {
+        const float d = p[c] - mx, e = __expf(d);
+        s += e;
+        if (ENT) sd += e > 0.f ? e * d : 0.f;
+    }
+    s = block_sum<256>(s, sh);
+    if (ENT) sd = block_sum<256>(sd, sh);
+    const bool live = label > 0 && label < V;
+    const float logs = __logf(s);
+    const float H = ENT ? logs - sd / s : 0.f;
+    if (threadIdx.x == 0) {
+        row_lp[row] = live ? (p[label] - mx) - logs : 0.f;
+        if (ENT) row_ent[row] = live ? H : 0.f;
+    }
+    if (WRITE_GRAD) {
+        __syncthreads();
+        const float ka = live ? scale * adv[row % N] : 0.f, kb = live ? scale * beta : 0.f;
+        const float inv = 1.f / s, hb = H - logs;
+        for (int c = threadIdx.x; c < V; c += 256) {
+            const float d = p[c] - mx, pv = __expf(d) * inv;
+            float g = ENT ? (pv > 0.f ? pv * (ka + kb * (d + hb)) : 0.f) : pv * ka;
+            if (c == label) g -= ka;
+            p[c] = g;
+        }
+        for (long c = V + threadIdx.x; c < ld; c += 256) p[c] = 0.f;
+    }
+}
+
 }  // namespace vc
 
 using namespace vc;
@@ -814,6 +944,32 @@ extern "C" int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const 
     VC_CHECK_ARG(ce_num && ce_den && out4, "null pointer");
     hipLaunchKernelGGL(loss_finalize_kl_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ce_num, ce_den, reg_sumsq, reg_scale, kl_sum, inv_n,
                        ann, kl_coef, out4);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- self-critical training: the policy-gradient loss (dispatch rule: vc_softmax_xent_f32's; beta == 0 runs the kernels without
+// the entropy arithmetic, row_ent may then be NULL)
+extern "C" int vc_softmax_xent_policy_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
+                                          const float* adv, int N, float scale, float beta, float* row_lp, float* row_ent, int write_grad) {
+    VC_CHECK_ARG(logits && labels && adv && row_lp && rows >= 0 && V > 0 && ld >= V, "bad argument");
+    VC_CHECK_ARG(N > 0 && rows % N == 0, "rows must be a multiple of N (time-major [T, N] rows)");
+    VC_CHECK_ARG(beta >= 0.f && beta < INFINITY && scale == scale && fabsf(scale) < INFINITY, "beta must be finite and >= 0, scale finite");
+    VC_CHECK_ARG(beta == 0.f || row_ent, "row_ent required with beta > 0");
+    if (rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
+    const bool ent = beta > 0.f;
+    dim3 g((unsigned)rows), b(256);
+#define VC_POLICY_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, st, logits, labels, V, ld, adv, N, scale, beta, row_lp, row_ent)
+    if (reg) {
+        if (write_grad) { if (ent) VC_POLICY_LAUNCH((xent_policy_reg_kernel<true, true>)); else VC_POLICY_LAUNCH((xent_policy_reg_kernel<true, false>)); }
+        else { if (ent) VC_POLICY_LAUNCH((xent_policy_reg_kernel<false, true>)); else VC_POLICY_LAUNCH((xent_policy_reg_kernel<false, false>)); }
+    } else {
+        if (write_grad) { if (ent) VC_POLICY_LAUNCH((xent_policy_mem_kernel<true, true>)); else VC_POLICY_LAUNCH((xent_policy_mem_kernel<true, false>)); }
+        else { if (ent) VC_POLICY_LAUNCH((xent_policy_mem_kernel<false, true>)); else VC_POLICY_LAUNCH((xent_policy_mem_kernel<false, false>)); }
+    }
+#undef VC_POLICY_LAUNCH
     VC_LAUNCH_CHECK();
     return 0;
 }

@@ -235,6 +235,11 @@ class CaptionEngine(object):
         if self.kl_cycle[0] > 0:
             self.ann_on = 0   # the cyclical schedule owns the coefficient (also under --restore / --fine_tune: Q10 is about the tanh one)
         self.ostat = torch.zeros(2, **f32) if self.free_bits > 0 else None   # vc_objective_stats_f32: mean unclamped KL, floored share
+        # Self-critical training (DESIGN.md "Self-critical training"): True while a policy step prepares its forward -- z is GIVEN (no eps,
+        # no GMM draw); everything else off = the training step as it was
+        self.policy = False
+        self.policy_beta = 0.0
+        self.pstat = torch.zeros(4, **f32)    # policy step: [0] sum row_lp, [1] live rows, [2] sum row_ent
 
     def _reduce_scatter(self, out, inp):
         """sum-reduce-scatter of inp [world*n, L] into out [n, L] (RCCL; backends without the primitive,
@@ -588,7 +593,7 @@ class CaptionEngine(object):
         """Device-generated noise when none was injected (Philox, advanced by the step counter)."""
         p, lib, st = self.p, self.lib, _stream()
         S, N, L, T = p.gen_z_samples, self.N, p.latent_size, self.T
-        if self.enc:
+        if self.enc and not self.policy:   # (a policy step is handed its z: no encoder sample)
             eps = self._b("eps", (S, N, L))
             lib.vc_philox_normal_f32(st, P(eps), eps.numel(), self.seed * 1000003 + self.rank, 1 << 32, P(self.step))
         if p.dec_keep_rate < 1:
@@ -597,7 +602,7 @@ class CaptionEngine(object):
         if p.dec_lstm_drop < 1:
             m = self._b("drop_out", (T, N, p.decoder_hidden))
             lib.vc_philox_bernoulli_f32(st, P(m), m.numel(), p.dec_lstm_drop, self.seed * 1000003 + self.rank, 3 << 32, P(self.step))
-        if self.gmm_draw:  # encoder.py:72-75: component index ~ Categorical(softmax(c_v)) per row
+        if self.gmm_draw and not self.policy:  # encoder.py:72-75: component index ~ Categorical(softmax(c_v)) per row
             u = self._b("gmm_u", (N,))
             lib.vc_philox_uniform_f32(st, P(u), N, self.seed * 1000003 + self.rank, 4 << 32, P(self.step))
             lib.vc_multinomial_rows_f32(st, P(self.buf["c_v"]), N, K_CL, K_CL, 1.0, P(u), P(self._b("gmm_idx", (N,), torch.int32)))
@@ -819,8 +824,11 @@ class CaptionEngine(object):
                                      P(ann) if self.enc else None, P(self.out))
 
     # ---------------------------------------------------------------- backward
-    def backward(self, want_dfeatures=False):
-        """Gradients of sum(lower_bound) w.r.t. every non-CNN variable, into store.g."""
+    def backward(self, want_dfeatures=False, policy=False):
+        """Gradients of sum(lower_bound) w.r.t. every non-CNN variable, into store.g.
+        policy: the backward pass of policy_forward -- z was given, so the pass ends at the z step of the decoder: z_rnn's weight
+        gradient is the last thing z reaches; no dz, no latent / heads / encoder-LSTM gradients (the encoder/* ranges of store.g keep
+        whatever an earlier step left there and are read by nobody: policy_apply_gradients)."""
         p, lib, st, S = self.p, self.lib, _stream(), self.store
         N, T, B, nc = self.N, self.T, self.B, self.nc
         E, He, Hd, L, Sm, V, F = p.embed_size, p.encoder_hidden, p.decoder_hidden, p.latent_size, p.gen_z_samples, self.V, p.cnn_feature_size
@@ -876,6 +884,7 @@ class CaptionEngine(object):
             dz_dec = dXd[zi]
             z = self.buf["z"]
             side(lambda: self.dense_bwd_w(z, N, Sm * L, E, dz_dec, "decoder/net/z_rnn/kernel", "decoder/net/z_rnn/bias"))
+        if self.enc and not policy:
             dz = self._b("dz", (Sm, N, L))
             self.gemm(0, 1, N, Sm * L, E, dz_dec, E, S.param("decoder/net/z_rnn/kernel"), E, dz, Sm * L)
             mean, std = self.buf["mean"], self.buf["std"]
@@ -970,6 +979,120 @@ class CaptionEngine(object):
         part = self._b("embpart_" + key, (max(nsub, 1), E))
         lib.vc_embedding_grad_sorted_f32(st, P(part), P(self.buf["order_" + key]), P(seg1), E, nsub, P(dX))
         lib.vc_embedding_grad_sorted_f32(st, P(self.store.grad(name)), None, P(seg2), E, self.V, P(part))
+
+    # ---------------------------------------------------------------- self-critical (policy-gradient) step
+    def _policy_check(self):
+        if self.collectives:
+            raise RuntimeError("the policy (self-critical) step is single-GPU: not in a data-parallel run (world > 1 or forced collectives)")
+        if self.p.fine_tune:
+            raise RuntimeError("the policy (self-critical) step does not train the VGG16 (--fine_tune): no CNN backward from the policy loss")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("the policy (self-critical) step cannot be captured into a hipGraph (its batch shape follows the samples)")
+
+    def policy_ranges(self):
+        """The trained ranges [(offset, floats)] of the flat store in a policy step: the dense prefix in front of encoder/* (cv_emb only
+        where it is fed, imf_emb, the decoder cell, z_rnn, rnn_logits) and the dec_embeddings table.  encoder/* is off the loss path."""
+        S = self.store
+        lo = 0 if (self.feed_cv or not self.use_ci) else S.offset("imf_emb/kernel")
+        hi = S.offset(spec.ENC_CELL + "kernel") if self.enc else self.n_dense
+        off, shape = S.offsets["decoder/net/dec_embeddings"]
+        return (lo, hi - lo), (off, _round(int(np.prod(shape))))
+
+    def policy_forward(self, adv, z=None, beta=0.0, features=None):
+        """Forward pass of a policy-gradient step on the uploaded batch of SAMPLED captions (set_batch: cap_dec = <BOS> + sampled words,
+        cap_enc = the sampled words (+ <EOS> if the sample ended), lengths = their number) + in-place d(J)/d(logits),
+        J = 1/N sum over the sampled tokens (-adv[n] log p(token) - beta H).  adv: [N] advantages (host or device); z: the [N, S*L]
+        (any shape of N*S*L elements) latent rows the captions were sampled under -- row n = b*nc + k is what z_rnn is fed for row n;
+        the encoder does not run, there is no KL.  Models without an encoder take no z.  Advances the global step like any training
+        step.  Returns the loss scalars buffer (rec_loss = lower_bound = mean -log p per sampled token, kld = 0)."""
+        self._policy_check()
+        p, lib = self.p, self.lib
+        if not (0.0 <= float(beta) < float("inf")):
+            raise ValueError("beta must be finite and >= 0 (got %r)" % (beta,))
+        N, L, Sm = self.N, p.latent_size, p.gen_z_samples
+        n_adv = adv.numel() if isinstance(adv, torch.Tensor) else int(np.size(adv))   # (every argument is checked before the step counter moves)
+        if n_adv != N:
+            raise ValueError("%d advantages for %d caption rows" % (n_adv, N))
+        if self.enc:
+            if z is None:
+                raise ValueError("a policy step of a model with an encoder needs the z its captions were sampled under")
+            if not isinstance(z, torch.Tensor):
+                z = torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32))
+            if z.numel() != N * Sm * L:
+                raise ValueError("z holds %d values, the %d caption rows need %d x %d x %d" % (z.numel(), N, N, Sm, L))
+        self.policy = True
+        try:
+            self.fw_prepare(features, True)
+        finally:
+            self.policy = False
+        if self.enc:
+            self._b("z", (Sm, N, L)).view(-1).copy_(z.reshape(-1))
+        self.fw_decode()
+        return self.fw_policy_loss(adv, beta)
+
+    def fw_policy_loss(self, adv, beta=0.0):
+        """vc_softmax_xent_policy_f32 on the logits of fw_decode (gradient in place, scale 1 / N) + the step's reporting sums."""
+        lib, st = self.lib, _stream()
+        N, T, V = self.N, self.T, self.V
+        if not isinstance(adv, torch.Tensor):
+            adv = torch.from_numpy(np.ascontiguousarray(adv, dtype=np.float32))
+        if adv.numel() != N:
+            raise ValueError("%d advantages for %d caption rows" % (adv.numel(), N))
+        advd = self._b("adv", (N,))
+        advd.copy_(adv.reshape(-1))
+        logits, labels = self.buf["logits"], self.buf["cap_enc_t"]
+        row_lp = self._b("row_lp", (T * N,))
+        row_ent = self._b("row_ent", (T * N,)) if beta > 0 else None
+        self.policy_beta = float(beta)
+        self._timed("hbm_softmax_xent", 8.0 * T * N * V,
+                    lambda: lib.vc_softmax_xent_policy_f32(st, P(logits), P(labels), T * N, V, _round(V, 4), P(advd), N, 1.0 / N, float(beta),
+                                                           P(row_lp), P(row_ent), 1))
+        # reporting: per-caption log-probabilities (column sums of the [T, N] rows), their total, the live rows, the entropy sum
+        self.colsum(row_lp, T, N, self._b("cap_lp", (N,)))
+        lib.vc_reduce_sum_f32(st, P(row_lp), T * N, 1.0, P(self.pstat), 0)
+        lib.vc_count_nonzero_i32(st, P(labels), T * N, self.pstat.data_ptr() + 4)
+        if row_ent is not None:
+            lib.vc_reduce_sum_f32(st, P(row_ent), T * N, 1.0, self.pstat.data_ptr() + 8, 0)
+        lib.vc_reduce_sum_f32(st, P(row_lp), T * N, -1.0, P(self.red), 0)
+        self.red[1:2].copy_(self.pstat[1:2])
+        self._losses_deferred = False
+        lib.vc_loss_finalize_f32(st, P(self.red), self.red.data_ptr() + 4, None, 0.0, None, 1.0 / N, P(self.scal[1:2]) if self.enc else None, P(self.out))
+        return self.out
+
+    def policy_stats(self):
+        """{"logprob": mean log-probability of a sampled caption, "entropy": mean row entropy over the sampled tokens (None with
+        beta == 0), "tokens": sampled tokens} of the last policy forward."""
+        o = self.pstat.detach().cpu().numpy()
+        live = max(float(o[1]), 1.0)
+        return {"logprob": float(o[0]) / self.N, "entropy": float(o[2]) / live if self.policy_beta > 0 else None, "tokens": int(o[1])}
+
+    def policy_apply_gradients(self):
+        """apply_gradients for a policy step: the global-norm clip over the TRAINED variables only (policy_ranges + the IndexedSlices
+        term of dec_embeddings, Q5) and the optimiser on those ranges of the flat store alone -- tf.train.Optimizer skips a variable
+        whose gradient is None, so the parameters and the slots of encoder/* stay as they are, bit for bit."""
+        p, lib, st, S, nb = self.p, self.lib, _stream(), self.store, self.nb
+        self.param_updates += 1
+        (lo, n), (eo, en) = self.policy_ranges()
+        at = lambda t, o: t.data_ptr() + o * 4
+        lib.vc_sumsq_partial_f32(st, at(S.g, lo), n, P(self.part))
+        self.part[nb:nb + 1].copy_(S.g[S.n:S.n + 1])   # pack_tail: sum ||dX||^2 of dec_embeddings (the encoder table's share is 0)
+        lib.vc_clip_finalize_f32(st, P(self.part), nb + 1, float(p.lstm_clip_by_norm), P(self.ns))
+        scale = self.ns.data_ptr() + 4
+        if p.optimizer == "Adam":
+            m, v = S.slot("m"), S.slot("v")
+            for o, k in ((lo, n), (eo, en)):
+                lib.vc_adam_f32(st, at(S.p, o), at(S.g, o), at(m, o), at(v, o), k, P(self.scal), scale, 0.8, 0.999, 1e-8, 0.0)
+        elif p.optimizer == "SGD":
+            for o, k in ((lo, n), (eo, en)):
+                lib.vc_sgd_f32(st, at(S.p, o), at(S.g, o), k, self.scal.data_ptr() + 8, scale, 0.0)
+        else:
+            a = S.slot("a")
+            lr = self.scal.data_ptr() + 8
+            lib.vc_momentum_f32(st, at(S.p, lo), at(S.g, lo), at(a, lo), n, lr, scale, 0.9, 0.0, None, 0)
+            shape = S.offsets["decoder/net/dec_embeddings"][1]
+            touched = self._b("touched_cap_dec_t", (self.V,), zero=True)
+            lib.vc_mark_rows_f32(st, P(touched), P(self.buf["cap_dec_t"]), self.T * self.N, self.V)
+            lib.vc_momentum_f32(st, at(S.p, eo), at(S.g, eo), at(a, eo), shape[0] * shape[1], lr, scale, 0.9, 0.0, P(touched), shape[1])
 
     # ---------------------------------------------------------------- optimiser
     def pack_tail(self):

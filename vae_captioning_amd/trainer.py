@@ -830,6 +830,121 @@ class Trainer(object):
         else:
             self._step()
 
+    # ------------------------------------------------------------------ self-critical training (scst.py; DESIGN.md "Self-critical training")
+    def enable_scst(self, reward, bos, eos, baseline="average", beta=0.0, max_len=None):
+        """Make scst_step available.  reward: a scst.CiderReward; baseline: "average" (the image's other samples) or "greedy" (the
+        greedy decode under the same z); beta: weight of the token-entropy bonus (>= 0); max_len: longest sample (default gen_max_len)."""
+        from . import scst
+        from .generate import CaptionGenerator
+        p = self.p
+        if self.fine:
+            raise RuntimeError("self-critical training does not train the VGG16: not with --fine_tune")
+        if self.collectives:
+            raise RuntimeError("self-critical training is single-GPU: not in a data-parallel run")
+        if p.mode != "training":
+            raise RuntimeError("self-critical training needs --mode training")
+        if float(p.temperature) != 1.0:
+            raise ValueError("self-critical training samples at temperature 1: the policy gradient needs the probabilities of the "
+                             "distribution that was sampled (got %r)" % (p.temperature,))
+        scst.check_baseline(baseline, p.num_captions)
+        if not (0.0 <= float(beta) < float("inf")):
+            raise ValueError("the entropy weight must be finite and >= 0 (got %r)" % (beta,))
+        self.scst = dict(reward=reward, bos=int(bos), eos=int(eos), baseline=baseline, beta=float(beta), max_len=int(max_len or p.gen_max_len),
+                         gen=CaptionGenerator(self.cap))
+        self.scst_stats = None
+        self.scst_times = None   # a dict: scst_step adds the host-clock seconds of its phases (tools/scst_time.py; synchronises per phase)
+
+    def scst_sample(self, batch, method="sample", eps=None, uniforms=None):
+        """The K = num_captions captions of every image of `batch` decoded under K prior draws: -> (per image its K candidates
+        (tokens incl. <EOS> when ended, logprob, ended) in draw order, i.e. caption row b*K + k; the z rows [B*K, S, L] they were decoded
+        under -- the sampler's own device buffer, valid until its next pass; None without an encoder).
+        eps [K, S, B, L] / uniforms [K, max_len, B]: injected draws (Philox on the device step counter when None: a "greedy" pass that
+        follows a "sample" pass of the same step decodes under the same z)."""
+        from .engine import K_CL
+        sc, p, cap = self.scst, self.p, self.cap
+        gen, K = sc["gen"], int(p.num_captions)
+        feats = np.asarray(batch["features"], np.float32)
+        B = feats.shape[0]
+        if B * K > gen.diverse_rows:
+            raise ValueError("%d images x %d samples exceed the sampler's %d rows per pass" % (B, K, gen.diverse_rows))
+        c_v = np.asarray(batch["c_v"], np.float32).reshape(B, K, K_CL)[:, 0] if cap.use_ci else None   # (batches carry c_v tiled to rows)
+        _, cands = gen._diverse_pass(feats, c_v, eps, K, method, sc["bos"], sc["eos"], sc["max_len"], 0.7, None, uniforms, 4)
+        return cands, (gen.buf["dvi%d_%d_z" % (B, K)] if cap.enc else None)
+
+    def policy_step(self, adv, z=None, beta=0.0):
+        """One policy-gradient step on the uploaded batch of sampled captions (CaptionEngine.policy_forward / backward(policy) /
+        policy_apply_gradients), with the step's off-chain structure: weight gradients, clip and optimiser on the weight-gradient stream."""
+        cap = self.cap
+        if self.graph is not None:
+            raise RuntimeError("a trainer whose step was captured into a hipGraph cannot run policy steps (the graph bakes the XE step's inputs)")
+        import time
+        times = getattr(self, "scst_times", None)   # (a dict: this step's phases on the host clock, each closed by a device synchronise)
+        t0 = time.perf_counter()
+        self._range("policy_forward")
+        cap.policy_forward(adv, z, beta)
+        self._range("policy_backward")
+        cap.backward(policy=True)
+        with cap.off_chain():
+            cap.pack_tail()
+        if times is not None:
+            cap.join_off_chain()
+            torch.cuda.synchronize()
+            times["policy_fwd_bwd"] = times.get("policy_fwd_bwd", 0.0) + time.perf_counter() - t0
+            t0 = time.perf_counter()
+        self._range("optimizers")
+        with cap.off_chain():
+            cap.policy_apply_gradients()
+        cap.join_off_chain()
+        self._range(None)
+        if times is not None:
+            torch.cuda.synchronize()
+            times["optimiser"] = times.get("optimiser", 0.0) + time.perf_counter() - t0
+
+    def scst_step(self, batch, noise=None, eps=None, uniforms=None):
+        """One self-critical step on an XE batch (features [B, F], cap_enc / lengths: the images' human captions = the references,
+        c_v): sample, (greedy baseline), rewards -> advantages, policy step.  noise: injected decoder dropout masks of the policy
+        forward (drop_in / drop_out, [T, N, .] with T = the longest sample -- tests); eps / uniforms: injected draws of the sampler.
+        Returns (and keeps in self.scst_stats) reward (mean sampled reward), baseline (mean baseline reward), sample_len, ended_share,
+        entropy (mean token entropy, None with beta == 0), logprob (mean log-probability of a sample under the policy forward)."""
+        import time
+        from . import scst
+        sc, p, cap = self.scst, self.p, self.cap
+        K = int(p.num_captions)
+        times = self.scst_times
+
+        def lap(name, t0):
+            if times is not None and name is not None:
+                torch.cuda.synchronize()
+                times[name] = times.get(name, 0.0) + time.perf_counter() - t0
+            return time.perf_counter()
+        t = lap(None, 0.0)
+        cands, z = self.scst_sample(batch, "sample", eps, uniforms)
+        if z is not None:
+            z = z.clone()   # (the greedy pass runs through the same sampler buffers; equal values, but the step keeps its own copy)
+        t = lap("sample", t)
+        B = len(cands)
+        samples = [list(c[0]) for cs in cands for c in cs]
+        refs = scst.batch_references(batch["cap_enc"], batch["lengths"], K)
+        g = None
+        if sc["baseline"] == "greedy":
+            gc, _ = self.scst_sample(batch, "greedy", eps, None)
+            t = lap("greedy", t)
+            g = sc["reward"].rewards([[c[0] for c in cs] for cs in gc], refs).reshape(B, K)
+        r = sc["reward"].rewards([[c[0] for c in cs] for cs in cands], refs).reshape(B, K)
+        adv = scst.advantages(r, sc["baseline"], g)
+        t = lap("reward", t)
+        pb = scst.policy_batch(samples, sc["bos"], sc["eos"])
+        pb["features"] = batch["features"]
+        if cap.use_ci:
+            pb["c_v"] = batch["c_v"]
+        self.set_batch(pb, noise)
+        t = lap("upload", t)
+        self.policy_step(adv.reshape(-1).astype(np.float32), z, sc["beta"])
+        ps = cap.policy_stats()
+        self.scst_stats = dict(reward=float(r.mean()), baseline=float((r - adv).mean()), sample_len=float(pb["lengths"].mean()),
+                               ended_share=float(np.mean([c[2] for cs in cands for c in cs])), entropy=ps["entropy"], logprob=ps["logprob"])
+        return self.scst_stats
+
     def capture(self, warmup=2):
         """Capture the whole step into one hipGraph (removes ~300 launch latencies per step).
         Requires fixed shapes and device-generated noise; collectives stay outside graphs."""

@@ -31,6 +31,8 @@ _DEFAULTS = dict(
     no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
     # training objective options (every one off by default: the reference's objective)
     kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
+    # self-critical training (off by default)
+    scst=False, scst_baseline="average", scst_entropy=0.0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -63,6 +65,8 @@ _FLAGS = [
     ("--kl_cycle_steps", "kl_cycle_steps", int, None), ("--kl_cycle_ramp", "kl_cycle_ramp", float, None),
     ("--kl_cycles", "kl_cycles", int, None), ("--label_smoothing", "label_smoothing", float, None),
     ("--word_drop", "word_drop", float, None),
+    ("--scst", "scst", "flag", None), ("--scst_baseline", "scst_baseline", str, ["average", "greedy"]),
+    ("--scst_entropy", "scst_entropy", float, None),
 ]
 _KL_FLAGS = ("kl_free_bits", "kl_weight", "kl_cycle_steps", "kl_cycle_ramp", "kl_cycles")
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
@@ -116,6 +120,12 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                               "default 0 = off; validation losses stay unsmoothed)",
          "--word_drop": "training: each decoder input word behind <BOS> is replaced by <UNK> with this probability (in [0, 1); "
                         "default 0 = off; seeded by --seed; never in validation or inference)",
+         "--scst": "self-critical training: every training step samples num_captions captions per image, rewards them with CIDEr-D "
+                   "against the image's human captions and takes a policy-gradient step of the decoder (the encoder is left alone); "
+                   "meant for --restore from a cross-entropy-trained checkpoint; single GPU, precomputed features",
+         "--scst_baseline": "--scst: what a sample's reward is compared with -- average: the mean reward of the image's other samples "
+                            "(needs num_captions >= 2); greedy: the reward of the greedy caption under the same latent draw (default average)",
+         "--scst_entropy": "--scst: weight of the token-entropy bonus in the policy loss (finite, >= 0; default 0 = off)",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
@@ -221,6 +231,26 @@ class Parameters(object):
         if self.no_encoder and any(args[k] is not None for k in _KL_FLAGS):
             ap.error("--kl_free_bits / --kl_weight / --kl_cycle_steps / --kl_cycle_ramp / --kl_cycles shape the KL term, and "
                      "--no_encoder has none")
+        if not (0.0 <= self.scst_entropy < float("inf")):
+            ap.error("--scst_entropy must be finite and >= 0 (0 = off; got %r)" % self.scst_entropy)
+        if not self.scst and (args["scst_baseline"] is not None or args["scst_entropy"] is not None):
+            ap.error("--scst_baseline / --scst_entropy belong to --scst")
+        if self.scst:
+            if self.fine_tune:
+                ap.error("--scst does not go with --fine_tune: there is no VGG16 backward from the policy loss")
+            if self.mode != "training":
+                ap.error("--scst is a way of training: not with --mode %s" % self.mode)
+            if self.temperature != 1.0:
+                ap.error("--temperature must be 1 with --scst: the policy gradient needs the captions' probabilities under the "
+                         "distribution that was sampled (got %r)" % self.temperature)
+            if self.top_k != 0 or self.top_p != 1.0:
+                ap.error("--top_k / --top_p do not go with --scst: its samples come from the untruncated distribution")
+            shaped = [k for k in _KL_FLAGS + ("label_smoothing", "word_drop") if args[k] is not None]
+            if shaped:
+                ap.error("--%s shape(s) the cross-entropy / KL objective, which --scst does not optimise" % " / --".join(shaped))
+            if self.scst_baseline == "average" and self.num_captions < 2:
+                ap.error("--scst_baseline average compares an image's samples with each other: it needs num_captions >= 2 (got %d); "
+                         "give --scst_baseline greedy" % self.num_captions)
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.synthetic:
