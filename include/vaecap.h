@@ -46,6 +46,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the constrained beam search entry vc_beam_update_constrained.
  *      Added within 4 (additive, no layout change): the decoding-controls entry vc_decode_controls_f32.
  *      Added within 4 (additive, no layout change): the stochastic beam search entries vc_sbs_init / vc_sbs_expand_f32 / vc_sbs_update.
+ *      Added within 4 (additive, no layout change): the scheduled-sampling entry vc_sched_mix_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -272,6 +273,31 @@ int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const float* ce_d
 int vc_softmax_xent_policy_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
                                const float* adv, int N, float scale, float beta,
                                float* row_lp, float* row_ent, int write_grad);
+
+/* ------------------------------------------------------------------------------------
+ * Scheduled sampling, parallel form (additive in ABI 4; csrc/sched.hip; DESIGN.md "Scheduled sampling"): the mix between the two
+ * decoder passes of a training step.  logits [T*N, V] (row pitch ld) are the teacher-forced pass's, time-major, so the model's
+ * prediction for decoder input position (t, n) is row (t-1)*N + n.  cap_dec_t [T, N]: the gold decoder inputs; lens [N]: the caption
+ * lengths as the batch carries them (labels per row -- not the LSTM lengths with the init steps).
+ *   eligible  position (t, n) iff 1 <= t < lens[n]: <BOS>, PAD positions and rows of length 0 never are.
+ *   selected  an eligible position iff coin[t, n] < rate (strict).  Every other position: dec_mix_t = cap_dec_t.
+ *   the word  of a selected position: with u, the inverse-CDF draw of softmax(x / temperature) over the columns [0, V) with u[t, n]
+ *             -- the token vc_multinomial_rows_f32 returns for that row and that uniform, bit for bit; with u == NULL the first
+ *             maximum, as vc_argmax_rows_f32 returns it.  The eligibility and coin tests come before any read of the row: an
+ *             unselected position touches no logits memory, a selected row is read from memory once (V <= 36864; wider rows are
+ *             read in place).
+ *   the rate  from the DEVICE step counter, s = max(step[0] - 1, 0) (the counter vc_step_update has already incremented: the
+ *             first step of a run has s = 0).  schedule 0: rate_max.  1 (linear): rate_max * min(1, s / ramp_steps).
+ *             2 (inverse sigmoid, Bengio et al. 2015 eq. 3 as a sampling rate): rate_max * (1 - k / (k + exp(s / k))), k = ramp_steps,
+ *             evaluated as rate_max / (1 + k * exp(-s / k)).
+ *   outputs   dec_mix_t [T, N]: EVERY element is written.  stats (may be NULL): stats[0] += eligible, stats[1] += selected
+ *             positions (one thread's plain adds, in stream order).  rate_out (may be NULL): the rate of this call.
+ * VC_EINVAL, nothing written: V < 1, ld < V, T < 1, N < 1; temperature <= 0 with u; rate_max outside [0, 1]; an unknown schedule;
+ * ramp_steps <= 0 with schedule 1 or 2; a NULL logits / cap_dec_t / lens / coin / step / dec_mix_t.  T == 1 is valid (a copy).
+ * ---------------------------------------------------------------------------------- */
+int vc_sched_mix_f32(void* stream, const float* logits, long ld, int V, int T, int N, const int32_t* cap_dec_t, const int32_t* lens,
+                     const float* coin, const float* u, float temperature, const int32_t* step, int schedule, float rate_max,
+                     int ramp_steps, int32_t* dec_mix_t, int32_t* stats, float* rate_out);
 
 /* ------------------------------------------------------------------------------------
  * Small data-movement ops.

@@ -231,6 +231,11 @@ def main(params):
             if cap.free_bits > 0:
                 o = tr.objective_stats()
                 say("Free bits: kl_raw: {} floored_share: {}".format(o["kl_raw"], o["floored_share"]))
+
+        def say_sched():   # --sched_sampling: the rate of the last step and the share of its eligible words that were replaced (this rank's rows)
+            o = tr.sched_stats()
+            if o is not None:
+                say("Sched sampling: rate: {} replaced_share: {}".format(o["rate"], o["replaced"] / max(o["eligible"], 1)))
         for e in range(params.num_epochs):
             if real is not None:
                 it = real.next_batch(use_obj_vectors=spec.uses_ci(params), num_captions=params.num_captions)
@@ -271,6 +276,7 @@ def main(params):
                     if not params.no_encoder:
                         say("Annealing coefficient:{} KLD: {}".format(ann, kl))
                         say_objective()
+                    say_sched()
             if params.scst:
                 if tr.scst_stats is not None:
                     say_scst(e, int(global_step.item()))
@@ -279,6 +285,7 @@ def main(params):
                 say("Epoch: {} Iteration: {} VLB: {} Rec Loss: {}".format(e, int(global_step.item()), lb, rl))
                 if not params.no_encoder:
                     say_objective()
+                say_sched()
             # validate(): rec_loss of the training graph on held-out batches (main.py:262-284)
             val = []
             held_out = coco_batches(coco_val, params) if coco_val is not None else SyntheticBatches(params, 4, params.seed + 99991 + rank).next_batch()

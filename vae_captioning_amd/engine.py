@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import abi, dp, spec
+from . import abi, dp, objective, spec
 from .abi import ptr as P
 
 K_CL = spec.NUM_CLUSTERS
@@ -240,6 +240,41 @@ class CaptionEngine(object):
         self.policy = False
         self.policy_beta = 0.0
         self.pstat = torch.zeros(4, **f32)    # policy step: [0] sum row_lp, [1] live rows, [2] sum row_ent
+        # Scheduled sampling (DESIGN.md "Scheduled sampling"): sched_rate > 0 = a training forward runs the decoder twice -- on the gold
+        # inputs, then on dec_mix_t, the gold inputs with a share `rate` of the words behind <BOS> replaced by draws from the first pass's
+        # own predictions (vc_sched_mix_f32).  0 = off: every code path launches exactly what it launched before.
+        self.sched_rate = 0.0
+        self.sched_schedule, self.sched_ramp, self.sched_pick, self.sched_temperature = "linear", 10000, "sample", 1.0
+        self.sstat = self.srate = None        # [eligible, replaced] positions and the rate of the last mix
+        self._dec_ids, self._dec_key = "cap_dec_t", "dec"   # what the last fw_decode gathered: the token buffer and its gradient index
+        self._train = False                   # the current forward is a training one (fw_prepare)
+        self.configure_sched(float(getattr(p, "sched_sampling", 0.0)), getattr(p, "sched_schedule", "linear"), int(getattr(p, "sched_ramp_steps", 10000)),
+                             getattr(p, "sched_pick", "sample"), float(getattr(p, "sched_temperature", 1.0)))
+
+    SCHEDULES = objective.SCHED_SCHEDULES   # the index is vc_sched_mix_f32's `schedule`
+
+    def configure_sched(self, rate, schedule="linear", ramp=10000, pick="sample", temperature=1.0):
+        """Set the scheduled-sampling state (the Trainer's parameters arrive here: --sched_sampling, --sched_schedule, --sched_ramp_steps,
+        --sched_pick, --sched_temperature).  rate: the schedule's maximum in [0, 1], 0 = off."""
+        if not (0.0 <= rate <= 1.0):
+            raise ValueError("scheduled-sampling rate must be in [0, 1] (0 = off; got %r)" % (rate,))
+        if schedule not in self.SCHEDULES:
+            raise ValueError("scheduled-sampling schedule must be one of %s (got %r)" % (", ".join(self.SCHEDULES), schedule))
+        if pick not in ("sample", "argmax"):
+            raise ValueError("scheduled-sampling pick must be 'sample' or 'argmax' (got %r)" % (pick,))
+        if rate > 0 and schedule != "constant" and int(ramp) < 1:
+            raise ValueError("scheduled-sampling ramp must be >= 1 step (got %r)" % (ramp,))
+        if rate > 0 and pick == "sample" and not (0.0 < temperature < float("inf")):
+            raise ValueError("scheduled-sampling temperature must be finite and > 0 (got %r)" % (temperature,))
+        if rate > 0 and self.V > int(self.lib.vc_embedding_index_max_vocab()):
+            # the gradient index of the mixed inputs is rebuilt on the device inside the step; such a vocabulary has its index built on the host
+            raise ValueError("scheduled sampling needs the on-device embedding-gradient index: vocabulary %d > %d"
+                             % (self.V, int(self.lib.vc_embedding_index_max_vocab())))
+        self.sched_rate, self.sched_schedule, self.sched_ramp = float(rate), schedule, int(ramp)
+        self.sched_pick, self.sched_temperature = pick, float(temperature)
+        if rate > 0 and self.sstat is None:
+            self.sstat = torch.zeros(2, dtype=torch.int32, device=self.dev)
+            self.srate = torch.zeros(1, dtype=torch.float32, device=self.dev)
 
     def _reduce_scatter(self, out, inp):
         """sum-reduce-scatter of inp [world*n, L] into out [n, L] (RCCL; backends without the primitive,
@@ -418,13 +453,15 @@ class CaptionEngine(object):
         items += [("cap_dec_t", cap_dec.T, torch.int32), ("cap_enc_t", cap_enc.T, torch.int32)]
         lens = np.asarray(batch["lengths"], np.int32)
         items += [("lens_e", lens + self.n_init_e, torch.int32), ("lens_d", lens + self.n_init_d, torch.int32)]
+        if self.sched_rate > 0:  # scheduled sampling: the caption lengths themselves (vc_sched_mix_f32's eligibility rule)
+            items.append(("lens", lens, torch.int32))
         if self.use_ci:
             items.append(("c_v", np.asarray(batch["c_v"], np.float32), torch.float32))
         was_injected = self.inject
         self.inject = noise is not None
         self.gmm_draw = False
         if noise is not None:
-            for k in ("eps", "drop_in", "drop_out"):
+            for k in ("eps", "drop_in", "drop_out") + (("ss_coin", "ss_u") if self.sched_rate > 0 else ()):
                 if k in noise:
                     items.append((k, np.asarray(noise[k], np.float32), torch.float32))
             if "gmm_idx" in noise:
@@ -432,7 +469,7 @@ class CaptionEngine(object):
         elif was_injected and not self.fixed_inputs:
             # views of an earlier injected batch: device-generated noise gets its own buffers (only then -- the device-noise
             # buffers otherwise persist from step to step: no re-allocation, no zero-fill, addresses stable under a hipGraph)
-            for k in ("eps", "drop_in", "drop_out", "gmm_idx"):
+            for k in ("eps", "drop_in", "drop_out", "gmm_idx", "ss_coin", "ss_u"):
                 self.buf.pop(k, None)
         if noise is None and self.enc and p.prior == "GMM":
             # encoder.py:72: tf.multinomial(c_i_ph, 1) -- the cluster vector used as LOGITS (Q15): drawn on device in _noise()
@@ -606,16 +643,25 @@ class CaptionEngine(object):
             u = self._b("gmm_u", (N,))
             lib.vc_philox_uniform_f32(st, P(u), N, self.seed * 1000003 + self.rank, 4 << 32, P(self.step))
             lib.vc_multinomial_rows_f32(st, P(self.buf["c_v"]), N, K_CL, K_CL, 1.0, P(u), P(self._b("gmm_idx", (N,), torch.int32)))
+        if self.sched_rate > 0 and self._train and not self.policy:   # scheduled sampling: the coins and the inverse-CDF uniforms
+            c = self._b("ss_coin", (T, N))
+            lib.vc_philox_uniform_f32(st, P(c), c.numel(), self.seed * 1000003 + self.rank, 10 << 32, P(self.step))
+            if self.sched_pick == "sample":
+                u = self._b("ss_u", (T, N))
+                lib.vc_philox_uniform_f32(st, P(u), u.numel(), self.seed * 1000003 + self.rank, 11 << 32, P(self.step))
 
     # ---------------------------------------------------------------- forward
     def forward(self, features=None, train=True):
         """Forward pass + (train) in-place d(loss)/d(logits).  `features` [B, F] device tensor
         (defaults to the uploaded precomputed features).  Stages (also callable one by one through
-        the Encoder / Decoder facades): fw_prepare -> fw_encode -> fw_decode -> fw_loss."""
+        the Encoder / Decoder facades): fw_prepare -> fw_encode -> fw_decode_train (training; fw_decode otherwise) -> fw_loss."""
         self.fw_prepare(features, train)
         if self.enc:
             self.fw_encode()
-        self.fw_decode()
+        if train:
+            self.fw_decode_train()
+        else:
+            self.fw_decode()
         return self.fw_loss(train)
 
     def _dims(self):
@@ -629,6 +675,7 @@ class CaptionEngine(object):
         N, T, B, nc, E, He, Hd, L, Sm, V, F = self._dims()
         feats = features if features is not None else self.buf["features"]
         self.feats = feats
+        self._train = bool(train)
         if not self.inject:
             self._noise()
         if train and self.kl_cycle[0] > 0:  # cyclical KL annealing: the coefficient from the device step counter, like the tanh one
@@ -739,20 +786,61 @@ class CaptionEngine(object):
         self.kl_sum = self.red.data_ptr() + 8
         return z
 
-    def fw_decode(self):
-        """vae_model/decoder.py:34-129 (training mode): returns the logits buffer [T*N, V]."""
+    def fw_decode_train(self):
+        """The decoder of a training forward: fw_decode on the gold inputs and, with scheduled sampling on, the mix and a second
+        fw_decode on the mixed inputs (same z, same dropout masks, same image states; the encoder, the KL term, the step counter and
+        the data-parallel all-gather belong to the stages before and run once)."""
+        logits = self.fw_decode()
+        if self.sched_rate > 0 and self._train and not self.policy:
+            self.fw_sched_mix()
+            logits = self.fw_decode("dec_mix_t", "mix", init_done=True)
+        return logits
+
+    def fw_sched_mix(self):
+        """vc_sched_mix_f32 on the logits of the pass just run -> the persistent dec_mix_t [T, N], then the embedding-gradient index of
+        the mixed ids on the COMPUTE stream into buffers of its own (order_mix / seg1_mix / seg2_mix and their workspace: the copy
+        stream is building the next batch's order_dec_<slot> under this step)."""
+        lib, st = self.lib, _stream()
+        N, T, V = self.N, self.T, self.V
+        R = T * N
+        if "lens" not in self.buf:
+            raise RuntimeError("scheduled sampling was switched on after set_batch: upload the batch again (the mix needs its caption lengths)")
+        sample = self.sched_pick == "sample"
+        missing = [k for k in (("ss_coin", "ss_u") if sample else ("ss_coin",)) if k not in self.buf]
+        if missing:
+            raise ValueError("scheduled sampling with injected noise needs %s ([T, N] float32 uniforms in [0, 1))" % " and ".join(missing))
+        mix = self._b("dec_mix_t", (T, N), torch.int32)
+        self.sstat.zero_()
+        lib.vc_sched_mix_f32(st, P(self.buf["logits"]), _round(V, 4), V, T, N, P(self.buf["cap_dec_t"]), P(self.buf["lens"]), P(self.buf["ss_coin"]),
+                             P(self.buf["ss_u"]) if sample else None, self.sched_temperature, P(self.step), self.SCHEDULES.index(self.sched_schedule),
+                             self.sched_rate, self.sched_ramp, P(mix), P(self.sstat), P(self.srate))
+        nsub = int(lib.vc_embedding_index_max_subsegments(R, V, 32))
+        iws = self._cap_buf("idx_ws_mix", lib.vc_embedding_index_workspace_bytes(R, V) // 4 + 16, torch.int32)
+        o = self._cap_buf("order_mix", R, torch.int32)[:R]
+        s1 = self._cap_buf("seg1_mix", nsub + 1, torch.int32)[:nsub + 1]
+        s2 = self._cap_buf("seg2_mix", V + 1, torch.int32)
+        lib.vc_embedding_grad_index(st, P(mix), R, V, 32, P(o), P(s1), P(s2), P(iws), iws.numel() * 4)
+        self.buf["order_mix"], self.buf["seg1_mix"], self.buf["seg2_mix"] = o, s1, s2
+        return mix
+
+    def fw_decode(self, ids="cap_dec_t", index="dec", init_done=False):
+        """vae_model/decoder.py:34-129 (training mode): returns the logits buffer [T*N, V].  ids / index: the [T, N] token buffer the
+        decoder reads and the key of its embedding-gradient index (backward takes the decoder table's gradient through it).
+        init_done: the init-chain rows of Xd (image, c_v, z step) stand from an earlier pass over the same z -- the z_rnn product is
+        not repeated (the word rows behind them are rewritten by every pass)."""
         p, lib, st, S = self.p, self.lib, _stream(), self.store
         N, T, B, nc, E, He, Hd, L, Sm, V, F = self._dims()
         Td = T + self.n_init_d
         Xd = self.buf["Xd"]
-        if self.enc:
+        self._dec_ids, self._dec_key = ids, index
+        if self.enc and not init_done:
             # decoder.py:109-111: z viewed as [N, S*L] (Q1) -> z_rnn -> the z step of the init chain
             z = self.buf["z"]
             zi = self.n_init_d - 1
             self.gemm(0, 0, N, E, Sm * L, z, Sm * L, S.param("decoder/net/z_rnn/kernel"), E, Xd[zi], E, S.param("decoder/net/z_rnn/bias"))
         xw = Xd[self.n_init_d]
         self._timed("hbm_embedding_gather", T * N * (4.0 + 8.0 * E),
-                    lambda: lib.vc_embedding_gather_f32(st, P(S.param("decoder/net/dec_embeddings")), P(self.buf["cap_dec_t"]), T * N, E, V, P(xw)))
+                    lambda: lib.vc_embedding_gather_f32(st, P(S.param("decoder/net/dec_embeddings")), P(self.buf[ids]), T * N, E, V, P(xw)))
         if p.dec_keep_rate < 1:  # no train/eval switch in the reference (Q21)
             lib.vc_dropout_f32(st, P(xw), P(self.buf["drop_in"]), p.dec_keep_rate, T * N * E, P(xw))
         act_d, cs_d, hs_d = self._b("act_d", (Td, N, 4 * Hd)), self._b("cs_d", (Td + 1, N, Hd)), self._b("hs_d", (Td + 1, N, Hd))
@@ -874,7 +962,7 @@ class CaptionEngine(object):
             ws, wsb = self._need_ws(lib.vc_lstm_seq_workspace_bytes(Td, N, E, Hd))
             lib.vc_lstm_seq_bwd_weights_f32(_stream(), Td, N, E, Hd, P(self.buf["Xd"]), P(self.buf["hs_d"]), P(dG),
                                             P(S.grad(spec.DEC_CELL + "kernel")), P(S.grad(spec.DEC_CELL + "bias")), ws, wsb, self.lstm_flags)
-            self._embedding_grad("decoder/net/dec_embeddings", "dec", dxw)
+            self._embedding_grad("decoder/net/dec_embeddings", self._dec_key, dxw)   # (the index of the ids the last fw_decode gathered)
             lib.vc_sumsq_partial_f32(_stream(), P(dxw), T * N * E, self.part.data_ptr() + nb * 4)  # IndexedSlices.values (Q5)
         side(dec_w)
         d_imfv = dXd[0]       # [N, E] gradient w.r.t. images_fv (decoder part)
@@ -1135,7 +1223,7 @@ class CaptionEngine(object):
             a = S.slot("a")
             lr = self.scal.data_ptr() + 8
             lib.vc_momentum_f32(st, P(S.p), P(S.g), P(a), self.n_dense, lr, scale, 0.9, 0.0, None, 0)
-            for name, ids in (("decoder/net/dec_embeddings", "cap_dec_t"), ("encoder/enc_embeddings", "cap_enc_t")):
+            for name, ids in (("decoder/net/dec_embeddings", self._dec_ids), ("encoder/enc_embeddings", "cap_enc_t")):
                 if name not in S.offsets:
                     continue
                 off, shape = S.offsets[name]
@@ -1163,6 +1251,15 @@ class CaptionEngine(object):
             return None
         o = self.ostat.detach().cpu().numpy()
         return {"kl_raw": float(o[0]), "floored_share": float(o[1])}
+
+    def sched_stats(self):
+        """Scheduled sampling (--sched_sampling > 0): {"rate": the sampling rate the last training forward used, "eligible": this rank's
+        decoder input positions behind <BOS> and inside the captions, "replaced": how many of them took the model's own word}; None
+        when the mode is off."""
+        if self.sched_rate <= 0 or self.sstat is None:
+            return None
+        s = self.sstat.detach().cpu().numpy()
+        return {"rate": float(self.srate.item()), "eligible": int(s[0]), "replaced": int(s[1])}
 
 
 def embedding_grad_index(ids, vocab, chunk=32):

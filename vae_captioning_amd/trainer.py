@@ -981,6 +981,9 @@ class Trainer(object):
     def objective_stats(self):
         return self.cap.objective_stats()
 
+    def sched_stats(self):
+        return self.cap.sched_stats()
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self):
         """Every trainable variable of the reference graph (main.py:186-191).  The reference builds the VGG16 variables

@@ -33,6 +33,8 @@ _DEFAULTS = dict(
     kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
     # self-critical training (off by default)
     scst=False, scst_baseline="average", scst_entropy=0.0,
+    # scheduled sampling in the cross-entropy phase (off by default)
+    sched_sampling=0.0, sched_schedule="linear", sched_ramp_steps=10000, sched_pick="sample", sched_temperature=1.0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -67,8 +69,12 @@ _FLAGS = [
     ("--word_drop", "word_drop", float, None),
     ("--scst", "scst", "flag", None), ("--scst_baseline", "scst_baseline", str, ["average", "greedy"]),
     ("--scst_entropy", "scst_entropy", float, None),
+    ("--sched_sampling", "sched_sampling", float, None), ("--sched_schedule", "sched_schedule", str, ["constant", "linear", "sigmoid"]),
+    ("--sched_ramp_steps", "sched_ramp_steps", int, None), ("--sched_pick", "sched_pick", str, ["sample", "argmax"]),
+    ("--sched_temperature", "sched_temperature", float, None),
 ]
 _KL_FLAGS = ("kl_free_bits", "kl_weight", "kl_cycle_steps", "kl_cycle_ramp", "kl_cycles")
+_SCHED_FLAGS = ("sched_schedule", "sched_ramp_steps", "sched_pick", "sched_temperature")
 _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", "--vocab": "vocabulary size for --synthetic (default 10000)",
          "--max_steps": "steps per epoch (0 = the reference's num_ex_per_epoch rule, main.py:217-221)",
          "--captions_json": "COCO captions json (with --features_pickle: in-memory real-data path)",
@@ -126,6 +132,16 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--scst_baseline": "--scst: what a sample's reward is compared with -- average: the mean reward of the image's other samples "
                             "(needs num_captions >= 2); greedy: the reward of the greedy caption under the same latent draw (default average)",
          "--scst_entropy": "--scst: weight of the token-entropy bonus in the policy loss (finite, >= 0; default 0 = off)",
+         "--sched_sampling": "scheduled sampling, two-pass form: each decoder input word behind <BOS> is replaced with (at most) this "
+                             "probability by a word the model itself predicts for that position in a first, teacher-forced pass; the "
+                             "decoder is then re-run on the mixed inputs and trained against the unchanged labels (in [0, 1]; default "
+                             "0 = off; never in validation or inference; not with --scst)",
+         "--sched_schedule": "--sched_sampling: how the probability moves with the global step s -- constant: R; linear: R * min(1, s / K); "
+                             "sigmoid: R * (1 - K / (K + exp(s / K))), K = --sched_ramp_steps (default linear)",
+         "--sched_ramp_steps": "--sched_sampling: K of the linear and the sigmoid schedule (>= 1; default 10000; constant ignores it)",
+         "--sched_pick": "--sched_sampling: the model's word is a draw from its prediction (sample) or its most likely word (argmax; "
+                         "default sample)",
+         "--sched_temperature": "--sched_sampling --sched_pick sample: temperature of the draw (> 0; default 1.0)",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
@@ -251,6 +267,19 @@ class Parameters(object):
             if self.scst_baseline == "average" and self.num_captions < 2:
                 ap.error("--scst_baseline average compares an image's samples with each other: it needs num_captions >= 2 (got %d); "
                          "give --scst_baseline greedy" % self.num_captions)
+        if not (0.0 <= self.sched_sampling <= 1.0):
+            ap.error("--sched_sampling must be in [0, 1] (0 = off; got %r)" % self.sched_sampling)
+        if self.sched_ramp_steps < 1:
+            ap.error("--sched_ramp_steps must be >= 1 (got %d)" % self.sched_ramp_steps)
+        if not (0.0 < self.sched_temperature < float("inf")):
+            ap.error("--sched_temperature must be finite and > 0 (got %r)" % self.sched_temperature)
+        if not self.sched_sampling > 0 and any(args[k] is not None for k in _SCHED_FLAGS):
+            ap.error("--sched_schedule / --sched_ramp_steps / --sched_pick / --sched_temperature belong to --sched_sampling > 0")
+        if self.sched_sampling > 0:
+            if self.scst:
+                ap.error("--sched_sampling mixes the inputs of the cross-entropy step, which --scst does not take")
+            if self.mode != "training":
+                ap.error("--sched_sampling is a way of training: not with --mode %s" % self.mode)
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.synthetic:

@@ -53,7 +53,7 @@ class Decoder(object):
             if tr.vgg is not None and tr.vgg.wd:
                 tr.vgg.reg_sumsq(eng.red.data_ptr() + 12)
             eng.fw_prepare(feats)
-        logits = eng.fw_decode()
+        logits = eng.fw_decode_train()   # (with --sched_sampling: both decoder passes; the logits are those of the mixed inputs)
         nid = eng.n_init_d
         hs, cs = eng.buf["hs_d"], eng.buf["cs_d"]
         shpe = (tuple(eng.buf["z"].shape) if eng.enc else (), (eng.T * eng.N, self.params.decoder_hidden),
