@@ -47,6 +47,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the decoding-controls entry vc_decode_controls_f32.
  *      Added within 4 (additive, no layout change): the stochastic beam search entries vc_sbs_init / vc_sbs_expand_f32 / vc_sbs_update.
  *      Added within 4 (additive, no layout change): the scheduled-sampling entry vc_sched_mix_f32.
+ *      Added within 4 (additive, no layout change): the ROUGE-L entry vc_lcs_overlap.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -750,6 +751,28 @@ int vc_ngram_overlap(void* stream, long C, const int32_t* c_off, const int32_t* 
                      const int32_t* c_len, long n_ref, const int32_t* r_off, const int32_t* r_nnz, const uint64_t* r_keys, const float* r_w,
                      const int32_t* r_len, const int32_t* lo, const int32_t* hi, const int32_t* skip, int32_t* total, int32_t* match,
                      int32_t* distinct, int32_t* unseen, int32_t* ref_len);
+
+/* ------------------------------------------------------------------------------------
+ * ROUGE-L counts (evaluate.py: lcs_overlap, CaptionEvaluator; scst.py: RougeReward; csrc/lcs.hip): longest common subsequences.
+ *   lcs_overlap     c_tok [C, c_ld] and r_tok [n_ref, r_ld] are word rows (consensus.word_rows): left-aligned, len[r] valid words per row
+ *                   (clamped to 0 .. min(64, ld)); entries at and past len are never read.  The two tables may be the same one.
+ *                   Hypothesis c is compared with the reference rows [lo[c], hi[c]) except row skip[c] (-1: none); the range is clamped
+ *                   on the device exactly as ngram_overlap's: lo' = min(max(lo, 0), n_ref), hi' = min(max(hi, lo'), n_ref), so lo > hi
+ *                   and ranges outside the table give the results of an empty range; a skip outside the range drops nothing.
+ *                   Only rows of the range with at least one word take part.  With LCS(c, r) the length of the longest common
+ *                   subsequence of the two word sequences:
+ *                     lcs_max[c]              = the largest LCS(c, r) over the range            (ROUGE-L precision = lcs_max / L_c)
+ *                     rec_lcs[c], rec_len[c]  = (LCS(c, r), L_r) of the row that maximises LCS(c, r) / L_r, ratios compared by integer
+ *                                               cross-multiplication; a tie in the ratio goes to the smaller L_r   (recall = rec_lcs / rec_len)
+ *                   No row taking part (empty range, also after the skip, or zero-word rows only): all three are 0.  All outputs are
+ *                   exact int32 values: a row's results depend on the row and its range only.  One wave per hypothesis, four per
+ *                   workgroup: lane i holds hypothesis word i, the match mask of a reference word is one 64-bit ballot, the LCS row state
+ *                   one 64-bit integer (bit-parallel recurrence V' = (V + (V & M)) | (V - (V & M)) modulo 2^64).  No LDS, no atomics.
+ *                   C == 0 is a successful no-op (no pointer is looked at); C < 0, n_ref < 0 or >= 2^31, a pitch < 1, or a null pointer
+ *                   with C > 0 are VC_EINVAL. */
+int vc_lcs_overlap(void* stream, long C, const int32_t* c_tok, long c_ld, const int32_t* c_len, long n_ref, const int32_t* r_tok, long r_ld,
+                   const int32_t* r_len, const int32_t* lo, const int32_t* hi, const int32_t* skip, int32_t* lcs_max, int32_t* rec_lcs,
+                   int32_t* rec_len);
 
 /* ------------------------------------------------------------------------------------
  * Scoring given captions (generate.py: CaptionGenerator.score; csrc/score.hip).  Forward only.

@@ -220,8 +220,14 @@ def main(params):
             else:
                 corpus = training_index_data(params, None)[1]
             bos, eos = cap_dict.word2idx["<BOS>"], cap_dict.word2idx["<EOS>"]
-            say("SCST: document frequencies from %d training images, baseline %s, entropy weight %g" % (len(corpus), params.scst_baseline, params.scst_entropy))
-            tr.enable_scst(CiderReward(cap, corpus, bos, eos, cap_dict.vocab_size), bos, eos, baseline=params.scst_baseline, beta=params.scst_entropy)
+            rouge_w = float(getattr(params, "scst_rouge", 0.0))
+            say("SCST: document frequencies from %d training images, baseline %s, entropy weight %g" % (len(corpus), params.scst_baseline, params.scst_entropy)
+                + (", ROUGE-L weight %g" % rouge_w if rouge_w > 0 else ""))
+            reward = CiderReward(cap, corpus, bos, eos, cap_dict.vocab_size)
+            if rouge_w > 0:   # the reward is CIDEr-D + W * ROUGE-L; with 0 it is the CiderReward alone and vc_lcs_overlap is never launched
+                from vae_captioning_amd.scst import RougeReward, SumReward
+                reward = SumReward([(reward, 1.0), (RougeReward(cap, bos, eos), rouge_w)])
+            tr.enable_scst(reward, bos, eos, baseline=params.scst_baseline, beta=params.scst_entropy)
 
         def say_scst(e, it):
             s = tr.scst_stats

@@ -8,11 +8,13 @@ tokens), eager launches, device noise.
   scst  Trainer.scst_step with baseline "average" and "greedy" (entropy weight 0.01), split into its phases on the HOST clock, each
         phase closed by a device synchronise (Trainer.scst_times): sample / greedy pass / reward (its host share -- token lists ->
         word rows -- beside it) / upload of the policy batch / policy forward + backward / optimiser; median over --reps steps of the
-        per-step sums.  The phases are serial in a step (each needs the one before it), so their sum is the step.
+        per-step sums.  The phases are serial in a step (each needs the one before it), so their sum is the step.  --scst_rouge W..:
+        one run per weight of the ROUGE-L term of the reward (0: CIDEr-D alone, the default; W > 0: scst.SumReward, CIDEr-D + W *
+        ROUGE-L, one more launch and one more copy-back in the reward phase).
 
 The weights are random, so samples rarely end before gen_max_len: the policy batch has T = 30 -- the most a step can cost at these
 shapes.  One JSON line per part.  There is no target: the numbers are what was measured.
-    python tools/scst_time.py [--reps 15] [--warmup 3]"""
+    python tools/scst_time.py [--reps 15] [--warmup 3] [--scst_rouge 0 0.5]"""
 import argparse
 import json
 import os
@@ -27,6 +29,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--scst_rouge", type=float, nargs="+", default=[0.0])
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -64,13 +67,15 @@ def main():
     print(json.dumps(dict({"part": "kernel", "rows": rows, "V": V, "reps": 2 * a.reps}, **{k + "_ms": round(float(np.median(v)), 4) for k, v in ts.items()},
                           **{k + "_GBps": round(8.0 * rows * V / (float(np.median(v)) * 1e-3) / 1e9, 1) for k, v in ts.items()})), flush=True)
     del logits
-    for baseline in ("average", "greedy"):
+    xe_done = False
+    for baseline, rouge_w in [(b, w) for b in ("average", "greedy") for w in a.scst_rouge]:
         p = Parameters()
         p.batch_size, p.vocab_size = B, V
         tr = Trainer(p, V, lib=lib, seed=3)
         tr.load_state_dict(spec.init_caption_params(p, V, seed=1))
         batch = synth.make_batch(rng, B, p.num_captions, T, V, variable_len=True)
-        if baseline == "average":   # the XE step beside it, once
+        if not xe_done:   # the XE step beside it, once
+            xe_done = True
             tr.set_batch(batch)
             ts = []
             for i in range(a.warmup + a.reps):
@@ -84,6 +89,8 @@ def main():
             print(json.dumps({"part": "xe", "workload": "cfg2 shape: 256 images (1280 rows), T 20, V 10000, eager launches", "step_ms": round(float(np.median(ts)), 3),
                               "min_max_ms": [round(min(ts), 3), round(max(ts), 3)], "reps": a.reps}), flush=True)
         reward = scst.CiderReward(tr.cap, corpus, synth.BOS, synth.EOS, V)
+        if rouge_w > 0:
+            reward = scst.SumReward([(reward, 1.0), (scst.RougeReward(tr.cap, synth.BOS, synth.EOS), rouge_w)])
         tr.enable_scst(reward, synth.BOS, synth.EOS, baseline=baseline, beta=0.01)
         for _ in range(a.warmup):
             tr.scst_step(batch)
@@ -99,7 +106,7 @@ def main():
             host.append(reward.host_seconds)
         tr.scst_times = None
         med = lambda k: round(1e3 * float(np.median([r.get(k, 0.0) for r in rows])), 3)
-        print(json.dumps({"part": "scst", "baseline": baseline, "workload": "cfg2 shape: 256 images x 5 samples, max_len 30, V 10000, entropy weight 0.01",
+        print(json.dumps({"part": "scst", "baseline": baseline, "scst_rouge": rouge_w, "workload": "cfg2 shape: 256 images x 5 samples, max_len 30, V 10000, entropy weight 0.01",
                           "step_ms": round(1e3 * float(np.median(wall)), 3), "min_max_ms": [round(1e3 * min(wall), 3), round(1e3 * max(wall), 3)],
                           "sample_ms": med("sample"), "greedy_ms": med("greedy"), "reward_ms": med("reward"),
                           "reward_host_ms": round(1e3 * float(np.median(host)), 3), "upload_ms": med("upload"),

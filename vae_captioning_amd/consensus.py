@@ -155,7 +155,8 @@ def upload(dev, a):
 
 def ngram_vectors(lib, dev, W, L, bos, eos, df_keys, idf, n_df, idf_unseen, head=None):
     """n-gram vectors of word rows (vc_ngram_vectors), CSR by capacity(L), weighted by the device df / idf table given (n_df = 0: every
-    n-gram gets idf_unseen).  The host inputs go up in one copy; head: an int32 array sent along (v.head is its device copy)."""
+    n-gram gets idf_unseen).  The host inputs go up in one copy; head: an int32 array sent along (v.head is its device copy).  The
+    uploaded word rows stay reachable: v.tok [n, v.ld] int32 and v.len [n] (what vc_lcs_overlap reads)."""
     n = int(W.shape[0])
     cap = capacity(L)
     off = np.zeros(n + 1, np.int64)
@@ -170,7 +171,8 @@ def ngram_vectors(lib, dev, W, L, bos, eos, df_keys, idf, n_df, idf_unseen, head
                               w=torch.empty(total, dtype=torch.float32, device=dev),
                               nnz=torch.empty(max(1, n), dtype=torch.int32, device=dev),
                               norm=torch.empty((max(1, n), 4), dtype=torch.float32, device=dev),
-                              words=torch.empty(max(1, n), dtype=torch.int32, device=dev))
+                              words=torch.empty(max(1, n), dtype=torch.int32, device=dev),
+                              tok=up[o2:], ld=int(W.shape[1]), len=up[o1:o2])
     if n:
         lib.vc_ngram_vectors(_stream(), P(up[o2:]), n, int(W.shape[1]), P(up[o1:o2]), int(bos), int(eos), P(df_keys), P(idf), int(n_df),
                              float(idf_unseen), P(v.off), P(v.keys), P(v.w), P(v.nnz), P(v.norm), P(v.words))

@@ -1,5 +1,5 @@
 """Evaluation of caption sets on the GPU: the numbers the AG-CVAE paper reports for a set of captions per image -- accuracy of the top
-caption (BLEU-1..4, CIDEr-D), "oracle" accuracy of the best caption of the set, and the diversity of the set (share of distinct
+caption (BLEU-1..4, CIDEr-D, ROUGE-L), "oracle" accuracy of the best caption of the set, and the diversity of the set (share of distinct
 captions, share of novel sentences, Div-1, Div-2, mBLEU-4).
 
 `CaptionEvaluator(lib_or_engine, references, bos, eos)` holds the n-gram vectors of every image's human captions on the device;
@@ -17,14 +17,19 @@ Every integer comes from the device, every float from float64 arithmetic on thos
 * CIDEr-D: vc_consensus_score on idf-weighted vectors with k = 1, nbr[b] = b, the references' offsets as img_cap and m = 2048, i.e.
   the mean over ALL references of the image of the one-reference CIDEr-D.  The idf is coco-caption's convention: document frequencies
   over the evaluated images' references (consensus.host_index), unseen n-grams log D.
+* ROUGE-L: csrc/lcs.hip's vc_lcs_overlap on the word rows the hypothesis and reference count tables already hold on the device, against
+  the image's references (the range array of the BLEU call): per caption the largest LCS and the (LCS, words) pair of the reference
+  with the largest LCS / words, three integers that ride in the one copy-back.  `rouge_l` turns them into coco-caption's score
+  (precision and recall take their maxima over the references separately, beta = 1.2).
 
 BLEU here is the plain corpus-level definition (corpus_bleu): it does NOT imitate coco-caption's smoothing constants (its 1e-9 "tiny" /
 1e-15 "small" terms), and the tokens are vocabulary ids after the vocabulary cut, not PTB tokens -- the numbers compare runs of this
 project with each other, not with a leaderboard ("Evaluation").
 
 Single-caption modes (greedy, sample, beam_search) hand in lists of one: the set metrics are then those of lists of one -- `distinct`
-1.0, `mbleu_4` 0.0 (no hypotheses), `oracle_cider_d` = `mean_cider_d` = `cider_d`."""
+1.0, `mbleu_4` 0.0 (no hypotheses), `oracle_cider_d` = `mean_cider_d` = `cider_d`, `oracle_rouge_l` = `mean_rouge_l` = `rouge_l`."""
 import math
+import types
 
 import numpy as np
 import torch
@@ -35,9 +40,10 @@ from .engine import _stream
 from .generate import DIVERSE_MAX_DRAWS
 
 METRICS = ("bleu_1", "bleu_2", "bleu_3", "bleu_4", "cider_d", "oracle_cider_d", "mean_cider_d", "distinct", "div_1", "div_2", "mbleu_4",
-           "novel")
+           "novel", "rouge_l", "oracle_rouge_l", "mean_rouge_l")
 MAX_REFS = MAX_POOL       # references per image (vc_consensus_score stages an image's pool in LDS)
 OUT_COLS = 17             # total, match, distinct, unseen [., 4] + ref_len per hypothesis
+LCS_COLS = 3              # lcs_max, rec_lcs, rec_len per hypothesis (vc_lcs_overlap)
 
 
 def corpus_bleu(match, total, hyp_len, ref_len):
@@ -101,6 +107,57 @@ def ngram_overlap(lib_or_engine, hyp, ref, lo, hi, skip=None):
     out = torch.empty(OUT_COLS * C, dtype=torch.int32, device=dev)
     _launch(lib, hyp, ref, rng, out)
     return _split(out.cpu().numpy(), C)
+
+
+def _launch_lcs(lib, hyp, ref, rng, out):
+    """hyp / ref: tables that hold their word rows on the device (tok [n, ld], len [n]: ngram_vectors outputs or word_table);
+    rng: int32 device [3, C] (lo, hi, skip); out: int32 device [LCS_COLS * C]"""
+    C = hyp.n
+    lib.vc_lcs_overlap(_stream(), C, P(hyp.tok), hyp.ld, P(hyp.len), ref.n, P(ref.tok), ref.ld, P(ref.len), P(rng), P(rng) + 4 * C,
+                       P(rng) + 8 * C, P(out), P(out) + 4 * C, P(out) + 8 * C)
+
+
+def _split_lcs(a, C):
+    """host int32 [LCS_COLS * C] -> dict of the three outputs"""
+    return dict(lcs_max=a[:C], rec_lcs=a[C:2 * C], rec_len=a[2 * C:3 * C])
+
+
+def word_table(dev, W, L, head=None):
+    """Word rows (consensus.word_rows) on the device, in one copy: what vc_lcs_overlap needs of a table (n, tok [n, ld], len [n]) without
+    the n-gram vectors.  head: an int32 array sent along (t.head is its device copy)."""
+    n = int(W.shape[0])
+    head = np.zeros(0, np.int32) if head is None else np.asarray(head, np.int32).reshape(-1)
+    h = head.size
+    up = upload(dev, np.concatenate([head, np.asarray(L, np.int32), np.asarray(W, np.int32).reshape(-1)]))
+    return types.SimpleNamespace(n=n, head=up[:h], len=up[h:h + n], tok=up[h + n:], ld=int(W.shape[1]))
+
+
+def lcs_overlap(lib_or_engine, hyp, ref, lo, hi, skip=None):
+    """One vc_lcs_overlap call on two tables that hold their word rows on the device (count_vectors / ngram_vectors outputs or
+    word_table; they may be the same one): hypothesis row c against reference rows [lo[c], hi[c]) without row skip[c] (-1 / None:
+    none).  -> dict of int32 arrays [C]: lcs_max (the largest LCS over the range), rec_lcs and rec_len (LCS and words of the row with the
+    largest LCS / words; a tie goes to the shorter row); all 0 when no row of the range has a word."""
+    lib, dev = library_and_device(lib_or_engine)
+    C = hyp.n
+    lo, hi, skip = check_ranges(lo, hi, np.full(C, -1) if skip is None else skip, C, ref.n)
+    if C == 0:
+        return _split_lcs(np.zeros(0, np.int32), 0)
+    rng = upload(dev, np.stack([lo, hi, skip]))
+    out = torch.empty(LCS_COLS * C, dtype=torch.int32, device=dev)
+    _launch_lcs(lib, hyp, ref, rng, out)
+    return _split_lcs(out.cpu().numpy(), C)
+
+
+def rouge_l(lcs_max, rec_lcs, rec_len, hyp_len, beta=1.2):
+    """coco-caption's ROUGE-L per caption from vc_lcs_overlap's integers and the captions' word counts: P = lcs_max / hyp_len,
+    R = rec_lcs / rec_len (each its maximum over the references), score = (1 + beta^2) P R / (R + beta^2 P) in float64, evaluated in
+    this order; 0.0 where hyp_len, rec_len or either LCS is 0.  -> float64 array"""
+    m, l, n, h = (np.asarray(a, np.float64).reshape(-1) for a in (lcs_max, rec_lcs, rec_len, hyp_len))
+    live = (m > 0) & (l > 0) & (n > 0) & (h > 0)
+    p = m / np.where(live, h, 1.0)
+    r = l / np.where(live, n, 1.0)
+    score = (1 + beta ** 2) * p * r / np.where(live, r + beta ** 2 * p, 1.0)
+    return np.where(live, score, 0.0)
 
 
 def _mean(x):
@@ -167,22 +224,26 @@ class CaptionEvaluator(object):
         rows = np.arange(C)
         start, end = cand_img[image_of], cand_img[image_of + 1]
         if C:
-            # ---- device: one hypothesis table, three overlap calls, the CIDEr-D path; one copy-back of the integers
+            # ---- device: one hypothesis table, three overlap calls, the LCS call, the CIDEr-D path; one copy-back of the integers
             hyp = count_vectors(self.lib, self.dev, W, L, self.bos, self.eos)
             none = np.full(C, -1)
             rng = upload(self.dev, np.stack([self.ref_off[image_of], self.ref_off[image_of + 1], none,      # the image's references
                                              start, rows, none,                                             # its earlier captions
                                              start, end, rows]).astype(np.int32).reshape(3, 3 * C))         # its other captions
-            out = torch.empty((3, OUT_COLS * C), dtype=torch.int32, device=self.dev)
+            flat_out = torch.empty((3 * OUT_COLS + LCS_COLS) * C, dtype=torch.int32, device=self.dev)
+            out = flat_out[:3 * OUT_COLS * C].view(3, OUT_COLS * C)
             for i, ref in enumerate((self.ref_counts, hyp, hyp)):
                 _launch(self.lib, hyp, ref, rng[i], out[i])
+            _launch_lcs(self.lib, hyp, self.ref_counts, rng[0], flat_out[3 * OUT_COLS * C:])   # the word rows of the two count tables
             cider_dev = self._cider(W, L, cand_img, int(per.max()))
-            ints = out.cpu().numpy()
+            ints = flat_out.cpu().numpy()
             cider = cider_dev.cpu().numpy()[:C]
-            to_ref, to_prev, to_rest = (_split(ints[i], C) for i in range(3))
+            to_ref, to_prev, to_rest = (_split(ints[OUT_COLS * C * i:OUT_COLS * C * (i + 1)], C) for i in range(3))
+            lcs = _split_lcs(ints[3 * OUT_COLS * C:], C)
         else:
             cider = np.zeros(0, np.float64)
             to_ref = to_prev = to_rest = _split(np.zeros(0, np.int32), 0)
+            lcs = _split_lcs(np.zeros(0, np.int32), 0)
         # ---- host: float64 from exact integers
         have = per > 0
         top = cand_img[:-1][have]
@@ -191,6 +252,11 @@ class CaptionEvaluator(object):
         best = np.array([cider[cand_img[b]:cand_img[b + 1]].max() if per[b] else np.nan for b in range(B)], np.float64)
         top_cider = np.full(B, np.nan)
         top_cider[have] = cider[top]
+        rouge = rouge_l(lcs["lcs_max"], lcs["rec_lcs"], lcs["rec_len"], L)
+        top_rouge, best_rouge = np.full(B, np.nan), np.full(B, np.nan)
+        top_rouge[have] = rouge[top]
+        if C:
+            best_rouge[have] = np.maximum.reduceat(rouge, top)   # (`top`: the first row of every image that lists a caption)
         # distinct word sequences per image: rows are 0-padded, so equal rows are equal captions
         uniq = np.unique(np.column_stack([image_of, W]), axis=0)[:, 0] if C else np.zeros(0, np.int64)
         n_distinct = np.bincount(uniq, minlength=B)
@@ -209,7 +275,10 @@ class CaptionEvaluator(object):
             novel = (sum(W[i, :L[i]].tobytes() not in self.train for i in range(C)) / C) if C else 0.0
         res = dict(bleu_1=bleu[0], bleu_2=bleu[1], bleu_3=bleu[2], bleu_4=bleu[3], cider_d=_mean(top_cider[have]),
                    oracle_cider_d=_mean(best[have]), mean_cider_d=_mean(cider), distinct=_mean(share[have]), div_1=_mean(div[0][words > 0]),
-                   div_2=_mean(div[1][words > 0]), mbleu_4=mbleu[3], novel=novel)
+                   div_2=_mean(div[1][words > 0]), mbleu_4=mbleu[3], novel=novel, rouge_l=_mean(top_rouge[have]),
+                   oracle_rouge_l=_mean(best_rouge[have]), mean_rouge_l=_mean(rouge))
         res["per_image"] = dict(captions=per, cider_d=top_cider, oracle_cider_d=best, distinct=share, div_1=div[0], div_2=div[1],
-                                caption_cider_d=[cider[cand_img[b]:cand_img[b + 1]].copy() for b in range(B)])
+                                caption_cider_d=[cider[cand_img[b]:cand_img[b + 1]].copy() for b in range(B)],
+                                rouge_l=top_rouge, oracle_rouge_l=best_rouge,
+                                caption_rouge_l=[rouge[cand_img[b]:cand_img[b + 1]].copy() for b in range(B)])
         return res

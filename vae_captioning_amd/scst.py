@@ -10,8 +10,13 @@ One `Trainer.scst_step(batch)`:
 4. one policy-gradient step of the decoder on the sampled captions under the given z (`CaptionEngine.policy_forward`, csrc/loss.hip's
    vc_softmax_xent_policy_f32): the gradient of 1/N sum_n -A[n] log p(caption n | z_n, image) (- beta * token entropies).
 
+The reward is any object with `rewards(candidates_per_image, references_per_image)`: `CiderReward` alone by default; with
+--scst_rouge W > 0 the `SumReward` CIDEr-D + W * ROUGE-L (`RougeReward`: csrc/lcs.hip's vc_lcs_overlap, evaluate.rouge_l).
+
 DESIGN.md, "Self-critical training", has the estimator, the trained variables and how z travels from the sampler to the step.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -112,28 +117,120 @@ class CiderReward(object):
         the references as the pool, as CaptionEvaluator._cider).  A candidate without words has reward 0."""
         import time
         t0 = time.perf_counter()
-        B = len(candidates_per_image)
-        if len(references_per_image) != B:
-            raise ValueError("%d images of candidates for %d images of references" % (B, len(references_per_image)))
-        per_c = np.fromiter((len(c) for c in candidates_per_image), np.int64, B)
-        per_r = np.fromiter((len(r) for r in references_per_image), np.int64, B)
-        if B == 0 or per_c.sum() == 0:
+        rows = reward_rows(candidates_per_image, references_per_image, self.bos, self.eos)
+        if rows is None:
             return np.zeros(0, np.float64)
-        if per_r.min() < 1:
-            raise ValueError("image %d has no reference caption" % int(np.argmin(per_r)))
-        if per_r.max() > MAX_POOL or per_c.max() > DIVERSE_MAX_DRAWS:
-            raise ValueError("at most %d references and %d candidates per image" % (MAX_POOL, DIVERSE_MAX_DRAWS))
-        ref_off, cand_off = np.zeros(B + 1, np.int64), np.zeros(B + 1, np.int64)
-        ref_off[1:], cand_off[1:] = np.cumsum(per_r), np.cumsum(per_c)
-        Wr, Lr = word_rows([r for rs in references_per_image for r in rs], self.bos, self.eos, owner=lambda i: "reference row %d" % i)
-        Wc, Lc = word_rows([c for cs in candidates_per_image for c in cs], self.bos, self.eos, owner=lambda i: "candidate row %d" % i)
         self.host_seconds += time.perf_counter() - t0
-        rv = self._vectors(Wr, Lr, np.concatenate([ref_off, np.arange(B)]))   # head: img_cap [B + 1], nbr [B, 1]
-        cv = self._vectors(Wc, Lc, cand_off)
+        return self.rewards_rows(rows)
+
+    def rewards_rows(self, rows):
+        """the device half of rewards() on the word rows reward_rows made (with this reward's bos / eos)"""
+        B, Lc = rows.B, rows.Lc
+        rv = self._vectors(rows.Wr, rows.Lr, np.concatenate([rows.ref_off, np.arange(B)]))   # head: img_cap [B + 1], nbr [B, 1]
+        cv = self._vectors(rows.Wc, Lc, rows.cand_off)
         out = torch.empty(max(1, cv.n), dtype=torch.float64, device=self.dev)
         self.lib.vc_consensus_score(_stream(), B, 1, P(rv.head[B + 1:]), P(rv.head[:B + 1]), P(rv.off), P(rv.nnz), P(rv.keys), P(rv.w),
-                                    P(rv.norm), P(rv.words), P(cv.head), int(per_c.max()), P(cv.off), P(cv.nnz), P(cv.keys), P(cv.w),
+                                    P(rv.norm), P(rv.words), P(cv.head), rows.max_cands, P(cv.off), P(cv.nnz), P(cv.keys), P(cv.w),
                                     P(cv.norm), P(cv.words), MAX_POOL, P(out))
         r = out.cpu().numpy()[:cv.n].copy()
         r[Lc == 0] = 0.0
         return r
+
+
+def reward_rows(candidates_per_image, references_per_image, bos, eos):
+    """Host half of a reward: the checks and limits every reward shares, and the token lists as word rows (consensus.word_rows).
+    -> a namespace (B, ref_off / cand_off [B + 1], Wr, Lr, Wc, Lc, max_cands), or None when there is no candidate at all."""
+    B = len(candidates_per_image)
+    if len(references_per_image) != B:
+        raise ValueError("%d images of candidates for %d images of references" % (B, len(references_per_image)))
+    per_c = np.fromiter((len(c) for c in candidates_per_image), np.int64, B)
+    per_r = np.fromiter((len(r) for r in references_per_image), np.int64, B)
+    if B == 0 or per_c.sum() == 0:
+        return None
+    if per_r.min() < 1:
+        raise ValueError("image %d has no reference caption" % int(np.argmin(per_r)))
+    if per_r.max() > MAX_POOL or per_c.max() > DIVERSE_MAX_DRAWS:
+        raise ValueError("at most %d references and %d candidates per image" % (MAX_POOL, DIVERSE_MAX_DRAWS))
+    ref_off, cand_off = np.zeros(B + 1, np.int64), np.zeros(B + 1, np.int64)
+    ref_off[1:], cand_off[1:] = np.cumsum(per_r), np.cumsum(per_c)
+    Wr, Lr = word_rows([r for rs in references_per_image for r in rs], bos, eos, owner=lambda i: "reference row %d" % i)
+    Wc, Lc = word_rows([c for cs in candidates_per_image for c in cs], bos, eos, owner=lambda i: "candidate row %d" % i)
+    return types.SimpleNamespace(B=B, ref_off=ref_off, cand_off=cand_off, Wr=Wr, Lr=Lr, Wc=Wc, Lc=Lc, max_cands=int(per_c.max()),
+                                 image_of=np.repeat(np.arange(B), per_c))
+
+
+class RougeReward(object):
+    """Per-caption ROUGE-L (coco-caption's definition, beta = 1.2: evaluate.rouge_l) against given references -- the duck type of
+    CiderReward, with its limits and its error messages for bad input.  It needs no corpus: the LCS counts come from vc_lcs_overlap on
+    the word rows of the step's candidates and references, the score from float64 arithmetic on those integers on the host.
+    lib_or_engine: the C-ABI library (abi.load()) or a CaptionEngine (its library and device)."""
+
+    def __init__(self, lib_or_engine, bos, eos, beta=1.2):
+        self.lib, self.dev = library_and_device(lib_or_engine)
+        self.bos, self.eos, self.beta = int(bos), int(eos), float(beta)
+        self.host_seconds = 0.0   # as CiderReward: the host half of rewards() (token lists -> word rows), accumulated
+
+    def rewards(self, candidates_per_image, references_per_image):
+        """As CiderReward.rewards: float64 [sum of candidates], each candidate's ROUGE-L against its image's references (precision and
+        recall take their maxima over the references separately).  A candidate without words has reward 0."""
+        import time
+        t0 = time.perf_counter()
+        rows = reward_rows(candidates_per_image, references_per_image, self.bos, self.eos)
+        if rows is None:
+            return np.zeros(0, np.float64)
+        self.host_seconds += time.perf_counter() - t0
+        return self.rewards_rows(rows)
+
+    def rewards_rows(self, rows):
+        """the device half of rewards() on the word rows reward_rows made (with this reward's bos / eos)"""
+        from . import evaluate as ev
+        C, img = int(rows.Lc.size), rows.image_of
+        rng = np.stack([rows.ref_off[img], rows.ref_off[img + 1], np.full(C, -1)]).astype(np.int32)
+        hyp = ev.word_table(self.dev, rows.Wc, rows.Lc, head=rng)     # one upload per table; the ranges ride with the candidates
+        ref = ev.word_table(self.dev, rows.Wr, rows.Lr)
+        out = torch.empty(ev.LCS_COLS * C, dtype=torch.int32, device=self.dev)
+        ev._launch_lcs(self.lib, hyp, ref, hyp.head, out)
+        o = ev._split_lcs(out.cpu().numpy(), C)
+        return ev.rouge_l(o["lcs_max"], o["rec_lcs"], o["rec_len"], rows.Lc, self.beta)
+
+
+class SumReward(object):
+    """The weighted sum of rewards: parts = [(reward, weight), ...], each reward an object with rewards(candidates_per_image,
+    references_per_image) and host_seconds (CiderReward, RougeReward).  When every part can work on prepared word rows (it has
+    rewards_rows) and the parts agree on <BOS> / <EOS>, the token lists are turned into word rows ONCE per call and shared; otherwise
+    each part does its own conversion.  host_seconds: the sum over the parts, plus the shared conversion's own time."""
+
+    def __init__(self, parts):
+        self.parts = [(r, float(w)) for r, w in parts]
+        if not self.parts:
+            raise ValueError("a sum of rewards needs at least one part")
+        marks = set((getattr(r, "bos", None), getattr(r, "eos", None)) for r, _ in self.parts)
+        self.shared = all(hasattr(r, "rewards_rows") for r, _ in self.parts) and len(marks) == 1 and None not in next(iter(marks))
+        self._own_seconds = 0.0
+
+    @property
+    def host_seconds(self):
+        return self._own_seconds + sum(r.host_seconds for r, _ in self.parts)
+
+    @host_seconds.setter
+    def host_seconds(self, value):
+        self._own_seconds = float(value)
+        for r, _ in self.parts:
+            r.host_seconds = 0.0
+
+    def rewards(self, candidates_per_image, references_per_image):
+        if self.shared:
+            import time
+            t0 = time.perf_counter()
+            first = self.parts[0][0]
+            rows = reward_rows(candidates_per_image, references_per_image, first.bos, first.eos)
+            if rows is None:
+                return np.zeros(0, np.float64)
+            self._own_seconds += time.perf_counter() - t0
+            each = [r.rewards_rows(rows) for r, _ in self.parts]
+        else:
+            each = [r.rewards(candidates_per_image, references_per_image) for r, _ in self.parts]
+        total = np.zeros(np.asarray(each[0]).shape, np.float64)
+        for (_, w), x in zip(self.parts, each):
+            total = total + w * np.asarray(x, np.float64)
+        return total

@@ -832,7 +832,8 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ self-critical training (scst.py; DESIGN.md "Self-critical training")
     def enable_scst(self, reward, bos, eos, baseline="average", beta=0.0, max_len=None):
-        """Make scst_step available.  reward: a scst.CiderReward; baseline: "average" (the image's other samples) or "greedy" (the
+        """Make scst_step available.  reward: any object with rewards(candidates_per_image, references_per_image) -> float64 per
+        candidate (scst.CiderReward, scst.RougeReward, a scst.SumReward of them); baseline: "average" (the image's other samples) or "greedy" (the
         greedy decode under the same z); beta: weight of the token-entropy bonus (>= 0); max_len: longest sample (default gen_max_len)."""
         from . import scst
         from .generate import CaptionGenerator

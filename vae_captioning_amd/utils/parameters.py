@@ -32,7 +32,7 @@ _DEFAULTS = dict(
     # training objective options (every one off by default: the reference's objective)
     kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
     # self-critical training (off by default)
-    scst=False, scst_baseline="average", scst_entropy=0.0,
+    scst=False, scst_baseline="average", scst_entropy=0.0, scst_rouge=0.0,
     # scheduled sampling in the cross-entropy phase (off by default)
     sched_sampling=0.0, sched_schedule="linear", sched_ramp_steps=10000, sched_pick="sample", sched_temperature=1.0,
 )
@@ -68,7 +68,7 @@ _FLAGS = [
     ("--kl_cycles", "kl_cycles", int, None), ("--label_smoothing", "label_smoothing", float, None),
     ("--word_drop", "word_drop", float, None),
     ("--scst", "scst", "flag", None), ("--scst_baseline", "scst_baseline", str, ["average", "greedy"]),
-    ("--scst_entropy", "scst_entropy", float, None),
+    ("--scst_entropy", "scst_entropy", float, None), ("--scst_rouge", "scst_rouge", float, None),
     ("--sched_sampling", "sched_sampling", float, None), ("--sched_schedule", "sched_schedule", str, ["constant", "linear", "sigmoid"]),
     ("--sched_ramp_steps", "sched_ramp_steps", int, None), ("--sched_pick", "sched_pick", str, ["sample", "argmax"]),
     ("--sched_temperature", "sched_temperature", float, None),
@@ -98,7 +98,7 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--top_p": "--sample_gen sample / --diverse_method sample: draw each word from the smallest set of most likely words that holds "
                     "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)",
          "--eval_captions": "--mode inference: also evaluate the validation captions against the images' human captions on the GPU (BLEU, "
-                            "CIDEr-D, oracle CIDEr-D, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json",
+                            "CIDEr-D, oracle CIDEr-D, ROUGE-L, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json",
          "--bound_draws": "--mode inference: also bound the likelihood of the validation images' human captions with this many posterior "
                           "draws per caption (ELBO, importance-weighted bound, KL, effective sample size, active latent units) and "
                           "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)",
@@ -132,6 +132,8 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--scst_baseline": "--scst: what a sample's reward is compared with -- average: the mean reward of the image's other samples "
                             "(needs num_captions >= 2); greedy: the reward of the greedy caption under the same latent draw (default average)",
          "--scst_entropy": "--scst: weight of the token-entropy bonus in the policy loss (finite, >= 0; default 0 = off)",
+         "--scst_rouge": "--scst: weight W of a ROUGE-L term in the reward, which is then CIDEr-D + W * ROUGE-L (finite, >= 0; "
+                         "default 0 = off: CIDEr-D alone)",
          "--sched_sampling": "scheduled sampling, two-pass form: each decoder input word behind <BOS> is replaced with (at most) this "
                              "probability by a word the model itself predicts for that position in a first, teacher-forced pass; the "
                              "decoder is then re-run on the mixed inputs and trained against the unchanged labels (in [0, 1]; default "
@@ -249,8 +251,12 @@ class Parameters(object):
                      "--no_encoder has none")
         if not (0.0 <= self.scst_entropy < float("inf")):
             ap.error("--scst_entropy must be finite and >= 0 (0 = off; got %r)" % self.scst_entropy)
+        if not (0.0 <= self.scst_rouge < float("inf")):
+            ap.error("--scst_rouge must be finite and >= 0 (0 = off; got %r)" % self.scst_rouge)
         if not self.scst and (args["scst_baseline"] is not None or args["scst_entropy"] is not None):
             ap.error("--scst_baseline / --scst_entropy belong to --scst")
+        if not self.scst and args["scst_rouge"] is not None:
+            ap.error("--scst_rouge belongs to --scst")
         if self.scst:
             if self.fine_tune:
                 ap.error("--scst does not go with --fine_tune: there is no VGG16 backward from the policy loss")
