@@ -18,17 +18,6 @@ namespace vc {
 
 constexpr int BOUND_MAX_K = 256;
 
-__device__ __forceinline__ double bound_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double bound_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // One workgroup per row; thread t owns the in-row element quads t, t + 256, ... (a partition by the position INSIDE the row: the same
 // whatever the row's index is).  Philox numbers are keyed by the flat element index row*SL + j, so a row whose first element is not a
 // multiple of 4 starts inside a Philox quad: an in-row quad then takes its four numbers from two neighbouring Philox quads.
@@ -85,7 +74,7 @@ __global__ __launch_bounds__(256) void posterior_latent_kernel(long SL, int L, i
             }
         }
     }
-    acc = bound_wave_sum(acc);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) logw[r] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(64) void gauss_kl_rows_kernel(int S, int L, const f
         const double s = (double)std_[c * L + l], d = (double)mean[c * L + l] - (pmr ? (double)pmr[l] : 0.0);
         acc += (log_sp - log(s)) + (s * s + d * d) * inv - 0.5;
     }
-    acc = bound_wave_sum(acc);
+    acc = wave_sum(acc);
     if (threadIdx.x == 0) kl[c] = (double)S * acc;
 }
 
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(64) void bound_reduce_kernel(const float* __restric
         }
         a[j] = v;
     }
-    mx = bound_wave_max(mx);
+    mx = wave_max(mx);
     double e1 = 0.0, e2 = 0.0;
 #pragma unroll
     for (int j = 0; j < BOUND_MAX_K / 64; ++j)
@@ -143,11 +132,11 @@ __global__ __launch_bounds__(64) void bound_reduce_kernel(const float* __restric
             e1 += v;
             e2 += v * v;
         }
-    s_a = bound_wave_sum(s_a);
-    s_rec = bound_wave_sum(s_rec);
-    s_w = bound_wave_sum(s_w);
-    e1 = bound_wave_sum(e1);
-    e2 = bound_wave_sum(e2);
+    s_a = wave_sum(s_a);
+    s_rec = wave_sum(s_rec);
+    s_w = wave_sum(s_w);
+    e1 = wave_sum(e1);
+    e2 = wave_sum(e2);
     if (lane == 0) {
         double* o = out + (long)c * 5;
         o[0] = s_a / (double)K;                      // elbo

@@ -55,6 +55,16 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    return v;
+}
 
 // block-wide sum for blockDim.x == NT (multiple of 64); result valid in every thread.
 template <int NT>
@@ -113,6 +123,11 @@ __device__ __forceinline__ void box_muller4(const uint32_t (&r)[4], float (&f)[4
     f[0] = ra * c; f[1] = ra * s;
     __sincosf(6.283185307179586f * u4, &s, &c);
     f[2] = rb * c; f[3] = rb * s;
+}
+
+// n of a packed n-gram key (four 16-bit word ids, ids >= 1: the highest non-zero 16-bit group); consensus.hip and evaluate.hip
+__device__ __forceinline__ int key_order(uint64_t key) {
+    return key >= (1ull << 48) ? 4 : key >= (1ull << 32) ? 3 : key >= (1ull << 16) ? 2 : 1;
 }
 
 // gemm.hip: split-K partial products for consumers that reduce them in their own kernel (lstm.hip)

@@ -162,10 +162,6 @@ __device__ __forceinline__ uint64_t ngram_key(const int* w, int i, int n) {
     return key;
 }
 
-__device__ __forceinline__ int key_order(uint64_t key) {   // n of an n-gram key (ids >= 1: the highest non-zero 16-bit group)
-    return key >= (1ull << 48) ? 4 : key >= (1ull << 32) ? 3 : key >= (1ull << 16) ? 2 : 1;
-}
-
 // One wave (workgroup of 64) per caption.
 __global__ __launch_bounds__(64) void ngram_vectors_kernel(const int32_t* __restrict__ tok, long ld, const int32_t* __restrict__ len, int bos,
                                                            int eos, const uint64_t* __restrict__ df_keys, const float* __restrict__ idf,

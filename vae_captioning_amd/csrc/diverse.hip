@@ -3,20 +3,19 @@
 //
 //   vc_diverse_latent_f32    z[r, s, l] = pm[r / K, l] + std * eps[r, s, l]: no [rows*S, L] mean / std tensors; eps injected or drawn
 //                            here with the Philox / Box-Muller code of vc_philox_normal_f32 (same seed, offset, step: same bits)
-//   vc_decode_pick_f32       one decoder round's token per row from ONE read of the logits: argmax (first maximum, as
-//                            argmax_rows_kernel) or the inverse-CDF draw with multinomial_rows_kernel's 256-chunk partition (same
-//                            expressions, same order: same token), plus the token's log-softmax at temperature 1 accumulated into the
-//                            row's candidate (sequence, length, float64 log-likelihood, <EOS> flag)
+//   vc_decode_pick_f32       one decoder round's token per row from ONE read of the logits: argmax (first maximum) or the
+//                            inverse-CDF draw, plus the token's log-softmax at temperature 1 accumulated into the row's candidate
+//                            (sequence, length, float64 log-likelihood, <EOS> flag); the pieces and the entries they agree with bit
+//                            for bit: row_ops.h
 //   vc_decode_pick_trunc_f32 the same round with the distribution truncated before the draw: the top_k best words and / or the smallest
 //                            set of best words holding a share top_p of the probability, found by a radix select (no sort of V words)
 //   vc_decode_round_end_i32  pending = rows without <EOS>, round += 1 (the device round counter keys the next round's uniforms)
 //   vc_diverse_rank          one workgroup per image: scores, 64-bit hashes confirmed by full compares, duplicates merged, ranked
-#include "common.h"
+#include "row_ops.h"
 #include "vaecap.h"
 
 namespace vc {
 
-constexpr int PICK_LDS_MAX = 12288;   // logits rows up to this width are staged in LDS (48 KiB): the row is read from memory once
 constexpr int RANK_MAX_K = 256;
 
 __global__ __launch_bounds__(256) void diverse_latent_kernel(long n, long SL, int L, int K, const float* __restrict__ pm, float std_,
@@ -59,67 +58,23 @@ __global__ __launch_bounds__(256) void decode_pick_kernel(const float* __restric
     __shared__ int s_tok;
     const long r = blockIdx.x;
     const int t = threadIdx.x;
-    const float* p = logits + r * ld;
-    if (STAGE) {
-        for (int c = t; c < V; c += 256) srow[c] = p[c];
-        __syncthreads();
-        p = srow;
-    }
-    // contiguous chunk per thread (multinomial_rows_kernel's partition: the scan order is the index order)
-    const int per = (V + 255) / 256;
-    const int c0 = t * per, c1 = min(V, c0 + per);
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int c = c0; c < c1; ++c) {
-        const float v = p[c];
-        if (v > bv) { bv = v; bi = c; }
-    }
-    const float mx1 = block_max<256>(bv, sh);
-    float s1 = 0.f;
-    for (int c = c0; c < c1; ++c) s1 += __expf(p[c] - mx1);
-    s1 = block_sum<256>(s1, sh);
-    if (u == nullptr) {   // argmax: the first maximum (chunks are in index order, so (value, lower index) picks argmax_rows_kernel's)
-        part[t] = bv;
-        si[t] = bi;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (t < o) {
-                const float v2 = part[t + o];
-                const int i2 = si[t + o];
-                if (v2 > part[t] || (v2 == part[t] && i2 < si[t])) {
-                    part[t] = v2;
-                    si[t] = i2;
-                }
-            }
-            __syncthreads();
-        }
+    const float* p = stage_row<STAGE>(logits + r * ld, V, srow);
+    int c0, c1;
+    const int per = row_chunk(V, c0, c1);
+    float mx1, s1, bv;
+    int bi;
+    row_max_sum(p, c0, c1, sh, mx1, s1, bv, bi);
+    if (u == nullptr) {   // argmax: the first maximum (chunks are in index order)
+        block_first_max(bv, bi, part, si);
         if (t == 0) s_tok = si[0];
-    } else {              // multinomial_rows_kernel, expression for expression
+    } else {              // the inverse-CDF draw (the scaled maximum over the chunks: the row may sit in LDS)
         float mx = -INFINITY;
         for (int c = c0; c < c1; ++c) mx = fmaxf(mx, p[c] * inv_temp);
         mx = block_max<256>(mx, sh);
-        float s = 0.f;
-        for (int c = c0; c < c1; ++c) s += __expf(p[c] * inv_temp - mx);
-        part[t] = s;
-        __syncthreads();
+        row_cdf_part(p, c0, c1, inv_temp, mx, part);
         if (t == 0) {
             const int rd = round ? min(max(round[0], 0), u_rounds - 1) : 0;
-            float tot = 0.f;
-            for (int i = 0; i < 256; ++i) tot += part[i];
-            const float target = u[(long)rd * rows + r] * tot;
-            float run = 0.f;
-            int k = 0;
-            for (; k < 255; ++k) {
-                if (run + part[k] > target) break;
-                run += part[k];
-            }
-            int idx = min(V - 1, k * per);
-            for (int c = k * per; c < min(V, (k + 1) * per); ++c) {
-                run += __expf(p[c] * inv_temp - mx);
-                idx = c;
-                if (run > target) break;
-            }
-            s_tok = idx;
+            s_tok = row_cdf_pick(p, V, per, inv_temp, mx, part, u + ((long)rd * rows + r));
         }
     }
     if (t == 0) {
@@ -127,7 +82,7 @@ __global__ __launch_bounds__(256) void decode_pick_kernel(const float* __restric
         tok[r] = w;
         const int n = len[r];
         if (!done[r] && n >= 0 && n < Lmax) {
-            const float lp = (p[min(max(w, 0), V - 1)] - mx1) - logf(s1);   // log softmax at temperature 1
+            const float lp = lsm_term(p[min(max(w, 0), V - 1)], mx1, logf(s1));
             seq[r * Lmax + n] = w;
             len[r] = n + 1;
             logprob[r] += (double)lp;
@@ -243,21 +198,14 @@ __global__ __launch_bounds__(256) void decode_pick_trunc_kernel(const float* __r
     __shared__ int s_tok, s_last;
     const long r = blockIdx.x;
     const int t = threadIdx.x;
-    const float* p = logits + r * ld;
-    if (STAGE) {
-        for (int c = t; c < V; c += 256) srow[c] = p[c];
-        __syncthreads();
-        p = srow;
-    }
+    const float* p = stage_row<STAGE>(logits + r * ld, V, srow);
     if (t == 0) { s_tok = -1; s_last = 0; }
-    const int per = (V + 255) / 256;
-    const int c0 = t * per, c1 = min(V, c0 + per);   // decode_pick_kernel's partition: contiguous chunks in index order
+    int c0, c1;
+    row_chunk(V, c0, c1);
     float bv = -INFINITY;
-    for (int c = t; c < V; c += 256) bv = fmaxf(bv, p[c]);
+    for (int c = t; c < V; c += 256) bv = fmaxf(bv, p[c]);   // (strided: the same maximum as row_max_sum's)
     const float mx1 = block_max<256>(bv, sh);
-    float s1 = 0.f;
-    for (int c = c0; c < c1; ++c) s1 += __expf(p[c] - mx1);   // (decode_pick_kernel's sum: the same log-softmax bits)
-    s1 = block_sum<256>(s1, sh);
+    const float s1 = row_exp_sum(p, c0, c1, mx1, sh);
     const float my = key_value(pick_key(mx1, inv_temp));   // max y (the scaling is monotone)
 
     // ---- the cut: words with key > T are kept, and the first j (index order) of the words with key == T
@@ -341,7 +289,7 @@ __global__ __launch_bounds__(256) void decode_pick_trunc_kernel(const float* __r
         if (kept) kept[r] = (int32_t)(n_gt + j);
         const int n = len[r];
         if (!done[r] && n >= 0 && n < Lmax) {
-            const float lp = (p[w] - mx1) - logf(s1);   // log softmax at temperature 1 over the full vocabulary
+            const float lp = lsm_term(p[w], mx1, logf(s1));   // over the full vocabulary
             seq[r * Lmax + n] = w;
             len[r] = n + 1;
             logprob[r] += (double)lp;
@@ -366,8 +314,6 @@ __global__ __launch_bounds__(256) void round_end_kernel(const int32_t* __restric
         if (round) round[0] += 1;
     }
 }
-
-__device__ __forceinline__ bool rank_better(double sa, int a, double sb, int b) { return sa > sb || (sa == sb && a < b); }
 
 // One workgroup per image, thread k = draw k.  O(K^2) LDS work per image with K <= 256: each draw finds the draws with its sequence
 // (hash + length filter, full compare to confirm), is its group's representative iff no other member scores better (ties: lower draw),
@@ -410,7 +356,7 @@ __global__ __launch_bounds__(256) void diverse_rank_kernel(int K, int Lmax, cons
             }
             if (!same) continue;
             ++cnt;
-            if (j != k && rank_better(s_score[j], j, sc, k)) lead = 0;
+            if (j != k && better(s_score[j], j, sc, k)) lead = 0;
         }
     }
     s_lead[k] = lead;
@@ -419,7 +365,7 @@ __global__ __launch_bounds__(256) void diverse_rank_kernel(int K, int Lmax, cons
     if (lead) {
         int pos = 0;
         for (int j = 0; j < K; ++j)
-            if (s_lead[j] && j != k && (s_end[j] > e || (s_end[j] == e && rank_better(s_score[j], j, sc, k)))) ++pos;
+            if (s_lead[j] && j != k && (s_end[j] > e || (s_end[j] == e && better(s_score[j], j, sc, k)))) ++pos;
         rep[base + pos] = k;
         count[base + pos] = cnt;
         score[base + pos] = sc;
@@ -456,7 +402,7 @@ extern "C" int vc_decode_pick_f32(void* stream, const float* logits, long rows, 
     VC_CHECK_ARG(rows > 0 && V > 0 && ld >= V && Lmax > 0, "bad shape");
     VC_CHECK_ARG(!u || (temperature > 0.f && u_rounds > 0), "sampling needs temperature > 0 and u_rounds > 0");
     const float inv_temp = u ? 1.0f / temperature : 1.0f;
-    if (V <= PICK_LDS_MAX)
+    if (V <= ROW_LDS_MAX)
         hipLaunchKernelGGL(decode_pick_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)V * sizeof(float), (hipStream_t)stream, logits,
                            rows, V, ld, inv_temp, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob);
     else
@@ -484,7 +430,7 @@ extern "C" int vc_decode_pick_trunc_f32(void* stream, const float* logits, long 
         return 0;
     }
     const float inv_temp = 1.0f / temperature;
-    if (V <= PICK_LDS_MAX)
+    if (V <= ROW_LDS_MAX)
         hipLaunchKernelGGL(decode_pick_trunc_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)V * sizeof(float), st, logits, rows, V, ld,
                            inv_temp, top_k, top_p, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob, kept);
     else

@@ -2,7 +2,7 @@
 // gradients), dropout, ReLU backward, row tiling, reductions.  All are coalesced,
 // 16-B vectorised where the layout allows, and sized as grid-stride loops over <= 2048
 // workgroups (cdna_hip_programming.md guideline 11).
-#include "common.h"
+#include "row_ops.h"
 #include "vaecap.h"
 
 namespace vc {
@@ -344,20 +344,7 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
         const float v = p[c];
         if (v > bv) { bv = v; bi = c; }
     }
-    sv[threadIdx.x] = bv;
-    si[threadIdx.x] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            const float v2 = sv[threadIdx.x + o];
-            const int i2 = si[threadIdx.x + o];
-            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) {
-                sv[threadIdx.x] = v2;
-                si[threadIdx.x] = i2;
-            }
-        }
-        __syncthreads();
-    }
+    block_first_max(bv, bi, sv, si);
     if (threadIdx.x == 0) out[blockIdx.x] = si[0];
 }
 
@@ -379,17 +366,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
             const bool eligible = (v < lv) || (v == lv && c > li);
             if (eligible && (v > bv || (v == bv && c < bi))) { bv = v; bi = c; }
         }
-        sv[threadIdx.x] = bv;
-        si[threadIdx.x] = bi;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) {
-                const float v2 = sv[threadIdx.x + o];
-                const int i2 = si[threadIdx.x + o];
-                if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v2; si[threadIdx.x] = i2; }
-            }
-            __syncthreads();
-        }
+        block_first_max(bv, bi, sv, si);
         lv = sv[0];
         li = si[0];
         if (threadIdx.x == 0) {
@@ -448,14 +425,14 @@ __global__ __launch_bounds__(256) void topk_rows_small_kernel(const float* __res
         for (int o = 32; o > 0; o >>= 1) {
             const float v2 = __shfl_xor(bv, o, 64);
             const int i2 = __shfl_xor(bi, o, 64), t2 = __shfl_xor(bt, o, 64);
-            if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; bt = t2; }
+            if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; bt = t2; }
         }
         if (lane == 0) { wv[wave] = bv; wi[wave] = bi; wt[wave] = bt; }
         __syncthreads();
         bv = wv[0]; bi = wi[0]; bt = wt[0];
 #pragma unroll
         for (int w = 1; w < 4; ++w)
-            if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; bt = wt[w]; }
+            if (better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; bt = wt[w]; }
         if (tid == bt) ++head;
         if (tid == 0) {
             out_val[(long)blockIdx.x * k + j] = bv;
@@ -600,13 +577,8 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float* __r
                     int bi = ci[0];
 #pragma unroll
                     for (int q = 1; q < TOPK_CAND / 64; ++q)
-                        if (cv[q] > bv || (cv[q] == bv && ci[q] < bi)) { bv = cv[q]; bi = ci[q]; }
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) {
-                        const float v2 = __shfl_xor(bv, o, 64);
-                        const int i2 = __shfl_xor(bi, o, 64);
-                        if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; }
-                    }
+                        if (better(cv[q], ci[q], bv, bi)) { bv = cv[q]; bi = ci[q]; }
+                    wave_best(bv, bi);
 #pragma unroll
                     for (int q = 0; q < TOPK_CAND / 64; ++q)
                         if (ci[q] == bi) { cv[q] = -INFINITY; ci[q] = 0x7fffffff; }   // (indices are unique: exactly one lane holds the winner)
@@ -646,14 +618,14 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float* __r
         for (int o = 32; o > 0; o >>= 1) {
             const float v2 = __shfl_xor(bv, o, 64);
             const int i2 = __shfl_xor(bi, o, 64), t2 = __shfl_xor(bt, o, 64);
-            if (v2 > bv || (v2 == bv && i2 < bi)) { bv = v2; bi = i2; bt = t2; }
+            if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; bt = t2; }
         }
         if (lane == 0) { wv[wave] = bv; wi[wave] = bi; wt[wave] = bt; }
         __syncthreads();
         bv = wv[0]; bi = wi[0]; bt = wt[0];
 #pragma unroll
         for (int w = 1; w < 4; ++w)
-            if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; bt = wt[w]; }
+            if (better(wv[w], wi[w], bv, bi)) { bv = wv[w]; bi = wi[w]; bt = wt[w]; }
         if (tid == bt) ++head;
         if (tid == 0) {
             out_val[(long)blockIdx.x * k + j] = bv;

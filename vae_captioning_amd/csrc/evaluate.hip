@@ -15,10 +15,6 @@ namespace vc {
 constexpr int OV_SLOTS = 256;   // key slots of a caption (consensus.hip: NG_SLOTS; 64 + 63 + 62 + 61 used at most)
 constexpr int OV_WAVES = 4;     // hypotheses per workgroup, one wave each
 
-__device__ __forceinline__ int ov_key_order(uint64_t key) {   // n of an n-gram key (ids >= 1: the highest non-zero 16-bit group)
-    return key >= (1ull << 48) ? 4 : key >= (1ull << 32) ? 3 : key >= (1ull << 16) ? 2 : 1;
-}
-
 // Wave w of workgroup g owns hypothesis row g * OV_WAVES + w.  The waves share nothing but the two barriers (which stand outside every
 // loop whose trip count differs between waves).  LDS: 4 * 256 * (8 + 4 + 4) = 16 KiB.
 __global__ __launch_bounds__(64 * OV_WAVES) void ngram_overlap_kernel(long C, const int32_t* __restrict__ c_off, const int32_t* __restrict__ c_nnz,
@@ -90,7 +86,7 @@ __global__ __launch_bounds__(64 * OV_WAVES) void ngram_overlap_kernel(long C, co
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0;
     for (int i = lane; i < cn; i += 64) {
-        const int n = ov_key_order(s_key[wv][i]) - 1;
+        const int n = key_order(s_key[wv][i]) - 1;
         const int cg = s_cnt[wv][i], mg = s_max[wv][i];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {

@@ -5,7 +5,7 @@
 // Reference: main.py:118-177 (KL, masked CE, lower bound), vae_model/encoder.py:59-109
 // (heads, zs.Normal sample), vae_model/decoder.py:109-110 (the z buffer is consumed as a
 // raw [N, S*L] reshape of [S, N, L] -- quirk Q1 -- i.e. the SAME memory, no kernel).
-#include "common.h"
+#include "row_ops.h"
 #include "vaecap.h"
 
 namespace vc {
@@ -177,7 +177,8 @@ __global__ __launch_bounds__(256) void softmax_rows_reg_kernel(const float* __re
 
 // Categorical sample per row from logits / temperature (tf.multinomial, vae_model/decoder.py:137-138) by
 // inverse CDF with an INJECTED uniform u[row] in [0,1): index = first i with cumsum(softmax)[i] > u.
-// (TF draws with its own Gumbel/Philox stream, which cannot be matched; the distribution is the same.)
+// (TF draws with its own Gumbel/Philox stream, which cannot be matched; the distribution is the same.)  The draw is row_ops.h's; the
+// scaled maximum in front of it is taken with strided (coalesced) loads, the row being read in place.
 __global__ __launch_bounds__(256) void multinomial_rows_kernel(const float* __restrict__ logits, int V, long ld, float inv_temp,
                                                                const float* __restrict__ u, int32_t* __restrict__ out) {
     __shared__ float sh[4];
@@ -186,31 +187,10 @@ __global__ __launch_bounds__(256) void multinomial_rows_kernel(const float* __re
     float mx = -INFINITY;
     for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, p[c] * inv_temp);
     mx = block_max<256>(mx, sh);
-    // contiguous chunk per thread so that the scan order is the index order
-    const int per = (V + 255) / 256;
-    const int c0 = threadIdx.x * per, c1 = min(V, c0 + per);
-    float s = 0.f;
-    for (int c = c0; c < c1; ++c) s += __expf(p[c] * inv_temp - mx);
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tot = 0.f;
-        for (int i = 0; i < 256; ++i) tot += part[i];
-        const float target = u[blockIdx.x] * tot;
-        float run = 0.f;
-        int t = 0;
-        for (; t < 255; ++t) {
-            if (run + part[t] > target) break;
-            run += part[t];
-        }
-        int idx = min(V - 1, t * per);
-        for (int c = t * per; c < min(V, (t + 1) * per); ++c) {
-            run += __expf(p[c] * inv_temp - mx);
-            idx = c;
-            if (run > target) break;
-        }
-        out[blockIdx.x] = idx;
-    }
+    int c0, c1;
+    const int per = row_chunk(V, c0, c1);
+    row_cdf_part(p, c0, c1, inv_temp, mx, part);
+    if (threadIdx.x == 0) out[blockIdx.x] = row_cdf_pick(p, V, per, inv_temp, mx, part, u + blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 //
 //   vc_mixture_topk_f32     q_g(v) = sum_k w_r exp(x_rv - M_r) / S_r with w = softmax_k(logw): the kc best words of every group.
 //                           Three launches, the vocabulary split across workgroups:
-//                             1. mixture_stat_kernel     one workgroup per row: (M_r, log S_r), decode_pick_kernel's expressions
+//                             1. mixture_stat_kernel     one workgroup per row: (M_r, log S_r) by row_ops.h's row_max_sum
 //                             2. mixture_partial_kernel  one workgroup per (group, 1024-column chunk): the group's weights (K <= 256
 //                                                        float64 terms, tree sums in LDS), the chunk's q in registers (four columns
 //                                                        per thread, k ascending), the best kc of each wave by shuffles, the four
@@ -17,55 +17,28 @@
 //                           sum), the rows' parents and tokens for the next round, and greedy decoding's per-group bookkeeping.
 #include <limits.h>
 
-#include "common.h"
+#include "row_ops.h"
 #include "vaecap.h"
 
 namespace vc {
 
-constexpr int MIX_LDS_MAX = 12288;   // (diverse.hip's PICK_LDS_MAX) logits rows up to this width are staged in LDS: read from memory once
 constexpr int MIX_CHUNK = 1024;      // columns per workgroup of the partial top-kc: four per thread
 constexpr int MIX_MAX_K = 256;       // draws per group: one thread per draw
 constexpr int MIX_MAX_KC = 16;       // words per group (vc_beam_update's BEAM_MAX)
 constexpr int MIX_MERGE_LDS = 1024;  // chunk lists of up to this many entries are merged from LDS
 
-// (value descending, column ascending): a strict total order over pairs with distinct columns
-__device__ __forceinline__ bool mix_better(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
-
-// the best pair of the wave, in every lane
-__device__ __forceinline__ void mix_wave_best(float& bv, int& bi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (mix_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-}
-
-// One workgroup per row: stat[r] = (M_r, log S_r) with decode_pick_kernel's partition, expressions and reduction order (the same bits
-// as the terms of its log-softmax).
+// One workgroup per row: stat[r] = (M_r, log S_r), the terms of the temperature-1 log-softmax (row_ops.h).
 template <bool STAGE>
 __global__ __launch_bounds__(256) void mixture_stat_kernel(const float* __restrict__ logits, int V, long ld, float* __restrict__ stat) {
     extern __shared__ float srow[];
     __shared__ float sh[4];
     const long r = blockIdx.x;
     const int t = threadIdx.x;
-    const float* p = logits + r * ld;
-    if (STAGE) {
-        for (int c = t; c < V; c += 256) srow[c] = p[c];
-        __syncthreads();
-        p = srow;
-    }
-    const int per = (V + 255) / 256;
-    const int c0 = min(V, t * per), c1 = min(V, c0 + per);
-    float bv = -INFINITY;
-    for (int c = c0; c < c1; ++c) {
-        const float v = p[c];
-        if (v > bv) bv = v;
-    }
-    const float mx1 = block_max<256>(bv, sh);
-    float s1 = 0.f;
-    for (int c = c0; c < c1; ++c) s1 += __expf(p[c] - mx1);
-    s1 = block_sum<256>(s1, sh);
+    const float* p = stage_row<STAGE>(logits + r * ld, V, srow);
+    int c0, c1;
+    row_chunk(V, c0, c1);
+    float mx1, s1;
+    row_max_sum(p, c0, c1, sh, mx1, s1);
     if (t == 0) {
         stat[2 * r] = mx1;
         stat[2 * r + 1] = logf(s1);
@@ -145,8 +118,8 @@ __global__ __launch_bounds__(256) void mixture_partial_kernel(const float* __res
         int bi = INT_MAX;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            if (!((taken >> j) & 1u) && mix_better(v[j], idx[j], bv, bi)) { bv = v[j]; bi = idx[j]; }
-        mix_wave_best(bv, bi);
+            if (!((taken >> j) & 1u) && better(v[j], idx[j], bv, bi)) { bv = v[j]; bi = idx[j]; }
+        wave_best(bv, bi);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (idx[j] == bi && v[j] == bv) taken |= 1u << j;
@@ -165,7 +138,7 @@ __global__ __launch_bounds__(256) void mixture_partial_kernel(const float* __res
         for (int j = 0; j < 64; ++j) {
             const float ov = __shfl(cv, j, 64);
             const int oi = __shfl(ci, j, 64);
-            if (mix_better(ov, oi, cv, ci) || (ov == cv && oi == ci && j < lane)) ++rank;
+            if (better(ov, oi, cv, ci) || (ov == cv && oi == ci && j < lane)) ++rank;
         }
         if (rank < kc) {
             const long o = (g * nchunks + chunk) * kc + rank;
@@ -199,9 +172,9 @@ __global__ __launch_bounds__(64) void mixture_merge_kernel(const float* __restri
         for (int j = lane; j < n; j += 64) {
             const float v = pv[j];
             const int i = pi[j];
-            if (mix_better(lv, li, v, i) && mix_better(v, i, bv, bi)) { bv = v; bi = i; }
+            if (better(lv, li, v, i) && better(v, i, bv, bi)) { bv = v; bi = i; }
         }
-        mix_wave_best(bv, bi);
+        wave_best(bv, bi);
         if (lane == 0) {
             top_p[g * kc + p] = bv;
             top_i[g * kc + p] = min(max(bi, 0), V - 1);
@@ -234,7 +207,7 @@ __global__ __launch_bounds__(256) void mixture_advance_kernel(const float* __res
         const long src = pg * K + k, dst = g * K + k;
         double lw = logw_in[src];
         if (live) {
-            const float lsm = (logits[src * ld + min(max(w, 0), V - 1)] - stat[2 * src]) - stat[2 * src + 1];   // decode_pick's term
+            const float lsm = lsm_term(logits[src * ld + min(max(w, 0), V - 1)], stat[2 * src], stat[2 * src + 1]);
             lw += (double)lsm;
         }
         logw_out[dst] = lw;
@@ -273,7 +246,7 @@ extern "C" int vc_mixture_topk_f32(void* stream, const float* logits, long G, in
     const int nchunks = cdiv(V, MIX_CHUNK);
     float* part_v = (float*)ws;
     int32_t* part_i = (int32_t*)(part_v + G * nchunks * kc);
-    if (V <= MIX_LDS_MAX)
+    if (V <= ROW_LDS_MAX)
         hipLaunchKernelGGL(mixture_stat_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)V * sizeof(float), st, logits, V, ld, stat);
     else
         hipLaunchKernelGGL(mixture_stat_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, logits, V, ld, stat);

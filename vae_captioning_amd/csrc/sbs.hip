@@ -4,7 +4,7 @@
 //
 //   vc_sbs_init        the starting state of every image, the image states expanded to the beam rows.
 //   vc_sbs_expand_f32  one workgroup per live, unfinished row: the f32 log-softmax of the row over the full vocabulary
-//                      (decode_pick_kernel's partition, expressions and reduction order: the same bits), a float64 Gumbel per word (injected,
+//                      (row_ops.h: the same bits as vc_decode_pick_f32's), a float64 Gumbel per word (injected,
 //                      or from Philox) and the kc best words by key = (double)lsm + g.  The row is staged in LDS (one read from
 //                      memory); every thread holds the keys of its columns in registers (twelve Philox quads = 48 columns per
 //                      tile of 12 288); every wave picks its best kc by kc rounds of "best pair after the previous winner"
@@ -17,31 +17,17 @@
 #include <float.h>
 #include <limits.h>
 
-#include "common.h"
+#include "row_ops.h"
 #include "vaecap.h"
 
 namespace vc {
 
 constexpr int SBS_MAX_N = 32;         // entries per image: one lane each, n + 1 winners <= 64
 constexpr int SBS_MAX_KC = 33;        // candidates per row: n + 1 (the (n+1)-th largest perturbed score is exact only then)
-constexpr int SBS_LDS_MAX = 12288;    // (diverse.hip's PICK_LDS_MAX) logits rows up to this width are staged in LDS
 constexpr int SBS_QPT = 12;           // Philox quads per thread and tile: 48 float64 keys in registers
 constexpr int SBS_TILE_Q = 256 * SBS_QPT;
 constexpr int SBS_LISTS = 5;          // the four waves' lists + the best kc of the tiles before
 constexpr int SBS_SLOTS = (SBS_MAX_N * SBS_MAX_KC + 63) / 64;   // candidates per lane of vc_sbs_update
-
-// (key descending, column ascending): a strict total order over pairs with distinct columns
-__device__ __forceinline__ bool sbs_better(double ka, int ia, double kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
-
-// the best pair of the wave, in every lane
-__device__ __forceinline__ void sbs_wave_best(double& bk, int& bi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ok = __shfl_xor(bk, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (sbs_better(ok, oi, bk, bi)) { bk = ok; bi = oi; }
-    }
-}
 
 __device__ __forceinline__ double sbs_sane(double k) { return k == k ? k : -INFINITY; }   // a NaN ranks below every number
 
@@ -59,24 +45,12 @@ __global__ __launch_bounds__(256) void sbs_expand_kernel(const float* __restrict
     const long r = blockIdx.x;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if ((int)(r % n) >= count[r / n] || done[r] != 0) return;   // (the same for every thread of the workgroup)
-    const float* p = logits + r * ld;
-    if (STAGE) {
-        for (int c = t; c < V; c += 256) srow[c] = p[c];
-        __syncthreads();
-        p = srow;
-    }
-    // ---- M and S: decode_pick_kernel's contiguous chunks and reductions
-    const int per = (V + 255) / 256;
-    const int c0 = min(V, t * per), c1 = min(V, c0 + per);
-    float bv = -INFINITY;
-    for (int c = c0; c < c1; ++c) {
-        const float v = p[c];
-        if (v > bv) bv = v;
-    }
-    const float mx1 = block_max<256>(bv, sh);
-    float s1 = 0.f;
-    for (int c = c0; c < c1; ++c) s1 += __expf(p[c] - mx1);
-    s1 = block_sum<256>(s1, sh);
+    const float* p = stage_row<STAGE>(logits + r * ld, V, srow);
+    // ---- M and S (row_ops.h)
+    int c0, c1;
+    row_chunk(V, c0, c1);
+    float mx1, s1;
+    row_max_sum(p, c0, c1, sh, mx1, s1);
     const float ls = logf(s1);
     // ---- the noise: element r*V + v of the call's stream; a thread takes whole Philox quads of the flat index
     const int rd = round ? round[0] : 0;
@@ -114,7 +88,7 @@ __global__ __launch_bounds__(256) void sbs_expand_kernel(const float* __restrict
                         const double u = ((double)rr[e] + 0.5) * 2.3283064365386963e-10;   // (0, 1): never 0 or 1
                         g = -log(-log(u));
                     }
-                    const float lsm = (p[v] - mx1) - ls;
+                    const float lsm = lsm_term(p[v], mx1, ls);
                     k = sbs_sane((double)lsm + g);
                 }
                 key[j * 4 + e] = k;
@@ -133,10 +107,10 @@ __global__ __launch_bounds__(256) void sbs_expand_kernel(const float* __restrict
                     const int v = 4 * (tq0 + j * 256 + t) + e - off;
                     const int idx = (v >= 0 && v < V) ? v : INT_MAX;
                     const double k = key[j * 4 + e];
-                    if (sbs_better(pk, pi, k, idx) && sbs_better(k, idx, bk, bi)) { bk = k; bi = idx; }
+                    if (better(pk, pi, k, idx) && better(k, idx, bk, bi)) { bk = k; bi = idx; }
                 }
             }
-            sbs_wave_best(bk, bi);
+            wave_best(bk, bi);
             if (lane == pp) { wk = bk; wi = bi; }
             pk = bk;
             pi = bi;
@@ -168,8 +142,8 @@ __global__ __launch_bounds__(256) void sbs_expand_kernel(const float* __restrict
                 int bi = INT_MAX;
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
-                    if (sbs_better(pk, pi, ek[j], ei[j]) && sbs_better(ek[j], ei[j], bk, bi)) { bk = ek[j]; bi = ei[j]; }
-                sbs_wave_best(bk, bi);
+                    if (better(pk, pi, ek[j], ei[j]) && better(ek[j], ei[j], bk, bi)) { bk = ek[j]; bi = ei[j]; }
+                wave_best(bk, bi);
                 if (lane == pp) { mk = bk; mi = bi; }
                 pk = bk;
                 pi = bi;
@@ -185,7 +159,7 @@ __global__ __launch_bounds__(256) void sbs_expand_kernel(const float* __restrict
         const int idx = min(max(mi, 0), V - 1);   // (kc <= V: every listed pair is a word)
         const long o = r * kc + lane;
         cand_key[o] = mk;
-        cand_lsm[o] = (p[idx] - mx1) - ls;
+        cand_lsm[o] = lsm_term(p[idx], mx1, ls);
         cand_idx[o] = idx;
     }
 }
@@ -371,7 +345,7 @@ extern "C" int vc_sbs_expand_f32(void* stream, const float* logits, long rows, i
     VC_CHECK_ARG(V > 0 && ld >= V, "bad shape (ld >= V)");
     VC_CHECK_ARG(kc >= 1 && kc <= SBS_MAX_KC && kc <= V, "kc must be 1..33 and <= V");
     VC_CHECK_ARG(!gumbel || g_rounds >= 1, "g_rounds must be >= 1 with injected noise");
-    if (V <= SBS_LDS_MAX)
+    if (V <= ROW_LDS_MAX)
         hipLaunchKernelGGL(sbs_expand_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)V * sizeof(float), (hipStream_t)stream, logits, rows, n, V,
                            ld, count, done, kc, gumbel, g_rounds, round, seed, offset, step, cand_key, cand_lsm, cand_idx);
     else

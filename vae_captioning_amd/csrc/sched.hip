@@ -5,14 +5,14 @@
 //   vc_sched_mix_f32   one workgroup per position (t, n) of the time-major [T, N] token array.  The eligibility (1 <= t < lens[n]) and
 //                      coin (coin[t, n] < rate) tests come first: a position that fails one copies its gold token and touches no logits
 //                      memory.  A selected position reads logits row (t-1) * N + n ONCE from memory (16-byte loads when the row's
-//                      address allows them) into LDS and draws the word there: the inverse-CDF draw with multinomial_rows_kernel's
-//                      256-chunk partition, expressions and summation order (same bits, same token -- decode_pick_kernel's recipe), or
-//                      the first maximum (argmax_rows_kernel's token) when u is NULL.  Rows too wide for the LDS (V > SCHED_LDS_MAX,
+//                      address allows them) into LDS and draws the word there: the inverse-CDF draw, or the first maximum when u is
+//                      NULL, both row_ops.h's (the tokens of vc_multinomial_rows_f32 / vc_decode_pick_f32 and of
+//                      vc_argmax_rows_f32).  Rows too wide for the LDS (V > SCHED_LDS_MAX,
 //                      beyond every vocabulary the engine runs the mode with) are read in place, several times.
 //                      The rate comes from the device step counter (constant / linear / inverse-sigmoid schedule): a captured step
 //                      needs no host value.  A one-workgroup kernel behind it counts the eligible and the replaced positions with the
 //                      same tests and reports the rate (plain integer adds by one thread: no atomics).
-#include "common.h"
+#include "row_ops.h"
 #include "vaecap.h"
 
 namespace vc {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void sched_mix_kernel(const float* __restrict_
     const int V4 = vec ? (V >> 2) : 0;          // whole quads inside [0, V); the rest (every column of an unaligned row) by 4-byte loads
     if (u == nullptr) {
         // ---- the first maximum.  A thread meets its columns in ascending order, so `>` keeps the first of its maxima; the tree then
-        // prefers the lower index among equal values: argmax_rows_kernel's token
+        // prefers the lower index among equal values (row_ops.h: block_first_max)
         float bv = -INFINITY;
         int bi = 0x7fffffff;
         for (int q = tid; q < V4; q += 256) {
@@ -68,25 +68,12 @@ __global__ __launch_bounds__(256) void sched_mix_kernel(const float* __restrict_
             const float v = p[c];
             if (v > bv) { bv = v; bi = c; }
         }
-        part[tid] = bv;
-        si[tid] = bi;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) {
-                const float v2 = part[tid + o];
-                const int i2 = si[tid + o];
-                if (v2 > part[tid] || (v2 == part[tid] && i2 < si[tid])) {
-                    part[tid] = v2;
-                    si[tid] = i2;
-                }
-            }
-            __syncthreads();
-        }
+        block_first_max(bv, bi, part, si);
         if (tid == 0) out[pos] = min(si[0], V - 1);   // (a row without any value above -inf: a token inside the vocabulary all the same)
         return;
     }
     // ---- the inverse-CDF draw.  The maximum of the scaled row is taken while the row is staged (a maximum does not depend on the
-    // order); everything that is summed follows multinomial_rows_kernel, expression for expression.
+    // order); everything that is summed is row_ops.h's.
     float mx = -INFINITY;
     if (STAGE) {
         for (int q = tid; q < V4; q += 256) {
@@ -105,31 +92,10 @@ __global__ __launch_bounds__(256) void sched_mix_kernel(const float* __restrict_
         for (int c = tid; c < V; c += 256) mx = fmaxf(mx, p[c] * inv_temp);
     }
     mx = block_max<256>(mx, sh);
-    // contiguous chunk per thread so that the scan order is the index order
-    const int per = (V + 255) / 256;
-    const int c0 = tid * per, c1 = min(V, c0 + per);
-    float s = 0.f;
-    for (int c = c0; c < c1; ++c) s += __expf(p[c] * inv_temp - mx);
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        float tot = 0.f;
-        for (int i = 0; i < 256; ++i) tot += part[i];
-        const float target = u[pos] * tot;
-        float run = 0.f;
-        int k = 0;
-        for (; k < 255; ++k) {
-            if (run + part[k] > target) break;
-            run += part[k];
-        }
-        int idx = min(V - 1, k * per);
-        for (int c = k * per; c < min(V, (k + 1) * per); ++c) {   // (STAGE: the walk inside the chosen chunk reads LDS)
-            run += __expf(p[c] * inv_temp - mx);
-            idx = c;
-            if (run > target) break;
-        }
-        out[pos] = idx;
-    }
+    int c0, c1;
+    const int per = row_chunk(V, c0, c1);
+    row_cdf_part(p, c0, c1, inv_temp, mx, part);
+    if (tid == 0) out[pos] = row_cdf_pick(p, V, per, inv_temp, mx, part, u + pos);   // (STAGE: the walk inside the chosen chunk reads LDS)
 }
 
 // stats[0] += eligible positions, stats[1] += replaced positions, rate_out[0] = the rate: one workgroup, the mixing kernel's tests

@@ -105,17 +105,6 @@ __global__ __launch_bounds__(256) void logprob_merge_kernel(const float2* __rest
     lp[r] = lab[r] - (m + logf(s));
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 constexpr int SCORE_MAX_K = 256;
 
 // One wave per caption; lane l owns the draws l, l + 64, ... (K <= 256).
@@ -132,18 +121,18 @@ __global__ __launch_bounds__(64) void score_reduce_kernel(const float* __restric
         const int k = lane + j * 64;
         double s = 0.0;
         if (k < K) {
-            for (int t = 0; t < n; ++t) s += (double)lp[t * N + (long)c * K + k];   // ascending t, float64 sum
+            for (int t = 0; t < n; ++t) s += (double)lp[t * N + (long)c * K + k];   // ascending t, float64 sum (bound_reduce_kernel repeats it)
             logprob[(long)c * K + k] = s;
             mx = fmax(mx, s);
         }
         v[j] = s;
     }
-    mx = wave_max_f64(mx);
+    mx = wave_max(mx);
     double e = 0.0;
 #pragma unroll
     for (int j = 0; j < SCORE_MAX_K / 64; ++j)
         if (lane + j * 64 < K) e += exp(v[j] - mx);
-    e = wave_sum_f64(e);
+    e = wave_sum(e);
     if (lane == 0) marginal[c] = mx + log(e) - log((double)K);
 }
 
