@@ -48,6 +48,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the stochastic beam search entries vc_sbs_init / vc_sbs_expand_f32 / vc_sbs_update.
  *      Added within 4 (additive, no layout change): the scheduled-sampling entry vc_sched_mix_f32.
  *      Added within 4 (additive, no layout change): the ROUGE-L entry vc_lcs_overlap.
+ *      Added within 4 (additive, no layout change): the in-set CIDEr-D entry vc_cider_gram.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -730,6 +731,21 @@ int vc_consensus_score(void* stream, int B, int k, const int32_t* nbr, const int
                        const uint64_t* r_keys, const float* r_w, const float* r_norm, const int32_t* r_len, const int32_t* cand_img,
                        int max_cands, const int32_t* c_off, const int32_t* c_nnz, const uint64_t* c_keys, const float* c_w,
                        const float* c_norm, const int32_t* c_len, int m, double* score);
+
+/* ------------------------------------------------------------------------------------
+ * In-set CIDEr-D (mbr.py: CiderGram; csrc/cider_gram.hip): every caption of an image against every caption of the same image.
+ *   cider_gram   ONE ngram_vectors table (off, nnz, keys, w, norm [.,4], words); image b (< B) owns its rows cand_img[b] ..
+ *                cand_img[b+1] - 1 (n_b <= max_cands <= 256).  For row i of image b and column j < n_b,
+ *                  gram[i * ld + j] = CIDEr-D(hypothesis = caption i, reference = caption j of the image)     (ld >= max_cands)
+ *                in f32 by consensus_score's pair function (csrc/cider_pair.h): the same bits for the same pair.  Columns j >= n_b of
+ *                a row are not written.
+ *                  mbr[i] = (sum_j weight[j] * (double)gram[i][j]) / sum_j weight[j]
+ *                over ALL j of the image (i included), weight [C] per caption row (NULL: all 1), in float64 with a fixed order (one term
+ *                per lane, an xor shuffle tree per wave, the wave sums in wave order; no atomics); 0.0 when the weight sum is 0.
+ *                gram or mbr may be NULL (not both).  A row's bits depend on its image's captions (and weights) only: not on B, the
+ *                other images or the row's place in its group.  One workgroup per image and 4 rows, 12 KiB LDS. */
+int vc_cider_gram(void* stream, int B, const int32_t* cand_img, int max_cands, const int32_t* off, const int32_t* nnz, const uint64_t* keys,
+                  const float* w, const float* norm, const int32_t* words, const double* weight, float* gram, long ld, double* mbr);
 
 /* ------------------------------------------------------------------------------------
  * Evaluation of caption sets (evaluate.py: CaptionEvaluator; csrc/evaluate.hip): BLEU-style clipped n-gram counts.

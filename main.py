@@ -102,6 +102,23 @@ def consensus_index(params, tr, cap_dict, coco_train):
     return ConsensusIndex(tr.cap, feats, caps, bos, eos, k=params.consensus_k, m=params.consensus_m, vocab_size=cap_dict.vocab_size)
 
 
+def mbr_gram(params, tr, cap_dict, coco_train, real=None):
+    """--diverse_rerank mbr: the idf table of the training captions (per image; no features are read, so --fine_tune works) that the
+    in-set CIDEr-D of an image's captions is weighted with."""
+    from vae_captioning_amd.mbr import CiderGram
+    if real is not None:
+        corpus = [real.caps[n] for n in real.names if real.caps[n]]
+    elif coco_train is not None:
+        from vae_captioning_amd.consensus import captions_from_generator
+        corpus = [c for c in captions_from_generator(coco_train) if c]
+    elif params.synthetic:
+        corpus = training_index_data(params, None)[1]
+    else:
+        raise SystemExit("--diverse_rerank mbr needs the MSCOCO training captions (--coco_dir) or --synthetic for its idf")
+    print("mbr re-ranking: idf over the captions of %d training images" % len(corpus))
+    return CiderGram(tr.cap, corpus, cap_dict.word2idx["<BOS>"], cap_dict.word2idx["<EOS>"], cap_dict.vocab_size)
+
+
 def training_captions(params, coco_train):
     """--eval_captions: the flat training captions `novel` is measured against -- the captions of the training generator's images (a
     walk of its caption table: no features are read, so --fine_tune works too) or of --synthetic's seeded index; None when neither is
@@ -311,6 +328,8 @@ def main(params):
         decoder = Decoder(None, None, None, params, cap_dict)
         if params.sample_gen in ("diverse", "stochastic_beam") and params.diverse_rerank == "consensus":
             decoder.consensus_index = consensus_index(params, tr, cap_dict, coco_train)
+        if params.sample_gen in ("diverse", "stochastic_beam") and params.diverse_rerank == "mbr":
+            decoder.mbr = mbr_gram(params, tr, cap_dict, coco_train, real)
         if params.sample_gen == "constrained_beam":   # the words the captions must mention, looked up in the vocabulary once
             from vae_captioning_amd.constraints import load_constraints
             decoder.constraints = load_constraints(params.constraints, cap_dict.word2idx, cap_dict.vocab_size, cap_dict.word2idx["<BOS>"],

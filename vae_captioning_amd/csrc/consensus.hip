@@ -8,8 +8,10 @@
 //                              workgroup
 //   vc_ngram_vectors           per caption (one wave): its words, sorted distinct 1..4-gram keys, count * idf weights, the four norms
 //   vc_consensus_score         per (image, 4 candidates): the pool of the neighbours' captions, CIDEr-D of every (candidate, pool
-//                              caption) pair in f32, each candidate's m' best sorted in LDS, their float64 mean
+//                              caption) pair in f32 (cider_pair.h: the one definition of the pair score, shared with
+//                              cider_gram.hip), each candidate's m' best sorted in LDS, their float64 mean
 #include "common.h"
+#include "cider_pair.h"
 #include "vaecap.h"
 
 namespace vc {
@@ -17,7 +19,7 @@ namespace vc {
 constexpr int TOPKW_CHUNK = 4096;     // keys per workgroup (32 KiB of LDS)
 constexpr int TOPKW_MAX_K = 256;
 constexpr int NG_MAX_WORDS = 64;      // words per caption
-constexpr int NG_SLOTS = 256;         // 4 * 64 n-gram slots (64 + 63 + 62 + 61 used at most)
+constexpr int NG_SLOTS = CP_SLOTS;    // 4 * 64 n-gram slots (64 + 63 + 62 + 61 used at most)
 constexpr int CS_CPB = 4;             // candidates per scoring workgroup
 constexpr int CS_MAX_POOL = 2048;
 constexpr int CS_MAX_K = 256;
@@ -251,8 +253,8 @@ __global__ __launch_bounds__(64) void ngram_vectors_kernel(const int32_t* __rest
 
 // Workgroup (b, group of CS_CPB candidates of image b).  The pool (every caption of the k neighbours, neighbour order) and each
 // candidate's sorted keys / weights are staged in LDS; thread j scores pool captions j, j + 256, ... against the group's candidates
-// (each reference key looked up by binary search in the candidate's keys), then each candidate's pool scores are sorted and the m'
-// largest summed in float64.  LDS: 8 + 4 * 3 + 4 * 8 KiB + small = ~53 KiB (two workgroups per CU fit in 160 KiB).
+// (cider_pair_scores: each reference key looked up by binary search in the candidate's keys), then each candidate's pool scores are
+// sorted and the m' largest summed in float64.  LDS: 8 + 4 * 3 + 4 * 8 KiB + small = ~53 KiB (two workgroups per CU fit in 160 KiB).
 __global__ __launch_bounds__(256) void consensus_score_kernel(int k, const int32_t* __restrict__ nbr, const int32_t* __restrict__ img_cap,
                                                               const int32_t* __restrict__ r_off, const int32_t* __restrict__ r_nnz,
                                                               const uint64_t* __restrict__ r_keys, const float* __restrict__ r_w,
@@ -290,82 +292,14 @@ __global__ __launch_bounds__(256) void consensus_score_kernel(int k, const int32
     }
     np = min(np, CS_MAX_POOL);
     for (int i = 0; i < cnt && p0 + i < CS_MAX_POOL; ++i) s_pool[p0 + i] = img_cap[id] + i;
-    int cn[CS_CPB], cl[CS_CPB];
-    float cnorm[CS_CPB][4];
-#pragma unroll
-    for (int c = 0; c < CS_CPB; ++c) {
-        cn[c] = 0;
-        cl[c] = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cnorm[c][q] = 0.f;
-        if (c < nc) {
-            const int ci = c0 + c;
-            cn[c] = min(c_nnz[ci], NG_SLOTS);
-            cl[c] = c_len[ci];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) cnorm[c][q] = c_norm[(long)ci * 4 + q];
-            for (int i = t; i < cn[c]; i += 256) {
-                s_ck[c][i] = c_keys[(long)c_off[ci] + i];
-                s_cw[c][i] = c_w[(long)c_off[ci] + i];
-            }
-        }
-    }
+    CiderHyps<CS_CPB> hyp;
+    cider_stage_hyps<CS_CPB>(c0, nc, c_off, c_nnz, c_keys, c_w, c_norm, c_len, s_ck, s_cw, hyp);
     __syncthreads();
     for (int j = t; j < np; j += 256) {
-        const int r = s_pool[j];
-        const long ro = r_off[r];
-        const int rn = r_nnz[r];
-        float sim[CS_CPB][4];
+        float sc[CS_CPB];   // CIDEr-D of the group's candidates against pool caption j (cider_pair.h: the one definition)
+        cider_pair_scores<CS_CPB>(s_pool[j], r_off, r_nnz, r_keys, r_w, r_norm, r_len, s_ck, s_cw, hyp, sc);
 #pragma unroll
-        for (int c = 0; c < CS_CPB; ++c)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sim[c][q] = 0.f;
-        for (int e0 = 0; e0 < rn; e0 += 8) {   // eight keys in flight per load round (the loop is latency-bound otherwise)
-            uint64_t kk[8];
-            float ww[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const bool ok = e0 + u < rn;
-                kk[u] = ok ? r_keys[ro + e0 + u] : 0ull;
-                ww[u] = ok ? r_w[ro + e0 + u] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (e0 + u >= rn) break;
-                const uint64_t key = kk[u];
-                const float wr = ww[u];
-                const int n = key_order(key) - 1;
-                int pos[CS_CPB];   // per candidate the last slot with a key < key: fixed 8 steps, the four searches interleave
-#pragma unroll
-                for (int c = 0; c < CS_CPB; ++c) pos[c] = -1;
-#pragma unroll
-                for (int st = NG_SLOTS / 2; st > 0; st >>= 1)
-#pragma unroll
-                    for (int c = 0; c < CS_CPB; ++c)
-                        if (pos[c] + st < cn[c] && s_ck[c][pos[c] + st] < key) pos[c] += st;
-#pragma unroll
-                for (int c = 0; c < CS_CPB; ++c) {
-                    const int lo = pos[c] + 1;
-                    if (lo < cn[c] && s_ck[c][lo] == key) {
-                        const float v = fminf(s_cw[c][lo], wr) * wr;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) sim[c][q] += q == n ? v : 0.f;
-                    }
-                }
-            }
-        }
-        const int rl = r_len[r];
-        float rnorm[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) rnorm[q] = r_norm[(long)r * 4 + q];
-#pragma unroll
-        for (int c = 0; c < CS_CPB; ++c) {
-            float s = 0.f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s += (cnorm[c][q] > 0.f && rnorm[q] > 0.f) ? sim[c][q] / (cnorm[c][q] * rnorm[q]) : 0.f;
-            const float d = (float)(cl[c] - rl);
-            s_sc[c][j] = 10.0f * expf(-(d * d) / 72.0f) * (0.25f * s);
-        }
+        for (int c = 0; c < CS_CPB; ++c) s_sc[c][j] = sc[c];
     }
     const int N = next_pow2(np);
     for (int i = np + t; i < N; i += 256)

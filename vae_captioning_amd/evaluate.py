@@ -26,6 +26,11 @@ BLEU here is the plain corpus-level definition (corpus_bleu): it does NOT imitat
 1e-15 "small" terms), and the tokens are vocabulary ids after the vocabulary cut, not PTB tokens -- the numbers compare runs of this
 project with each other, not with a leaderboard ("Evaluation").
 
+`evaluate(candidates, self_cider=True)` adds SET_METRICS from one more pass over the CIDEr-D path's candidate table (mbr.py,
+csrc/cider_gram.hip's vc_cider_gram: the CIDEr-D of every caption of an image against every caption of the same image): `self_cider`,
+the Self-CIDEr diversity of the set (host float64 eigenvalues of that matrix), and `mbr_cider_d`, the CIDEr-D of the caption with the
+highest mean in-set CIDEr-D -- what minimum-Bayes-risk selection would take.  Without it nothing changes and the kernel is not launched.
+
 Single-caption modes (greedy, sample, beam_search) hand in lists of one: the set metrics are then those of lists of one -- `distinct`
 1.0, `mbleu_4` 0.0 (no hypotheses), `oracle_cider_d` = `mean_cider_d` = `cider_d`, `oracle_rouge_l` = `mean_rouge_l` = `rouge_l`."""
 import math
@@ -41,6 +46,7 @@ from .generate import DIVERSE_MAX_DRAWS
 
 METRICS = ("bleu_1", "bleu_2", "bleu_3", "bleu_4", "cider_d", "oracle_cider_d", "mean_cider_d", "distinct", "div_1", "div_2", "mbleu_4",
            "novel", "rouge_l", "oracle_rouge_l", "mean_rouge_l")
+SET_METRICS = ("self_cider", "mbr_cider_d")   # evaluate(self_cider=True) only: they need the in-set CIDEr-D matrix (mbr.py, vc_cider_gram)
 MAX_REFS = MAX_POOL       # references per image (vc_consensus_score stages an image's pool in LDS)
 OUT_COLS = 17             # total, match, distinct, unseen [., 4] + ref_len per hypothesis
 LCS_COLS = 3              # lcs_max, rec_lcs, rec_len per hypothesis (vc_lcs_overlap)
@@ -198,16 +204,35 @@ class CaptionEvaluator(object):
     def _idf_vectors(self, W, L, head=None):
         return ngram_vectors(self.lib, self.dev, W, L, self.bos, self.eos, self.df_keys, self.idf, self.n_df, self.idf_unseen, head)
 
-    def _cider(self, W, L, cand_img, max_cands):
-        """CIDEr-D of every candidate: the mean over its image's references (vc_consensus_score, k = 1, m = 2048) -> device float64"""
-        cv, rv, B = self._idf_vectors(W, L, head=cand_img), self.ref_idf, self.B
+    def _cider(self, W, L, cand_img, max_cands, table=None):
+        """CIDEr-D of every candidate: the mean over its image's references (vc_consensus_score, k = 1, m = 2048) -> device float64.
+        table: the candidates' idf-weighted vectors (_idf_vectors(W, L, head=cand_img)) when the caller has built them already."""
+        cv, rv, B = table if table is not None else self._idf_vectors(W, L, head=cand_img), self.ref_idf, self.B
         out = torch.empty(max(1, cv.n), dtype=torch.float64, device=self.dev)
         self.lib.vc_consensus_score(_stream(), B, 1, P(rv.head[B + 1:]), P(rv.head[:B + 1]), P(rv.off), P(rv.nnz), P(rv.keys), P(rv.w),
                                     P(rv.norm), P(rv.words), P(cv.head), int(max_cands), P(cv.off), P(cv.nnz), P(cv.keys), P(cv.w),
                                     P(cv.norm), P(cv.words), MAX_REFS, P(out))
         return out
 
-    def evaluate(self, candidates):
+    def _set_metrics(self, cv, per, cider, cand_img):
+        """evaluate(self_cider=True): one vc_cider_gram pass over the candidates' idf-weighted table `cv` (uniform weights), then per
+        image Self-CIDEr of its matrix (host float64 eigenvalues) and the caption MBR selection would take: the first maximum of mbr"""
+        from . import mbr as M
+        B = self.B
+        if cv is None:
+            G, mb = [np.zeros((0, 0), np.float32)] * B, [np.zeros(0, np.float64)] * B
+        else:
+            G, mb = M.gram_of_table(self.lib, self.dev, cv, cv.head, per)
+        sc = np.array([M.self_cider(g) for g in G], np.float64)
+        choice = np.array([int(np.argmax(m)) if m.size else -1 for m in mb], np.int64)
+        chosen = np.array([cider[cand_img[b] + choice[b]] if choice[b] >= 0 else np.nan for b in range(B)], np.float64)
+        return sc, choice, chosen, mb
+
+    def evaluate(self, candidates, self_cider=False):
+        """self_cider=True adds SET_METRICS: `self_cider`, the mean over the images that list a caption of mbr.self_cider of the
+        image's in-set CIDEr-D matrix, and `mbr_cider_d`, the mean over those images of the CIDEr-D (against the human references) of
+        the caption with the highest mean in-set CIDEr-D (uniform weights, first maximum); per_image gains self_cider, mbr_choice (-1:
+        no caption) and caption_mbr.  Without it vc_cider_gram is never launched and nothing else changes."""
         B = self.B
         if len(candidates) != B:
             raise ValueError("%d images of candidates for %d images of references" % (len(candidates), B))
@@ -235,13 +260,14 @@ class CaptionEvaluator(object):
             for i, ref in enumerate((self.ref_counts, hyp, hyp)):
                 _launch(self.lib, hyp, ref, rng[i], out[i])
             _launch_lcs(self.lib, hyp, self.ref_counts, rng[0], flat_out[3 * OUT_COLS * C:])   # the word rows of the two count tables
-            cider_dev = self._cider(W, L, cand_img, int(per.max()))
+            cv = self._idf_vectors(W, L, head=cand_img)          # built once: the CIDEr-D call and the in-set matrices share it
+            cider_dev = self._cider(W, L, cand_img, int(per.max()), table=cv)
             ints = flat_out.cpu().numpy()
             cider = cider_dev.cpu().numpy()[:C]
             to_ref, to_prev, to_rest = (_split(ints[OUT_COLS * C * i:OUT_COLS * C * (i + 1)], C) for i in range(3))
             lcs = _split_lcs(ints[3 * OUT_COLS * C:], C)
         else:
-            cider = np.zeros(0, np.float64)
+            cv, cider = None, np.zeros(0, np.float64)
             to_ref = to_prev = to_rest = _split(np.zeros(0, np.int32), 0)
             lcs = _split_lcs(np.zeros(0, np.int32), 0)
         # ---- host: float64 from exact integers
@@ -281,4 +307,8 @@ class CaptionEvaluator(object):
                                 caption_cider_d=[cider[cand_img[b]:cand_img[b + 1]].copy() for b in range(B)],
                                 rouge_l=top_rouge, oracle_rouge_l=best_rouge,
                                 caption_rouge_l=[rouge[cand_img[b]:cand_img[b + 1]].copy() for b in range(B)])
+        if self_cider:
+            sc, choice, chosen, mb = self._set_metrics(cv, per, cider, cand_img)
+            res.update(self_cider=_mean(sc[have]), mbr_cider_d=_mean(chosen[have]))
+            res["per_image"].update(self_cider=sc, mbr_choice=choice, caption_mbr=mb)
         return res

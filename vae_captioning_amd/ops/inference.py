@@ -8,7 +8,9 @@ always decoded with `online_inference`, as in the reference.  `sample_gen == "di
 `diverse_inference`; `./val_{gen_name}.json` keeps the COCO shape with each image's top caption and
 `./val_{gen_name}_diverse.json` holds the full per-image lists (captions, scores, counts).  With `params.diverse_rerank ==
 "consensus"` (a `consensus.ConsensusIndex` attached to the decoder) the top caption is the consensus winner and the lists also hold
-the consensus scores; with `"marginal"` they hold each caption's likelihood over all of the image's draws.
+the consensus scores; with `"marginal"` they hold each caption's likelihood over all of the image's draws; with `"mbr"` (an
+`mbr.CiderGram` attached to the decoder) the top caption has the highest expected CIDEr-D against the image's own captions and the
+lists hold those values under `"mbr"`.
 `sample_gen == "diverse_beam"` (additive): group beam search (`decoder.diverse_beam_search`), written the same way: the merged ranked
 captions of an image's groups in `./val_{gen_name}_diverse.json`, its best one in `./val_{gen_name}.json`.
 `sample_gen == "stochastic_beam"` (additive): stochastic beam search (`decoder.stochastic_beam_search`), written the same way: the
@@ -32,7 +34,9 @@ captions).
 image in the diverse modes, a list of one otherwise) is evaluated against ALL human captions of each image (taken from the generator's
 caption table by image id, `validation_references`: the batches carry one random caption per image) (`decoder.caption_evaluator`,
 evaluate.py: BLEU, CIDEr-D, oracle and diversity metrics) once after the loop -> `./val_{gen_name}_metrics.json`, one printed line
-per metric.  The caption files are written exactly as without the flag.
+per metric.  The caption files are written exactly as without the flag.  `params.eval_self_cider` (additive, with `eval_captions`): the
+evaluator also makes its in-set CIDEr-D pass (mbr.py, vc_cider_gram) and the file and the printed lines gain `self_cider` and
+`mbr_cider_d`.
 `params.no_repeat_ngram` / `min_len` / `repetition_penalty` / `banned_words` (additive): the decoding controls
 (`controls.DecodeControls`, attached to the decoder as `decoder.controls`) go to whichever mode decodes, the test set's
 `online_inference` included; the caption records gain nothing, `./val_{gen_name}_metrics.json` lists the four flags."""
@@ -127,17 +131,21 @@ EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "di
 
 def store_metrics(params, metrics, images, captions):
     """./val_{gen_name}_metrics.json: the evaluator's dict without its per-image arrays, the number of images and of captions evaluated,
-    sample_gen and the decoding flags in force; one printed line per metric."""
-    from ..evaluate import METRICS
-    out = {k: metrics[k] for k in METRICS}
+    sample_gen and the decoding flags in force; one printed line per metric.  With params.eval_self_cider also the two SET_METRICS
+    (self_cider, mbr_cider_d) and the flag itself; without it the file and the lines are those of a run that never knew the flag."""
+    from ..evaluate import METRICS, SET_METRICS
+    names = METRICS + (SET_METRICS if getattr(params, "eval_self_cider", False) else ())
+    out = {k: metrics[k] for k in names}
     out.update(images=int(images), captions=int(captions), sample_gen=params.sample_gen)
     out.update({k: getattr(params, k) for k in EVAL_FLAGS if hasattr(params, k)})
+    if len(names) > len(METRICS):
+        out["eval_self_cider"] = True
     path = "./val_{}_metrics.json".format(params.gen_name)
     if os.path.exists(path):
         os.remove(path)
     with open(path, "w") as fh:
         json.dump(out, fh)
-    for k in METRICS:
+    for k in names:
         print("%s: %s" % (k, "n/a (no training captions at hand)" if out[k] is None else "%.6f" % out[k]))
     print("wrote the metrics of %d captions of %d images to %s" % (captions, images, path))
     return out
@@ -169,7 +177,9 @@ def evaluate_decoded(params, decoder, references, decoded):
     if len(keep) < len(references):
         print("%d images without a human caption are not evaluated" % (len(references) - len(keep)))
     references, decoded = [references[i] for i in keep], [decoded[i] for i in keep]
-    return store_metrics(params, decoder.caption_evaluator(references).evaluate(decoded), len(decoded), sum(map(len, decoded)))
+    evaluator = decoder.caption_evaluator(references)
+    metrics = evaluator.evaluate(decoded, self_cider=True) if getattr(params, "eval_self_cider", False) else evaluator.evaluate(decoded)
+    return store_metrics(params, metrics, len(decoded), sum(map(len, decoded)))
 
 
 def _store(path, records):

@@ -26,7 +26,7 @@ _DEFAULTS = dict(
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
-    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False,
+    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False, eval_self_cider=False,
     bound_draws=0, marginal_draws=20, constraints=None, cbs_width=0,
     no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
     # training objective options (every one off by default: the reference's objective)
@@ -55,10 +55,11 @@ _FLAGS = [
     ("--features_pickle", "features_pickle", str, None), ("--cluster_pickle", "cluster_pickle", str, None),
     ("--ckpt_format", "ckpt_format", str, ["tf", "npz"]),
     ("--diverse_draws", "diverse_draws", int, None), ("--diverse_method", "diverse_method", str, ["greedy", "sample"]),
-    ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal"]), ("--consensus_k", "consensus_k", int, None),
+    ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal", "mbr"]), ("--consensus_k", "consensus_k", int, None),
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
     ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
+    ("--eval_self_cider", "eval_self_cider", "flag", None),
     ("--bound_draws", "bound_draws", int, None), ("--marginal_draws", "marginal_draws", int, None),
     ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
     ("--no_repeat_ngram", "no_repeat_ngram", int, None), ("--min_len", "min_len", int, None),
@@ -84,7 +85,9 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--diverse_draws": "--sample_gen diverse: latent draws per image (1..256; default 20)",
          "--diverse_method": "--sample_gen diverse: decoding of each draw (greedy or sample; default greedy)",
          "--diverse_rerank": "--sample_gen diverse: order of each image's captions (likelihood, consensus with the captions of its "
-                             "nearest training images, or marginal: the likelihood over all of the image's draws; default likelihood)",
+                             "nearest training images, marginal: the likelihood over all of the image's draws, or mbr: the expected CIDEr-D "
+                             "against the image's own captions, weighted by their counts -- minimum-Bayes-risk selection, which needs "
+                             "only the training captions for its idf; default likelihood)",
          "--consensus_k": "--diverse_rerank consensus: nearest training images per image (1..256; default 90)",
          "--consensus_m": "--diverse_rerank consensus: best-matching pool captions averaged per candidate (>= 1; default 125)",
          "--score_draws": "--mode inference: also score the validation images' human captions under this many prior draws and write "
@@ -99,6 +102,9 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                     "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)",
          "--eval_captions": "--mode inference: also evaluate the validation captions against the images' human captions on the GPU (BLEU, "
                             "CIDEr-D, oracle CIDEr-D, ROUGE-L, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json",
+         "--eval_self_cider": "--eval_captions: also report self_cider (Self-CIDEr diversity of each image's caption set, from the "
+                              "eigenvalues of its in-set CIDEr-D matrix) and mbr_cider_d (the CIDEr-D of the caption that "
+                              "minimum-Bayes-risk selection would take)",
          "--bound_draws": "--mode inference: also bound the likelihood of the validation images' human captions with this many posterior "
                           "draws per caption (ELBO, importance-weighted bound, KL, effective sample size, active latent units) and "
                           "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)",
@@ -288,6 +294,8 @@ class Parameters(object):
                 ap.error("--sched_sampling is a way of training: not with --mode %s" % self.mode)
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
+        if self.eval_self_cider and not self.eval_captions:
+            ap.error("--eval_self_cider belongs to --eval_captions")
         if self.synthetic:
             self.vocab_size = int(args["vocab"]) if args["vocab"] is not None else 10000
         self.hdf5_file = self.coco_dir + os.path.basename(self.hdf5_file)  # the image array lives next to the data set

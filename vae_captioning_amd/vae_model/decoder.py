@@ -30,6 +30,7 @@ class Decoder(object):
         self.c_i_ph = None
         self.cap_clusters = None
         self.consensus_index = None  # consensus.ConsensusIndex: --diverse_rerank consensus re-ranks diverse captions against it
+        self.mbr = None              # mbr.CiderGram: --diverse_rerank mbr re-ranks diverse captions by their expected CIDEr-D against the set
         self.last_token_ids = None   # per image of the last generation call its ranked token-id lists (what --eval_captions evaluates);
                                      # every generation method clears it first, so a call that fails leaves None, never older ids
         self.bound_stats = None      # bound_captions: skipped images and the running sums behind the active-units count
@@ -90,16 +91,20 @@ class Decoder(object):
         texts = [self._text(e[0], skip) for e in entries]
         rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts, "scores": [float(e[1]) for e in entries], "counts": counts}
         rec.update(extra)
-        if rerank in ("consensus", "marginal"):
+        if rerank in ("consensus", "marginal", "mbr"):
             rec[rerank] = [float(e[3]) for e in entries]
         return rec
 
     def _rerank(self):
-        """params.diverse_rerank: "likelihood", "consensus" (RuntimeError without an attached consensus index) or "marginal" """
+        """params.diverse_rerank: "likelihood", "consensus" (RuntimeError without an attached consensus index), "marginal" or "mbr"
+        (RuntimeError without an attached mbr.CiderGram)"""
         mode = getattr(self.params, "diverse_rerank", "likelihood")
         if mode == "consensus" and self.consensus_index is None:
             raise RuntimeError("diverse_rerank = 'consensus' needs a consensus index: attach one with decoder.consensus_index = "
                                "vae_captioning_amd.consensus.ConsensusIndex(engine, train_features, train_captions, bos, eos)")
+        if mode == "mbr" and self.mbr is None:
+            raise RuntimeError("diverse_rerank = 'mbr' needs the idf of the training captions: attach one with decoder.mbr = "
+                               "vae_captioning_amd.mbr.CiderGram(engine, train_captions_per_image, bos, eos)")
         return mode
 
     def decode(self, mode, picture_ids, in_pictures, c_v=None, sess=None, placeholder=None, **overrides):
@@ -151,19 +156,23 @@ class Decoder(object):
         `consensus_index` (consensus.py) before n_best cuts the list; the records gain "consensus" (aligned with "captions") and
         "caption" is the consensus winner.  params.diverse_rerank == "marginal": the distinct captions are ordered by their likelihood
         over ALL draws of the image (generate.py: diverse(rerank="marginal")); "scores" are those scores and the records gain "marginal"
-        (aligned with "captions")."""
+        (aligned with "captions").  params.diverse_rerank == "mbr": every distinct caption is re-ranked by its expected CIDEr-D against
+        the image's own captions, each weighted by its count (the attached `mbr`: mbr.CiderGram), before n_best cuts the list; the
+        records gain "mbr" (aligned with "captions") and "caption" is the minimum-Bayes-risk choice."""
         self.last_token_ids = None
         bos, eos, use_cv = self._call(c_v)
         draws = int(draws if draws is not None else self.params.diverse_draws)
         method = method if method is not None else self.params.diverse_method
         rerank = self._rerank()
-        consensus, marginal = rerank == "consensus", rerank == "marginal"
+        consensus, marginal, mbr = rerank == "consensus", rerank == "marginal", rerank == "mbr"
         feats = self._features(in_pictures)
-        res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus else n_best,
+        res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus or mbr else n_best,
                                   max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood",
                                   top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
         if consensus:
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
+        if mbr:
+            res = self.mbr.rerank(res, n_best=n_best)     # weights: the counts
         cap_list = [self._ranked_record(pid, entries, (bos, eos), [int(e[2]) for e in entries], rerank=rerank) for pid, entries in zip(picture_ids, res)]
         self.last_token_ids = [[list(e[0]) for e in entries] for entries in res]
         return cap_list
@@ -198,7 +207,8 @@ class Decoder(object):
         (1 + len)^len_norm_f descending): per image {"image_id", "caption", "captions", "scores", "counts" (all 1: the captions are
         distinct), "logprob", "perturbed", "weight", "norm_weight" (aligned with "captions"), "kappa"}.  params.diverse_rerank ==
         "consensus" re-ranks by the attached consensus index and adds "consensus"; "marginal" adds "marginal" (one latent draw per
-        image: the caption's logprob, so the order is the likelihood order)."""
+        image: the caption's logprob, so the order is the likelihood order); "mbr" re-ranks by the expected CIDEr-D against the image's
+        captions, each weighted by its norm_weight (the weights that estimate an expectation under the model), and adds "mbr"."""
         self.last_token_ids = None
         bos, eos, use_cv = self._call(c_v)
         n = int(beam_size if beam_size is not None else self.params.beam_size)
@@ -214,6 +224,8 @@ class Decoder(object):
         if consensus:
             ranked = self.consensus_index.rerank(feats, ranked)
         by_words = [{tuple(c[0]): c for c in r["captions"]} for r in res]
+        if rerank == "mbr":
+            ranked = self.mbr.rerank(ranked, weights=[[float(by[tuple(e[0])][5]) for e in entries] for entries, by in zip(ranked, by_words)])
         if marginal:
             ranked = [rerank_by_marginal(entries, [by[tuple(e[0])][1] for e in entries], eos, len_norm_f) for entries, by in zip(ranked, by_words)]
         cap_list = []
