@@ -49,6 +49,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the scheduled-sampling entry vc_sched_mix_f32.
  *      Added within 4 (additive, no layout change): the ROUGE-L entry vc_lcs_overlap.
  *      Added within 4 (additive, no layout change): the in-set CIDEr-D entry vc_cider_gram.
+ *      Added within 4 (additive, no layout change): the mutual-information entry vc_gauss_mix_lse_f64.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -834,6 +835,27 @@ int vc_gauss_kl_rows_f64(void* stream, long C, int S, int L, const float* mean, 
                          float prior_std, double* kl);
 int vc_bound_reduce_f64(void* stream, const float* lp, int T, int C, int K, const int32_t* len, const double* logw, double* logprob,
                         double* out);
+
+/* ------------------------------------------------------------------------------------
+ * Mutual information I(x; z) under the aggregated posterior (latent_mi.py: mutual_information; csrc/latent_mi.hip; DESIGN.md "Bounds",
+ * "Mutual information"): the draws of N captions scored under a table of M Gaussian posteriors.  z [N, S, L], mean and std_ [M, L], all
+ * f32; every operation is float64 on the f32 inputs converted to float64:
+ *   gauss_mix_lse   t[n, s, m]      = sum_l [ -0.5 ((z[n,s,l] - mean[m,l]) / std_[m,l])^2 - log std_[m,l] ] - 0.5 L log(2 pi)
+ *                   lse_block[n, s] = log sum_m exp(t[n, s, m])              [N, S]: one L-dimensional block under the mixture
+ *                   lse_full[n]     = log sum_m exp(sum_s t[n, s, m])        [N]: the S*L-dimensional code the decoder is given
+ *                   both max-subtracted: a table of sharp posteriors, whose far terms underflow, gives finite values.  The quotient is
+ *                   formed as (z - mean) * (1 / std_) with one IEEE division per table element; sum_l log std_ is summed apart from the
+ *                   squares.  std_ > 0 is the caller's to check (latent_mi.py does): the kernel does not.
+ *                   A workgroup owns 128 / S whole captions (64 / S for S < 8) with all their draws and streams the table past them in
+ *                   chunks of 64 posteriors by tiles of 32 dimensions (mean and 1 / std_ as float64 in LDS, ~129 KiB); a lane keeps the
+ *                   running (max, sum) pair of every row it owns for the posteriors lane, lane + 64, ... in ascending order, rescaled
+ *                   online; the 64 lanes' pairs are merged by xor shuffle trees.  sum_s runs in ascending s.  No atomics: two calls
+ *                   give identical bits, and a caption's outputs depend on its own z rows and the table only -- not on N, on its index
+ *                   or on the other captions.  No load runs past a row's end (any L >= 1).
+ *                   N == 0 is a successful no-op (no pointer is looked at).  N < 0, M, S or L < 1, S > 128 (the rows a workgroup keeps
+ *                   in registers), N or M >= 2^31, or a null pointer with N > 0 are VC_EINVAL, returned before any launch. */
+int vc_gauss_mix_lse_f64(void* stream, long N, long M, int S, int L, const float* z, const float* mean, const float* std_,
+                         double* lse_block, double* lse_full);
 
 /* ------------------------------------------------------------------------------------
  * Marginal decoding: search under the K-draw mixture p(y | I) ~ 1/K sum_k p(y | z_k, I) (generate.py: CaptionGenerator.marginal_greedy /

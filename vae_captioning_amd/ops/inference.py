@@ -29,7 +29,9 @@ caption's log-likelihood over the draws) and `"draws"`.
 "active_units", "latent_size"}, then per image {"image_id", "captions": [{"tokens", "elbo", "iwae", "rec", "kl", "ess"}]}; five printed
 lines: the perplexity bounds exp(-sum iwae / sum tokens) and exp(-sum elbo / sum tokens), the mean KL per caption, the mean effective
 sample size over K and the active latent units (Burda et al. 2016: dimensions whose posterior mean varies by more than 0.01 over the
-captions).
+captions).  `params.bound_mi = N >= 1` (additive, with `bound_draws`): the posteriors of the first N bounded captions
+(`decoder.bound_stats`) give the mutual information I(x; z) under the aggregated posterior (latent_mi.py: mutual_information, seeded by
+`params.seed`) once after the loop; the header gains {"mi", "mi_block", "mi_captions", "mi_ceiling"} and a sixth line is printed.
 `params.eval_captions` (additive): what was decoded for the validation images (`decoder.last_token_ids`: the whole ranked list of an
 image in the diverse modes, a list of one otherwise) is evaluated against ALL human captions of each image (taken from the generator's
 caption table by image id, `validation_references`: the batches carry one random caption per image) (`decoder.caption_evaluator`,
@@ -108,12 +110,26 @@ def bound_summary(bound_records, draws):
             sum(c["kl"] for c in caps) / len(caps), sum(c["ess"] for c in caps) / (len(caps) * draws))
 
 
+def mutual_information_of(params, stats):
+    """--bound_mi: the MI estimate of the posteriors bound_captions kept in stats ("mi_mean", "mi_std"), params.gen_z_samples draws
+    each, seeded by params.seed -> latent_mi.mutual_information's dict; None when the flag is off or no posterior was kept"""
+    if not int(getattr(params, "bound_mi", 0) or 0) or not stats.get("mi_mean"):
+        return None
+    from .. import latent_mi
+    return latent_mi.mutual_information(np.stack(stats["mi_mean"]), np.stack(stats["mi_std"]), int(params.gen_z_samples),
+                                        seed=int(getattr(params, "seed", 0)))
+
+
 def store_bounds(params, bound_records, stats):
-    """./val_{gen_name}_bound.json and the five printed lines; stats = decoder.bound_stats (None: nothing was bounded)"""
+    """./val_{gen_name}_bound.json and the five printed lines (six with --bound_mi); stats = decoder.bound_stats (None: nothing was
+    bounded)"""
     K, L = int(params.bound_draws), int(params.latent_size)
     stats = stats or {"skipped_images": 0, "captions": 0, "mu_sum": np.zeros(L), "mu_sq": np.zeros(L)}
     active = active_units(stats["mu_sum"], stats["mu_sq"], stats["captions"])
     header = {"draws": K, "skipped_images": int(stats["skipped_images"]), "active_units": active, "latent_size": L}
+    mi = mutual_information_of(params, stats)
+    if mi is not None:
+        header.update(mi=float(mi["mi"]), mi_block=float(mi["mi_block"]), mi_captions=int(mi["captions"]), mi_ceiling=float(mi["mi_ceiling"]))
     _store("./val_{}_bound.json".format(params.gen_name), [header] + list(bound_records))
     ppl_iwae, ppl_elbo, kl, ess = bound_summary(bound_records, K)
     print("Perplexity bound of the human captions from the importance-weighted bound, %d posterior draws: %.17g" % (K, ppl_iwae))
@@ -121,6 +137,9 @@ def store_bounds(params, bound_records, stats):
     print("Mean KL(q || p) per caption: %.6f nats" % kl)
     print("Mean effective sample size / draws: %.6f" % ess)
     print("Active latent units: %d of %d (%d images without a cluster vector skipped)" % (active, L, header["skipped_images"]))
+    if mi is not None:
+        print("Mutual information of caption and latent code: mi %.6f nats, mi_block %.6f nats per block (mi_ceiling %.6f = log of "
+              "mi_captions %d)" % (header["mi"], header["mi_block"], header["mi_ceiling"], header["mi_captions"]))
     return header
 
 

@@ -27,7 +27,7 @@ _DEFAULTS = dict(
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False, eval_self_cider=False,
-    bound_draws=0, marginal_draws=20, constraints=None, cbs_width=0,
+    bound_draws=0, bound_mi=0, marginal_draws=20, constraints=None, cbs_width=0,
     no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
     # training objective options (every one off by default: the reference's objective)
     kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
@@ -60,7 +60,7 @@ _FLAGS = [
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
     ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
     ("--eval_self_cider", "eval_self_cider", "flag", None),
-    ("--bound_draws", "bound_draws", int, None), ("--marginal_draws", "marginal_draws", int, None),
+    ("--bound_draws", "bound_draws", int, None), ("--bound_mi", "bound_mi", int, None), ("--marginal_draws", "marginal_draws", int, None),
     ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
     ("--no_repeat_ngram", "no_repeat_ngram", int, None), ("--min_len", "min_len", int, None),
     ("--repetition_penalty", "repetition_penalty", float, None), ("--banned_words", "banned_words", str, None),
@@ -108,6 +108,10 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--bound_draws": "--mode inference: also bound the likelihood of the validation images' human captions with this many posterior "
                           "draws per caption (ELBO, importance-weighted bound, KL, effective sample size, active latent units) and "
                           "write ./val_{gen_name}_bound.json (0..256; default 0 = off; not with --no_encoder)",
+         "--bound_mi": "--bound_draws: also estimate the mutual information I(x; z) between a caption and its latent code under the "
+                       "aggregated posterior, from the posteriors of the first this many bounded captions (every draw scored under "
+                       "every posterior: the work grows with its square), and add mi, mi_block, mi_captions and mi_ceiling to the "
+                       "header of ./val_{gen_name}_bound.json (0..65536; default 0 = off; gen_z_samples <= 128)",
          "--marginal_draws": "--sample_gen marginal_greedy / marginal_beam: latent draws per image whose mixture is searched (1..256; "
                              "default 20)",
          "--constraints": "--sample_gen constrained_beam: JSON file {image_id: [[word, ...], ...]} of the words the captions must mention "
@@ -197,6 +201,12 @@ class Parameters(object):
             ap.error("--bound_draws needs --mode inference (got --mode %s)" % self.mode)
         if self.bound_draws and self.no_encoder:
             ap.error("--bound_draws needs the encoder's posterior: not with --no_encoder")
+        if not 0 <= self.bound_mi <= 65536:
+            ap.error("--bound_mi must be 0..65536 (0 = off; got %d)" % self.bound_mi)
+        if self.bound_mi and not self.bound_draws:
+            ap.error("--bound_mi reads the posteriors that --bound_draws > 0 computes (--mode inference, not with --no_encoder)")
+        if self.bound_mi and not 1 <= self.gen_z_samples <= 128:
+            ap.error("--bound_mi scores at most 128 draws per caption (got --gen_z_samples %d)" % self.gen_z_samples)
         if self.sample_gen == "diverse_beam":
             if self.beam_groups < 1:
                 ap.error("--beam_groups must be >= 1 (got %d)" % self.beam_groups)

@@ -315,7 +315,10 @@ class Decoder(object):
         normalised cluster vector (encoder.py:72-75 draws it per training row), by a generator seeded from params.seed that lives as long
         as this decoder.  AG / GMM: an image with an empty cluster vector has no posterior; it is left out and counted in
         self.bound_stats["skipped_images"].  bound_stats also keeps running float64 sums of the posterior means and their squares per
-        latent dimension over every caption scored ("mu_sum", "mu_sq", "captions"): what ops.inference.active_units reads."""
+        latent dimension over every caption scored ("mu_sum", "mu_sq", "captions"): what ops.inference.active_units reads.  With
+        params.bound_mi = N > 0 it also keeps the posteriors (mean, std) of the first N captions scored ("mi_mean", "mi_std": lists of
+        float32 [L] rows; under the GMM prior the head of the component drawn here), which ops.inference.store_bounds hands to
+        latent_mi.mutual_information."""
         bos, eos, use_cv = self._call(c_v)
         p = self.params
         use_cv = np.asarray(use_cv, np.float32) if use_cv is not None else None
@@ -326,6 +329,8 @@ class Decoder(object):
             L = p.latent_size
             st = self.bound_stats = {"skipped_images": 0, "captions": 0, "mu_sum": np.zeros(L, np.float64), "mu_sq": np.zeros(L, np.float64),
                                      "rng": np.random.default_rng(p.seed)}
+            if int(getattr(p, "bound_mi", 0) or 0) > 0:
+                st.update(mi_mean=[], mi_std=[])
         keep = list(range(len(picture_ids)))
         if p.prior in ("AG", "GMM") and use_cv is not None:
             keep = [b for b in keep if use_cv[b].any()]
@@ -349,6 +354,9 @@ class Decoder(object):
                 st["mu_sum"] += mu
                 st["mu_sq"] += mu * mu
                 st["captions"] += 1
+                if "mi_mean" in st and len(st["mi_mean"]) < int(p.bound_mi):
+                    st["mi_mean"].append(r["mean"])
+                    st["mi_std"].append(r["std"])
             out.append({"image_id": picture_ids[b], "captions": [{k: (int(r[k]) if k == "tokens" else float(r[k]))
                                                                    for k in ("tokens", "elbo", "iwae", "rec", "kl", "ess")} for r in rs]})
         return out
