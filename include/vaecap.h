@@ -50,6 +50,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the ROUGE-L entry vc_lcs_overlap.
  *      Added within 4 (additive, no layout change): the in-set CIDEr-D entry vc_cider_gram.
  *      Added within 4 (additive, no layout change): the mutual-information entry vc_gauss_mix_lse_f64.
+ *      Added within 4 (additive, no layout change): the unlikelihood-training entries vc_softmax_xent_ul_f32, vc_ul_stats_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -276,6 +277,31 @@ int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const float* ce_d
 int vc_softmax_xent_policy_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
                                const float* adv, int N, float scale, float beta,
                                float* row_lp, float* row_ent, int write_grad);
+
+/* ------------------------------------------------------------------------------------
+ * Unlikelihood training (additive in ABI 4; csrc/loss.hip; DESIGN.md "Unlikelihood training"): vc_softmax_xent_smooth_f32 with the
+ * token-level repetition penalty of Welleck et al. (2020) in the same pass over the row.  Rows are time-major [T, N] (rows % N == 0,
+ * r = t * N + n, the layout of vc_softmax_xent_policy_f32); y = labels[r]; a row is live when 0 < y < V.
+ *   candidates  C_r = the distinct values of labels[t' * N + n], max(0, t - window) <= t' < t, without values <= 0, values >= V and y
+ *               itself; gathered by the kernel from `labels`.  t = 0 has none.
+ *   terms       p = softmax(x) over the V real columns; om_c = 1 - p_c; a candidate with om_c <= 1e-5 is clamped: it adds -log(1e-5) to
+ *               row_ul and nothing to the gradient (torch.clamp's autograd); otherwise r_c = p_c / om_c.  R = sum of r_c, unclamped c.
+ *   row_loss[r] = what vc_softmax_xent_smooth_f32 writes (cross-entropy alone, smoothed by eps; eps = 0: the plain loss)
+ *   row_ul[r]   = live * sum_c -log(max(om_c, 1e-5));  row_cand[r] = live * |C_r|;  row_mass[r] = live * sum_c p_c
+ *   write_grad  logits[r, v] <- k * (p_v - (1 - eps) [v == y] - eps / V + alpha * (r_v [v in C_r, unclamped] - p_v * R)) for v < V,
+ *               k = live * gscale / den[0], and exactly 0 for the pitch padding V <= v < ld; a row that is not live comes back all-zero.
+ *               write_grad = 0 leaves the logits untouched.
+ * Same dispatch rule as vc_softmax_xent_f32 (register kernel / generic kernel); per row at most 128 label reads, 128 scattered 4-byte
+ * reads and 128 scattered 4-byte writes on top of the smoothed entry's traffic.  VC_EINVAL before any launch: window outside 1..128,
+ * alpha not finite or <= 0, N < 1 or rows % N != 0, a null row_ul / row_cand / row_mass, and everything the smoothed entry rejects.
+ *   vc_ul_stats_f32: out3 = {sum row_ul, sum row_cand, sum row_mass} / #{r: 0 < labels[r] < V}, sums in fixed order (zeros when no row
+ *   is live): the unlikelihood loss per live row, the mean candidate count and the mean probability on already-said words.
+ * ---------------------------------------------------------------------------------- */
+int vc_softmax_xent_ul_f32(void* stream, float* logits, const int32_t* labels, long rows, int N, int V, long ld, const float* den,
+                           float gscale, float eps, float alpha, int window, float* row_loss, float* row_ul, int32_t* row_cand,
+                           float* row_mass, int write_grad);
+int vc_ul_stats_f32(void* stream, long rows, int V, const int32_t* labels, const float* row_ul, const int32_t* row_cand,
+                    const float* row_mass, float* out3);
 
 /* ------------------------------------------------------------------------------------
  * Scheduled sampling, parallel form (additive in ABI 4; csrc/sched.hip; DESIGN.md "Scheduled sampling"): the mix between the two

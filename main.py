@@ -255,6 +255,11 @@ def main(params):
                 o = tr.objective_stats()
                 say("Free bits: kl_raw: {} floored_share: {}".format(o["kl_raw"], o["floored_share"]))
 
+        def say_ul():   # --unlikelihood: the penalty before its weight, and the probability the model puts on words the caption has already said
+            if cap.unlikelihood > 0:
+                o = tr.objective_stats()
+                say("Unlikelihood: ul: {} candidates: {} repeat_mass: {}".format(o["ul"], o["ul_candidates"], o["repeat_mass"]))
+
         def say_sched():   # --sched_sampling: the rate of the last step and the share of its eligible words that were replaced (this rank's rows)
             o = tr.sched_stats()
             if o is not None:
@@ -299,6 +304,7 @@ def main(params):
                     if not params.no_encoder:
                         say("Annealing coefficient:{} KLD: {}".format(ann, kl))
                         say_objective()
+                    say_ul()
                     say_sched()
             if params.scst:
                 if tr.scst_stats is not None:
@@ -308,6 +314,7 @@ def main(params):
                 say("Epoch: {} Iteration: {} VLB: {} Rec Loss: {}".format(e, int(global_step.item()), lb, rl))
                 if not params.no_encoder:
                     say_objective()
+                say_ul()
                 say_sched()
             # validate(): rec_loss of the training graph on held-out batches (main.py:262-284)
             val = []

@@ -756,6 +756,214 @@ __global__ __launch_bounds__(256) void xent_policy_mem_kernel(float* __restrict_
     }
 }
 
+// =======================================================================================
+// Unlikelihood training (DESIGN.md "Unlikelihood training"; Welleck et al. 2020, token level): the smoothed cross-entropy of
+// xent_smooth_*_kernel plus alpha * sum_{c in C} -log(1 - p_c) over the row's candidate set C, the distinct words of the same caption's
+// up to `window` earlier labels (rows are time-major, r = t * N + n) that are words (0 < c < V) and not the row's own label y.
+//   om_c = 1 - p_c; a candidate with om_c <= 1e-5 is CLAMPED: it adds -log(1e-5) to row_ul and nothing to the gradient (torch.clamp);
+//   r_c = p_c / om_c otherwise, R = sum_c r_c.  live = 0 < y < V, k = live * gscale / den:
+//   row_loss = the smoothed kernel's (cross-entropy alone); row_ul = live * sum_c -log(max(om_c, 1e-5)); row_cand = live * |C|;
+//   row_mass = live * sum_c p_c;  d[v] = k * (p_v * (1 - alpha * R) - (1 - eps) [v == y] - eps / V + alpha * r_v [v in C, unclamped]).
+// How the hazards of doing this in place are handled, in both kernels:
+//   * thread i < min(window, t) owns the label i + 1 steps back.  It reads that label, and -- before anything else is waited for -- the
+//     logit x_c of it; thread 0 reads x_y likewise.  All of these loads stand in front of the block reductions, whose barriers every
+//     thread passes before the first store to the row: no x_c or x_y can see a gradient.
+//   * duplicates: the raw candidates go to LDS, and behind the barriers of the first reduction a thread drops its word when a thread
+//     with a smaller index holds the same one.  No compaction, no host-built table; t = 0 (and a PAD row) has no owner threads at all.
+//   * the row is scaled and stored as the smoothed kernel does it (p_v * (1 - alpha * R) in place of p_v; label column patched branch-free
+//     by the thread that stores it), padding columns and quads written as exact zeros by the threads that stored them.  The candidate
+//     columns are NOT patched inside those vector stores: behind one more workgroup barrier (the vector stores of other threads must be
+//     ordered before it) the owner thread stores its column's complete value, one float.  A candidate is never the label (excluded)
+//     and two owners never hold the same word (dedupe), so a candidate sharing its float4 with the label, with another candidate or
+//     with the pitch padding of the last quad (V % 4 != 0) is simply another 4-byte store to an address nobody else writes after the
+//     barrier; the padding stays the zeros its owner wrote (c < V).
+// Traffic: the smoothed kernel's 4 B read + 4 B written per logit, plus at most 128 label reads, 128 scattered 4-byte reads and 128
+// scattered 4-byte writes per row.
+// =======================================================================================
+constexpr int UL_MAXW = 128;
+#define VC_UL_CLAMP 1e-5f
+
+// sums of four per-thread values in ONE pass through LDS (block_sum of common.h four times with the barriers shared), fixed order
+__device__ __forceinline__ void block_sum4(float& a, float& b, float& c, float& d, float* sh /* 16 floats */) {
+    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); d = wave_sum(d);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh[w] = a; sh[4 + w] = b; sh[8 + w] = c; sh[12 + w] = d; }
+    __syncthreads();
+    a = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    b = ((sh[4] + sh[5]) + sh[6]) + sh[7];
+    c = ((sh[8] + sh[9]) + sh[10]) + sh[11];
+    d = ((sh[12] + sh[13]) + sh[14]) + sh[15];
+}
+
+// number of owner threads of row `row`: min(window, t), none for a row that is not live
+__device__ __forceinline__ int ul_owners(long row, int N, int window, bool live) {
+    const long t = row / N;
+    return live ? (int)(t < (long)window ? t : (long)window) : 0;
+}
+// thread i < owners: the label i + 1 steps back in the same caption, -1 unless it is a word other than y; left in cand[i] for ul_first
+__device__ __forceinline__ int ul_load(const int32_t* __restrict__ labels, long row, int N, int V, int owners, int y, int* cand /* UL_MAXW */) {
+    int c = -1;
+    if ((int)threadIdx.x < owners) {
+        c = labels[row - (long)(threadIdx.x + 1) * N];
+        if (c <= 0 || c >= V || c == y) c = -1;
+        cand[threadIdx.x] = c;
+    }
+    return c;
+}
+// (behind a barrier) keep the word only in the owner with the smallest index
+__device__ __forceinline__ int ul_first(int c, const int* cand) {
+    if (c >= 0)
+        for (int j = 0; j < (int)threadIdx.x; ++j)
+            if (cand[j] == c) { c = -1; break; }
+    return c;
+}
+// one candidate's terms from e_c = exp(x_c - max) and s = sum exp: -log(max(om, clamp)), p_c, r_c (0 when clamped)
+__device__ __forceinline__ void ul_terms(float ec, float s, float& ul, float& pc, float& rc) {
+    pc = ec / s;
+    const float om = 1.f - pc;
+    const bool clamped = om <= VC_UL_CLAMP;
+    ul = clamped ? -logf(VC_UL_CLAMP) : -log1pf(-pc);
+    rc = clamped ? 0.f : pc / om;
+}
+
+template <bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void xent_ul_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                          int V, long ld, const float* __restrict__ den, float gscale,
+                                                          float eps, int N, float alpha, int window, float* __restrict__ row_loss,
+                                                          float* __restrict__ row_ul, int32_t* __restrict__ row_cand,
+                                                          float* __restrict__ row_mass) {
+    __shared__ float sh[16];
+    __shared__ int cand[UL_MAXW];
+    const long row = blockIdx.x;
+    float* r = logits + row * ld;
+    float4* p = reinterpret_cast<float4*>(r);
+    const int V4 = (V + 3) >> 2;
+    const int label = labels[row];
+    const bool live = label > 0 && label < V;
+    float4 x[XENT_MAXQ];
+    // straight-line loads, as in xent_smooth_reg_kernel: a thread past the row's last quad re-reads that quad, its lanes are masked below
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
+    int c = ul_load(labels, row, N, V, ul_owners(row, N, window, live), label, cand);
+    const float xc = c >= 0 ? r[c] : 0.f;                            // (a duplicate reads its word's logit too: dropped below)
+    const float xy = (threadIdx.x == 0 && live) ? r[label] : 0.f;
+    float mx = -INFINITY, sx = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {
+        const int i = threadIdx.x + q * 256, cc = i * 4;
+        const bool v0 = cc < V, v1 = cc + 1 < V, v2 = cc + 2 < V, v3 = cc + 3 < V;
+        sx += ((v0 ? x[q].x : 0.f) + (v1 ? x[q].y : 0.f)) + ((v2 ? x[q].z : 0.f) + (v3 ? x[q].w : 0.f));
+        x[q].x = v0 ? x[q].x : -INFINITY; x[q].y = v1 ? x[q].y : -INFINITY;
+        x[q].z = v2 ? x[q].z : -INFINITY; x[q].w = v3 ? x[q].w : -INFINITY;
+        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
+    }
+    block_max_sum(mx, sx, sh);   // (its barriers stand between ul_load's cand[] writes and ul_first's reads)
+    c = ul_first(c, cand);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {
+        x[q].x = __expf(x[q].x - mx); x[q].y = __expf(x[q].y - mx);
+        x[q].z = __expf(x[q].z - mx); x[q].w = __expf(x[q].w - mx);
+        s += (x[q].x + x[q].y) + (x[q].z + x[q].w);
+    }
+    s = block_sum<256>(s, sh);
+    float ec = 0.f, ul = 0.f, mass = 0.f, rc = 0.f, R, cnt = 0.f;
+    if (c >= 0) {
+        ec = __expf(xc - mx);
+        ul_terms(ec, s, ul, mass, rc);
+        cnt = 1.f;
+    }
+    R = rc;
+    block_sum4(ul, mass, R, cnt, sh);   // every x_c and x_y has been read in front of these barriers: the stores below come behind them
+    const float ev = eps / (float)V;
+    if (threadIdx.x == 0) {
+        row_loss[row] = live ? __logf(s) + mx - (1.f - eps) * xy - ev * sx : 0.f;
+        row_ul[row] = ul;
+        row_cand[row] = (int32_t)cnt;
+        row_mass[row] = mass;
+    }
+    if (WRITE_GRAD) {
+        const float k = live ? gscale / den[0] : 0.f;
+        const float inv = k * (1.f - alpha * R) / s, ke = k * ev, kl = k * (1.f - eps);
+        const bool own = live && (int)threadIdx.x == ((label >> 2) & 255);
+        const int lq = own ? (label >> 10) : -1, lc = label & 3;
+        const float a0 = lc == 0 ? kl : 0.f, a1 = lc == 1 ? kl : 0.f, a2 = lc == 2 ? kl : 0.f, a3 = lc == 3 ? kl : 0.f;
+#pragma unroll
+        for (int q = 0; q < XENT_MAXQ; ++q) {
+            const int i = threadIdx.x + q * 256;
+            if (i < V4) {
+                const float m = q == lq ? 1.f : 0.f;
+                p[i] = make_float4((x[q].x * inv - ke) - m * a0, (x[q].y * inv - ke) - m * a1, (x[q].z * inv - ke) - m * a2, (x[q].w * inv - ke) - m * a3);
+            }
+        }
+        // the last quad's padding columns and the quads of the pitch past it: exactly 0 (written by the thread that stored that quad)
+        if ((int)threadIdx.x == ((V4 - 1) & 255))
+            for (int cc = V; cc < V4 * 4; ++cc) r[cc] = 0.f;
+        const int L4 = (int)(ld >> 2);
+        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
+        __syncthreads();   // the candidate columns were vector-stored by other threads: their owners write them behind this barrier
+        if (c >= 0) r[c] = (ec * inv - ke) + k * alpha * rc;
+    }
+}
+
+// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
+template <bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void xent_ul_mem_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                          int V, long ld, const float* __restrict__ den, float gscale,
+                                                          float eps, int N, float alpha, int window, float* __restrict__ row_loss,
+                                                          float* __restrict__ row_ul, int32_t* __restrict__ row_cand,
+                                                          float* __restrict__ row_mass) {
+    __shared__ float sh[16];
+    __shared__ int cand[UL_MAXW];
+    const long row = blockIdx.x;
+    float* p = logits + row * ld;
+    const int label = labels[row];
+    const bool live = label > 0 && label < V;
+    int c = ul_load(labels, row, N, V, ul_owners(row, N, window, live), label, cand);
+    const float xc = c >= 0 ? p[c] : 0.f;
+    const float xy = (threadIdx.x == 0 && live) ? p[label] : 0.f;
+    float mx = -INFINITY, sx = 0.f;
+    for (int cc = threadIdx.x; cc < V; cc += 256) {
+        const float v = p[cc];
+        mx = fmaxf(mx, v);
+        sx += v;
+    }
+    mx = block_max<256>(mx, sh);   // (its barriers stand between ul_load's cand[] writes and ul_first's reads)
+    sx = block_sum<256>(sx, sh);
+    c = ul_first(c, cand);
+    float s = 0.f;
+    for (int cc = threadIdx.x; cc < V; cc += 256) s += __expf(p[cc] - mx);
+    s = block_sum<256>(s, sh);
+    float ec = 0.f, ul = 0.f, mass = 0.f, rc = 0.f, R, cnt = 0.f;
+    if (c >= 0) {
+        ec = __expf(xc - mx);
+        ul_terms(ec, s, ul, mass, rc);
+        cnt = 1.f;
+    }
+    R = rc;
+    block_sum4(ul, mass, R, cnt, sh);   // every read of the row stands in front of these barriers, every store behind them
+    const float ev = eps / (float)V;
+    if (threadIdx.x == 0) {
+        row_loss[row] = live ? __logf(s) + mx - (1.f - eps) * xy - ev * sx : 0.f;
+        row_ul[row] = ul;
+        row_cand[row] = (int32_t)cnt;
+        row_mass[row] = mass;
+    }
+    if (WRITE_GRAD) {
+        const float k = live ? gscale / den[0] : 0.f;
+        const float inv = k * (1.f - alpha * R) / s, ke = k * ev, kl = k * (1.f - eps);
+        for (int cc = threadIdx.x; cc < V; cc += 256) {
+            float d = __expf(p[cc] - mx) * inv - ke;
+            if (cc == label) d -= kl;
+            p[cc] = d;
+        }
+        for (long cc = V + threadIdx.x; cc < ld; cc += 256) p[cc] = 0.f;
+        __syncthreads();   // the candidate columns were stored by other threads: their owners write them behind this barrier
+        if (c >= 0) p[c] =(ec * inv - ke) + k * alpha * rc;
+    }
+}
+
 }  // namespace vc
 
 using namespace vc;
@@ -950,6 +1158,64 @@ extern "C" int vc_softmax_xent_policy_f32(void* stream, float* logits, const int
         else { if (ent) VC_POLICY_LAUNCH((xent_policy_mem_kernel<false, true>)); else VC_POLICY_LAUNCH((xent_policy_mem_kernel<false, false>)); }
     }
 #undef VC_POLICY_LAUNCH
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- unlikelihood training: the smoothed cross-entropy with the repetition penalty in the same pass (dispatch rule: vc_softmax_xent_f32's)
+extern "C" int vc_softmax_xent_ul_f32(void* stream, float* logits, const int32_t* labels, long rows, int N, int V, long ld,
+                                      const float* den, float gscale, float eps, float alpha, int window, float* row_loss,
+                                      float* row_ul, int32_t* row_cand, float* row_mass, int write_grad) {
+    VC_CHECK_ARG(logits && labels && row_loss && rows >= 0 && V > 0 && ld >= V, "bad argument");
+    VC_CHECK_ARG(!write_grad || den, "den required for the gradient");
+    VC_CHECK_ARG(eps >= 0.f && eps < 1.f, "eps must be in [0, 1)");
+    VC_CHECK_ARG(row_ul && row_cand && row_mass, "row_ul, row_cand and row_mass required");
+    VC_CHECK_ARG(window >= 1 && window <= UL_MAXW, "window must be in 1..128");
+    VC_CHECK_ARG(alpha > 0.f && alpha < INFINITY, "alpha must be finite and > 0");
+    VC_CHECK_ARG(N > 0 && rows % N == 0, "rows must be a multiple of N (time-major [T, N] rows)");
+    if (rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
+    dim3 g((unsigned)rows), b(256);
+#define VC_UL_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, N, alpha, window, row_loss, row_ul, row_cand, row_mass)
+    if (reg) {
+        if (write_grad) VC_UL_LAUNCH(xent_ul_reg_kernel<true>); else VC_UL_LAUNCH(xent_ul_reg_kernel<false>);
+    } else {
+        if (write_grad) VC_UL_LAUNCH(xent_ul_mem_kernel<true>); else VC_UL_LAUNCH(xent_ul_mem_kernel<false>);
+    }
+#undef VC_UL_LAUNCH
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// What vc_softmax_xent_ul_f32 leaves per row, as three means over the live rows (0 < label < V) of the call, sums in fixed order:
+// out3 = {sum row_ul, sum row_cand, sum row_mass} / #live (zeros when no row is live).  One workgroup.
+namespace vc {
+__global__ __launch_bounds__(256) void ul_stats_kernel(const int32_t* __restrict__ labels, int V, const float* __restrict__ row_ul,
+                                                       const int32_t* __restrict__ row_cand, const float* __restrict__ row_mass,
+                                                       long rows, float* __restrict__ out) {
+    __shared__ float sh[16];
+    float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
+    for (long i = threadIdx.x; i < rows; i += 256) {
+        a += row_ul[i];
+        b += (float)row_cand[i];
+        c += row_mass[i];
+        d += (labels[i] > 0 && labels[i] < V) ? 1.f : 0.f;
+    }
+    block_sum4(a, b, c, d, sh);
+    if (threadIdx.x == 0) {
+        const float inv = d > 0.f ? 1.f / d : 0.f;
+        out[0] = a * inv;
+        out[1] = b * inv;
+        out[2] = c * inv;
+    }
+}
+}  // namespace vc
+
+extern "C" int vc_ul_stats_f32(void* stream, long rows, int V, const int32_t* labels, const float* row_ul, const int32_t* row_cand,
+                               const float* row_mass, float* out3) {
+    VC_CHECK_ARG(labels && row_ul && row_cand && row_mass && out3 && rows > 0 && V > 0, "bad argument");
+    hipLaunchKernelGGL(ul_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, labels, V, row_ul, row_cand, row_mass, rows, out3);
     VC_LAUNCH_CHECK();
     return 0;
 }

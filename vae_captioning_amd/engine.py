@@ -235,6 +235,16 @@ class CaptionEngine(object):
         if self.kl_cycle[0] > 0:
             self.ann_on = 0   # the cyclical schedule owns the coefficient (also under --restore / --fine_tune: Q10 is about the tanh one)
         self.ostat = torch.zeros(2, **f32) if self.free_bits > 0 else None   # vc_objective_stats_f32: mean unclamped KL, floored share
+        # Unlikelihood training (DESIGN.md "Unlikelihood training"): alpha > 0 = a TRAINING fw_loss launches vc_softmax_xent_ul_f32 in place
+        # of the plain / smoothed entry (label_smoothing is its eps); 0 = off: nothing of it is resolved or launched.  The window bounds
+        # the look-back only: a caption longer than window + 1 words is no error, its late rows see their last `window` labels.
+        self.unlikelihood = float(getattr(p, "unlikelihood", 0.0))
+        self.ul_window = int(getattr(p, "ul_window", 128))
+        if not (0.0 <= self.unlikelihood < float("inf")):
+            raise ValueError("unlikelihood weight must be finite and >= 0 (0 = off; got %r)" % (self.unlikelihood,))
+        if self.unlikelihood > 0 and not 1 <= self.ul_window <= 128:
+            raise ValueError("unlikelihood window must be 1..128 (got %r)" % (self.ul_window,))
+        self.ustat = torch.zeros(3, **f32) if self.unlikelihood > 0 else None   # vc_ul_stats_f32: ul, candidates, repeat mass per live row
         # Self-critical training (DESIGN.md "Self-critical training"): True while a policy step prepares its forward -- z is GIVEN (no eps,
         # no GMM draw); everything else off = the training step as it was
         self.policy = False
@@ -878,7 +888,14 @@ class CaptionEngine(object):
         Ng = N * self.world
         gscale = dp.scales(N, self.world, vector_loss)[0]
         row_loss = self._b("row_loss", (T * N,))
-        if train and self.label_smoothing > 0:  # (validation, train=False, keeps the plain loss: comparable between runs)
+        if train and self.unlikelihood > 0 and not self.policy:  # the smoothed cross-entropy (eps may be 0) with the repetition penalty in the same pass
+            R = T * N
+            rul, rcd, rms = self._b("row_ul", (R,)), self._b("row_cand", (R,), torch.int32), self._b("row_mass", (R,))
+            self._timed("hbm_softmax_xent", 8.0 * T * N * V,
+                        lambda: lib.vc_softmax_xent_ul_f32(st, P(logits), P(labels), R, N, V, _round(V, 4), P(den), gscale, self.label_smoothing,
+                                                           self.unlikelihood, self.ul_window, P(row_loss), P(rul), P(rcd), P(rms), 1))
+            lib.vc_ul_stats_f32(st, R, V, P(labels), P(rul), P(rcd), P(rms), P(self.ustat))
+        elif train and self.label_smoothing > 0:  # (validation, train=False, keeps the plain loss: comparable between runs)
             self._timed("hbm_softmax_xent", 8.0 * T * N * V,
                         lambda: lib.vc_softmax_xent_smooth_f32(st, P(logits), P(labels), T * N, V, _round(V, 4), P(den), gscale, self.label_smoothing, P(row_loss), 1))
         else:
@@ -1245,12 +1262,21 @@ class CaptionEngine(object):
         return float(o[1]), float(o[0]), float(o[2]), float(o[3])
 
     def objective_stats(self):
-        """Free bits (--kl_free_bits > 0): {"kl_raw": mean unclamped KL per caption row, "floored_share": share of the N * L latent
-        dimensions held at the floor} of the last forward pass over this rank's rows; None when free bits are off."""
-        if self.ostat is None:
+        """What the objective options report about the last forward pass over this rank's rows; None when none of them is on.
+        Free bits (--kl_free_bits > 0): {"kl_raw": mean unclamped KL per caption row, "floored_share": share of the N * L latent
+        dimensions held at the floor}.  Unlikelihood training (--unlikelihood > 0): {"ul": the unlikelihood loss per live row (before
+        its weight), "ul_candidates": mean number of candidate words per live row, "repeat_mass": mean probability per live row on
+        the words the caption has already said} of the last TRAINING forward."""
+        if self.ostat is None and self.ustat is None:
             return None
-        o = self.ostat.detach().cpu().numpy()
-        return {"kl_raw": float(o[0]), "floored_share": float(o[1])}
+        d = {}
+        if self.ostat is not None:
+            o = self.ostat.detach().cpu().numpy()
+            d.update({"kl_raw": float(o[0]), "floored_share": float(o[1])})
+        if self.ustat is not None:
+            u = self.ustat.detach().cpu().numpy()
+            d.update({"ul": float(u[0]), "ul_candidates": float(u[1]), "repeat_mass": float(u[2])})
+        return d
 
     def sched_stats(self):
         """Scheduled sampling (--sched_sampling > 0): {"rate": the sampling rate the last training forward used, "eligible": this rank's

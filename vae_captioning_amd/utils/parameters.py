@@ -35,6 +35,8 @@ _DEFAULTS = dict(
     scst=False, scst_baseline="average", scst_entropy=0.0, scst_rouge=0.0,
     # scheduled sampling in the cross-entropy phase (off by default)
     sched_sampling=0.0, sched_schedule="linear", sched_ramp_steps=10000, sched_pick="sample", sched_temperature=1.0,
+    # unlikelihood training (off by default)
+    unlikelihood=0.0, ul_window=128,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -73,6 +75,7 @@ _FLAGS = [
     ("--sched_sampling", "sched_sampling", float, None), ("--sched_schedule", "sched_schedule", str, ["constant", "linear", "sigmoid"]),
     ("--sched_ramp_steps", "sched_ramp_steps", int, None), ("--sched_pick", "sched_pick", str, ["sample", "argmax"]),
     ("--sched_temperature", "sched_temperature", float, None),
+    ("--unlikelihood", "unlikelihood", float, None), ("--ul_window", "ul_window", int, None),
 ]
 _KL_FLAGS = ("kl_free_bits", "kl_weight", "kl_cycle_steps", "kl_cycle_ramp", "kl_cycles")
 _SCHED_FLAGS = ("sched_schedule", "sched_ramp_steps", "sched_pick", "sched_temperature")
@@ -154,6 +157,11 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--sched_pick": "--sched_sampling: the model's word is a draw from its prediction (sample) or its most likely word (argmax; "
                          "default sample)",
          "--sched_temperature": "--sched_sampling --sched_pick sample: temperature of the draw (> 0; default 1.0)",
+         "--unlikelihood": "training objective: weight alpha of the token-level unlikelihood term, which at every caption position adds "
+                           "-alpha * sum_c log(1 - p(c)) over the words c the target caption has already said (finite, >= 0; default "
+                           "0 = off; validation losses and the reported rec_loss stay the cross-entropy; not with --scst)",
+         "--ul_window": "--unlikelihood: how many earlier positions of the caption supply those words (1..128; default 128; a longer "
+                        "caption is no error, the window bounds the look-back)",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
@@ -302,6 +310,14 @@ class Parameters(object):
                 ap.error("--sched_sampling mixes the inputs of the cross-entropy step, which --scst does not take")
             if self.mode != "training":
                 ap.error("--sched_sampling is a way of training: not with --mode %s" % self.mode)
+        if not (0.0 <= self.unlikelihood < float("inf")):
+            ap.error("--unlikelihood must be finite and >= 0 (0 = off; got %r)" % self.unlikelihood)
+        if not 1 <= self.ul_window <= 128:
+            ap.error("--ul_window must be 1..128 (got %d)" % self.ul_window)
+        if not self.unlikelihood > 0 and args["ul_window"] is not None:
+            ap.error("--ul_window belongs to --unlikelihood > 0")
+        if self.unlikelihood > 0 and self.scst:
+            ap.error("--unlikelihood shapes the cross-entropy objective, which --scst does not optimise")
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.eval_self_cider and not self.eval_captions:
