@@ -51,6 +51,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the in-set CIDEr-D entry vc_cider_gram.
  *      Added within 4 (additive, no layout change): the mutual-information entry vc_gauss_mix_lse_f64.
  *      Added within 4 (additive, no layout change): the unlikelihood-training entries vc_softmax_xent_ul_f32, vc_ul_stats_f32.
+ *      Added within 4 (additive, no layout change): the bag-of-words loss entries vc_bow_xent_f32, vc_bow_stats_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -302,6 +303,30 @@ int vc_softmax_xent_ul_f32(void* stream, float* logits, const int32_t* labels, l
                            float* row_mass, int write_grad);
 int vc_ul_stats_f32(void* stream, long rows, int V, const int32_t* labels, const float* row_ul, const int32_t* row_cand,
                     const float* row_mass, float* out3);
+
+/* ------------------------------------------------------------------------------------
+ * Bag-of-words auxiliary loss (additive in ABI 4; csrc/loss.hip; DESIGN.md "Bag-of-words loss"; Zhao, Zhao & Eskenazi 2017): the
+ * multi-label member of the logits-row family.  One row of logits per CAPTION (rows = N, pitch ld), one workgroup per row; labels is the
+ * step's time-major [T, N] label buffer, ldl the stride between positions (N in the engine): position t of caption n is
+ * labels[t * ldl + n].
+ *   bag         of row n = the multiset { labels[t * ldl + n] : 0 <= t < T, 0 < label < V } (PAD and out-of-range ids are not in it);
+ *               m = its size with multiplicity, c_w = the count of word w in it; p = softmax(x) over the V real columns
+ *   row_loss[n] = m * lse(x) - sum_w c_w x_w       (= -sum over the bag of log p_w)
+ *   row_mass[n] = sum over the DISTINCT bag words of p_w;  row_words[n] = the number of distinct bag words
+ *   write_grad  logits[n, v] <- k * (m * p_v - c_v) for v < V, k = gscale / den[0], and exactly 0 for the pitch padding V <= v < ld;
+ *               a row with m = 0 has loss 0, mass 0, words 0 and comes back all-zero.  write_grad = 0 leaves the logits untouched.
+ * Same dispatch rule as vc_softmax_xent_f32 (register kernel / generic kernel); per row at most T label reads, T scattered 4-byte reads
+ * and T scattered 4-byte writes on top of one read and one write of the row.  VC_EINVAL before any launch: T outside 1..256 (one
+ * position per thread), ldl < rows, V < 1, ld < V, rows < 0, a null logits / labels / row_loss / row_mass / row_words, a null den with
+ * write_grad.  rows = 0 is a successful no-op.
+ *   vc_bow_stats_f32: out3 = {sum row_loss / sum m, sum row_words / #non-empty rows, sum row_mass / #non-empty rows} (zeros when every
+ *   bag is empty), sums in fixed order, m counted from the labels as above: nats per bag word, mean distinct words and mean probability
+ *   on the bag per non-empty caption.  One workgroup.
+ * ---------------------------------------------------------------------------------- */
+int vc_bow_xent_f32(void* stream, float* logits, long rows, int V, long ld, const int32_t* labels, int T, long ldl, const float* den,
+                    float gscale, float* row_loss, float* row_mass, int32_t* row_words, int write_grad);
+int vc_bow_stats_f32(void* stream, long rows, int V, const int32_t* labels, int T, long ldl, const float* row_loss,
+                     const float* row_mass, const int32_t* row_words, float* out3);
 
 /* ------------------------------------------------------------------------------------
  * Scheduled sampling, parallel form (additive in ABI 4; csrc/sched.hip; DESIGN.md "Scheduled sampling"): the mix between the two

@@ -260,6 +260,11 @@ def main(params):
                 o = tr.objective_stats()
                 say("Unlikelihood: ul: {} candidates: {} repeat_mass: {}".format(o["ul"], o["ul_candidates"], o["repeat_mass"]))
 
+        def say_bow():   # --bow_loss: the z-only head's loss per bag word, the distinct words per caption and the probability it puts on them
+            if cap.bow_loss > 0:
+                o = tr.objective_stats()
+                say("BoW: bow: {} words: {} mass: {}".format(o["bow"], o["bow_words"], o["bow_mass"]))
+
         def say_sched():   # --sched_sampling: the rate of the last step and the share of its eligible words that were replaced (this rank's rows)
             o = tr.sched_stats()
             if o is not None:
@@ -305,6 +310,7 @@ def main(params):
                         say("Annealing coefficient:{} KLD: {}".format(ann, kl))
                         say_objective()
                     say_ul()
+                    say_bow()
                     say_sched()
             if params.scst:
                 if tr.scst_stats is not None:
@@ -315,6 +321,7 @@ def main(params):
                 if not params.no_encoder:
                     say_objective()
                 say_ul()
+                say_bow()
                 say_sched()
             # validate(): rec_loss of the training graph on held-out batches (main.py:262-284)
             val = []

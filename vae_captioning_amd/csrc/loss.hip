@@ -964,6 +964,167 @@ __global__ __launch_bounds__(256) void xent_ul_mem_kernel(float* __restrict__ lo
     }
 }
 
+// =======================================================================================
+// Bag-of-words auxiliary loss (DESIGN.md "Bag-of-words loss"; Zhao, Zhao & Eskenazi 2017): the multi-label member of the family.  One
+// row of logits per CAPTION n; its targets are the bag of the caption's words, read from the step's time-major labels
+// (labels[t * ldl + n], 0 <= t < T <= 256), PAD and ids outside (0, V) left out.  m = the bag's size with multiplicity, c_w = the count
+// of word w, p = softmax over the V real columns, k = gscale / den:
+//   row_loss = m * lse(x) - sum_w c_w x_w;  row_mass = sum over the DISTINCT bag words of p_w;  row_words = their number;
+//   d[v] = k * (m * p_v - c_v) for v < V, exactly 0 in the pitch padding; a row with m = 0 comes back all-zero.
+// In place, with the means of xent_ul_*_kernel:
+//   * thread i < T owns position i.  It reads its word and that word's logit x_w in front of the first block reduction, whose barriers
+//     every thread passes before the first store to the row: no x_w can see a gradient.  The words go to LDS.
+//   * behind those barriers an owner KEEPS its word only if no lower-indexed owner holds it (bow_keep); the keeper counts the word's
+//     multiplicity over the owners behind it.  Two keepers never hold the same word.
+//   * the vector stores write k * m * p_v everywhere; behind one more workgroup barrier each keeper stores its column's complete value
+//     k * (m * p_w - c_w) as one float.  A bag word that shares its float4 with another bag word, or with the last quad's padding
+//     (V % 4 != 0), is still a single writer behind that barrier; the padding stays the zeros the vector store wrote (w < V).
+// Traffic: 4 B read + 4 B written per logit, plus at most T label reads, T scattered 4-byte reads and T scattered 4-byte writes a row.
+// =======================================================================================
+constexpr int BOW_MAXT = 256;
+
+// thread i: the word at position i of caption `row`, -1 unless 0 < word < V (and for i >= T); left in bag[i] for bow_keep
+__device__ __forceinline__ int bow_load(const int32_t* __restrict__ labels, long row, int T, long ldl, int V, int* bag /* BOW_MAXT */) {
+    int w = -1;
+    if ((int)threadIdx.x < T) {
+        w = labels[(long)threadIdx.x * ldl + row];
+        if (w <= 0 || w >= V) w = -1;
+    }
+    bag[threadIdx.x] = w;
+    return w;
+}
+// (behind a barrier) the multiplicity c_w of the thread's word if it is the word's first owner, 0 otherwise (and for w < 0)
+__device__ __forceinline__ int bow_keep(int w, int T, const int* bag) {
+    if (w < 0) return 0;
+    for (int j = 0; j < (int)threadIdx.x; ++j)
+        if (bag[j] == w) return 0;
+    int cnt = 1;
+    for (int j = threadIdx.x + 1; j < T; ++j) cnt += bag[j] == w ? 1 : 0;
+    return cnt;
+}
+
+template <bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void bow_xent_reg_kernel(float* __restrict__ logits, int V, long ld, const int32_t* __restrict__ labels,
+                                                           int T, long ldl, const float* __restrict__ den, float gscale,
+                                                           float* __restrict__ row_loss, float* __restrict__ row_mass,
+                                                           int32_t* __restrict__ row_words) {
+    __shared__ float sh[16];
+    __shared__ int bag[BOW_MAXT];
+    const long row = blockIdx.x;
+    float* r = logits + row * ld;
+    float4* p = reinterpret_cast<float4*>(r);
+    const int V4 = (V + 3) >> 2;
+    float4 x[XENT_MAXQ];
+    // straight-line loads, as in xent_smooth_reg_kernel: a thread past the row's last quad re-reads that quad, its lanes are masked below
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
+    const int w = bow_load(labels, row, T, ldl, V, bag);
+    const float xw = w >= 0 ? r[w] : 0.f;                            // (a duplicate reads its word's logit too: dropped below)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {
+        const int i = threadIdx.x + q * 256, cc = i * 4;
+        x[q].x = cc < V ? x[q].x : -INFINITY; x[q].y = cc + 1 < V ? x[q].y : -INFINITY;
+        x[q].z = cc + 2 < V ? x[q].z : -INFINITY; x[q].w = cc + 3 < V ? x[q].w : -INFINITY;
+        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
+    }
+    mx = block_max<256>(mx, sh);   // (its barriers stand between bow_load's bag[] writes and bow_keep's reads)
+    const int cw = bow_keep(w, T, bag);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_MAXQ; ++q) {   // (exp(-inf) = 0: the masked lanes add nothing)
+        x[q].x = __expf(x[q].x - mx); x[q].y = __expf(x[q].y - mx);
+        x[q].z = __expf(x[q].z - mx); x[q].w = __expf(x[q].w - mx);
+        s += (x[q].x + x[q].y) + (x[q].z + x[q].w);
+    }
+    s = block_sum<256>(s, sh);
+    const float ec = cw > 0 ? __expf(xw - mx) : 0.f;
+    float m = w >= 0 ? 1.f : 0.f, cx = (float)cw * (xw - mx), mass = ec / s, words = cw > 0 ? 1.f : 0.f;
+    block_sum4(m, cx, mass, words, sh);   // every x_w has been read in front of these barriers: the stores below come behind them
+    if (threadIdx.x == 0) {
+        row_loss[row] = m > 0.f ? m * __logf(s) - cx : 0.f;
+        row_mass[row] = mass;
+        row_words[row] = (int32_t)words;
+    }
+    if (WRITE_GRAD) {
+        const float k = m > 0.f ? gscale / den[0] : 0.f;
+        const float inv = k * m / s;
+#pragma unroll
+        for (int q = 0; q < XENT_MAXQ; ++q) {
+            const int i = threadIdx.x + q * 256;
+            if (i < V4) p[i] = make_float4(x[q].x * inv, x[q].y * inv, x[q].z * inv, x[q].w * inv);   // (masked lanes: 0 * inv = the padding's 0)
+        }
+        const int L4 = (int)(ld >> 2);
+        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
+        __syncthreads();   // the bag columns were vector-stored by other threads: their keepers write them behind this barrier
+        if (cw > 0) r[w] = ec * inv - k * (float)cw;
+    }
+}
+
+// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
+template <bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void bow_xent_mem_kernel(float* __restrict__ logits, int V, long ld, const int32_t* __restrict__ labels,
+                                                           int T, long ldl, const float* __restrict__ den, float gscale,
+                                                           float* __restrict__ row_loss, float* __restrict__ row_mass,
+                                                           int32_t* __restrict__ row_words) {
+    __shared__ float sh[16];
+    __shared__ int bag[BOW_MAXT];
+    const long row = blockIdx.x;
+    float* p = logits + row * ld;
+    const int w = bow_load(labels, row, T, ldl, V, bag);
+    const float xw = w >= 0 ? p[w] : 0.f;
+    float mx = -INFINITY;
+    for (int cc = threadIdx.x; cc < V; cc += 256) mx = fmaxf(mx, p[cc]);
+    mx = block_max<256>(mx, sh);   // (its barriers stand between bow_load's bag[] writes and bow_keep's reads)
+    const int cw = bow_keep(w, T, bag);
+    float s = 0.f;
+    for (int cc = threadIdx.x; cc < V; cc += 256) s += __expf(p[cc] - mx);
+    s = block_sum<256>(s, sh);
+    const float ec = cw > 0 ? __expf(xw - mx) : 0.f;
+    float m = w >= 0 ? 1.f : 0.f, cx = (float)cw * (xw - mx), mass = ec / s, words = cw > 0 ? 1.f : 0.f;
+    block_sum4(m, cx, mass, words, sh);   // every read of the row stands in front of these barriers, every store behind them
+    if (threadIdx.x == 0) {
+        row_loss[row] = m > 0.f ? m * __logf(s) - cx : 0.f;
+        row_mass[row] = mass;
+        row_words[row] = (int32_t)words;
+    }
+    if (WRITE_GRAD) {
+        const float k = m > 0.f ? gscale / den[0] : 0.f;
+        const float inv = k * m / s;
+        for (int cc = threadIdx.x; cc < V; cc += 256) p[cc] = __expf(p[cc] - mx) * inv;
+        for (long cc = V + threadIdx.x; cc < ld; cc += 256) p[cc] = 0.f;
+        __syncthreads();   // the bag columns were stored by other threads: their keepers write them behind this barrier
+        if (cw > 0) p[w] = ec * inv - k * (float)cw;
+    }
+}
+
+// What vc_bow_xent_f32 leaves per row, as the three reported numbers of this call's rows, sums in fixed order: out3 = {sum row_loss /
+// sum m, sum row_words / #non-empty, sum row_mass / #non-empty}, m counted from the labels (zeros when every bag is empty).  One workgroup.
+__global__ __launch_bounds__(256) void bow_stats_kernel(const int32_t* __restrict__ labels, int T, long ldl, int V, const float* __restrict__ row_loss,
+                                                        const float* __restrict__ row_mass, const int32_t* __restrict__ row_words,
+                                                        long rows, float* __restrict__ out) {
+    __shared__ float sh[16];
+    float a = 0.f, b = 0.f, c = 0.f, d = 0.f, m = 0.f;
+    for (long i = threadIdx.x; i < rows; i += 256) {
+        a += row_loss[i];
+        b += (float)row_words[i];
+        c += row_mass[i];
+        d += row_words[i] > 0 ? 1.f : 0.f;
+        for (int t = 0; t < T; ++t) {
+            const int w = labels[(long)t * ldl + i];
+            m += (w > 0 && w < V) ? 1.f : 0.f;
+        }
+    }
+    block_sum4(a, b, c, d, sh);
+    m = block_sum<256>(m, sh);
+    if (threadIdx.x == 0) {
+        const float inv = d > 0.f ? 1.f / d : 0.f;
+        out[0] = m > 0.f ? a / m : 0.f;
+        out[1] = b * inv;
+        out[2] = c * inv;
+    }
+}
+
 }  // namespace vc
 
 using namespace vc;
@@ -1216,6 +1377,37 @@ extern "C" int vc_ul_stats_f32(void* stream, long rows, int V, const int32_t* la
                                const float* row_mass, float* out3) {
     VC_CHECK_ARG(labels && row_ul && row_cand && row_mass && out3 && rows > 0 && V > 0, "bad argument");
     hipLaunchKernelGGL(ul_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, labels, V, row_ul, row_cand, row_mass, rows, out3);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- bag-of-words auxiliary loss: one row of logits per caption against the bag of its words (dispatch rule: vc_softmax_xent_f32's)
+extern "C" int vc_bow_xent_f32(void* stream, float* logits, long rows, int V, long ld, const int32_t* labels, int T, long ldl,
+                               const float* den, float gscale, float* row_loss, float* row_mass, int32_t* row_words, int write_grad) {
+    VC_CHECK_ARG(logits && labels && row_loss && row_mass && row_words, "null pointer");
+    VC_CHECK_ARG(rows >= 0 && V > 0 && ld >= V, "bad argument");
+    VC_CHECK_ARG(T >= 1 && T <= BOW_MAXT, "T must be in 1..256 (one caption position per thread)");
+    VC_CHECK_ARG(ldl >= rows, "ldl must be >= rows (labels are time-major [T, ldl])");
+    VC_CHECK_ARG(!write_grad || den, "den required for the gradient");
+    if (rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
+    dim3 g((unsigned)rows), b(256);
+#define VC_BOW_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, st, logits, V, ld, labels, T, ldl, den, gscale, row_loss, row_mass, row_words)
+    if (reg) {
+        if (write_grad) VC_BOW_LAUNCH(bow_xent_reg_kernel<true>); else VC_BOW_LAUNCH(bow_xent_reg_kernel<false>);
+    } else {
+        if (write_grad) VC_BOW_LAUNCH(bow_xent_mem_kernel<true>); else VC_BOW_LAUNCH(bow_xent_mem_kernel<false>);
+    }
+#undef VC_BOW_LAUNCH
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_bow_stats_f32(void* stream, long rows, int V, const int32_t* labels, int T, long ldl, const float* row_loss,
+                                const float* row_mass, const int32_t* row_words, float* out3) {
+    VC_CHECK_ARG(labels && row_loss && row_mass && row_words && out3 && rows > 0 && V > 0 && T >= 1 && ldl >= rows, "bad argument");
+    hipLaunchKernelGGL(bow_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, labels, T, ldl, V, row_loss, row_mass, row_words, rows, out3);
     VC_LAUNCH_CHECK();
     return 0;
 }

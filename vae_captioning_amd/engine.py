@@ -148,7 +148,9 @@ def internal_caption_variables(p, vocab):
     # the logits layer is stored with its vocabulary dimension padded to a multiple of 4 (zero columns): its three GEMMs keep
     # 16-byte operand loads for vocabularies such as the reference's observed 11313 (checkpoints carry the unpadded arrays)
     Vp = _round(int(vocab), 4)
-    fused = [(n, (sh[0], Vp)) if n == "decoder/rnn_logits/kernel" else ((n, (Vp,)) if n == "decoder/rnn_logits/bias" else (n, sh)) for n, sh in fused]
+    # (the bag-of-words head, where it exists, has the same vocabulary dimension and the same padding)
+    fused = [(n, (sh[0], Vp)) if n in ("decoder/rnn_logits/kernel", spec.BOW_KERNEL) else ((n, (Vp,)) if n in ("decoder/rnn_logits/bias", spec.BOW_BIAS) else (n, sh))
+             for n, sh in fused]
     emb = [e for e in fused if e[0].endswith("embeddings")]
     rest = [e for e in fused if not e[0].endswith("embeddings")]
     return rest + emb
@@ -245,6 +247,21 @@ class CaptionEngine(object):
         if self.unlikelihood > 0 and not 1 <= self.ul_window <= 128:
             raise ValueError("unlikelihood window must be 1..128 (got %r)" % (self.ul_window,))
         self.ustat = torch.zeros(3, **f32) if self.unlikelihood > 0 else None   # vc_ul_stats_f32: ul, candidates, repeat mass per live row
+        # Bag-of-words auxiliary loss (DESIGN.md "Bag-of-words loss"): A > 0 (and an encoder) = a TRAINING forward runs fw_bow behind its
+        # first fw_decode -- a head on the decoder's z step Xd[zi] that must predict the caption's words -- and backward adds the head's
+        # input gradient to dXd[zi]; 0 = off: the two variables do not exist and nothing of it is resolved or launched.
+        self.bow_loss = float(getattr(p, "bow_loss", 0.0))
+        if not (0.0 <= self.bow_loss < float("inf")):
+            raise ValueError("bag-of-words loss weight must be finite and >= 0 (0 = off; got %r)" % (self.bow_loss,))
+        if not spec.uses_bow(p):
+            self.bow_loss = 0.0
+        self.bstat = torch.zeros(3, **f32) if self.bow_loss > 0 else None   # vc_bow_stats_f32: nats per bag word, distinct words, mass on the bag
+        if self.bow_loss > 0:
+            # the head's own fresh initialisation (glorot kernel, zero bias, seeded): what load_params keeps when a checkpoint from
+            # before the head lacks bow/*
+            k0 = spec._glorot(np.random.default_rng([int(seed), 0xB0]), (p.embed_size, self.V))
+            self.store.param(spec.BOW_KERNEL)[:, :self.V].copy_(torch.from_numpy(k0))
+        self._den_early = False               # the label count of this forward is already in red[1] (fw_bow needs it in front of fw_loss)
         # Self-critical training (DESIGN.md "Self-critical training"): True while a policy step prepares its forward -- z is GIVEN (no eps,
         # no GMM draw); everything else off = the training step as it was
         self.policy = False
@@ -302,6 +319,11 @@ class CaptionEngine(object):
         p = self.p
         need = [n for n, _ in spec.caption_variables(p, self.V)]
         missing = [n for n in need if n not in named]
+        # the bag-of-words head is the one thing added to an EXISTING run: a checkpoint from before it keeps the head as it stands
+        keep = [n for n in missing if n in (spec.BOW_KERNEL, spec.BOW_BIAS)]
+        missing = [n for n in missing if n not in keep]
+        if keep and not missing:
+            print("checkpoint has no %s: the bag-of-words head keeps its fresh initialisation" % " / ".join(keep))
         if missing:  # tf.train.Saver.restore raises NotFoundError for the same situation
             raise KeyError("checkpoint lacks %d variable(s) of this model (prior=%s, no_encoder=%s, c_v=%s), e.g. %s -- was it saved "
                            "with different options?" % (len(missing), p.prior, p.no_encoder, p.use_c_v, missing[0]))
@@ -314,9 +336,11 @@ class CaptionEngine(object):
                 ks = [named[spec.head_scope(p.prior, k) + "dense/bias"] for k in range(K_CL)]
                 ls = [named[spec.head_scope(p.prior, k) + "dense_1/bias"] for k in range(K_CL)]
                 arr = np.concatenate(ks + ls, axis=0)
+            elif name in keep:
+                continue
             else:
                 arr = named[name]
-            if name.startswith("decoder/rnn_logits/") and np.shape(arr)[-1] == self.V != self.Vp:  # zero-pad the vocabulary columns
+            if name.startswith(("decoder/rnn_logits/", "bow/")) and np.shape(arr)[-1] == self.V != self.Vp:  # zero-pad the vocabulary columns
                 arr = np.concatenate([arr, np.zeros(np.shape(arr)[:-1] + (self.Vp - self.V,), np.float32)], axis=-1)
             dst = self.store.param(name)
             if tuple(np.shape(arr)) != tuple(dst.shape):
@@ -337,7 +361,7 @@ class CaptionEngine(object):
                 for k in range(K_CL):
                     out[spec.head_scope(p.prior, k) + "dense/bias"] = a[k * L:(k + 1) * L].copy()
                     out[spec.head_scope(p.prior, k) + "dense_1/bias"] = a[(K_CL + k) * L:(K_CL + k + 1) * L].copy()
-            elif name.startswith("decoder/rnn_logits/"):
+            elif name.startswith(("decoder/rnn_logits/", "bow/")):
                 out[name] = np.ascontiguousarray(a[..., :self.V])
             else:
                 out[name] = a
@@ -686,6 +710,7 @@ class CaptionEngine(object):
         feats = features if features is not None else self.buf["features"]
         self.feats = feats
         self._train = bool(train)
+        self._den_early = False
         if not self.inject:
             self._noise()
         if train and self.kl_cycle[0] > 0:  # cyclical KL annealing: the coefficient from the device step counter, like the tanh one
@@ -801,10 +826,43 @@ class CaptionEngine(object):
         fw_decode on the mixed inputs (same z, same dropout masks, same image states; the encoder, the KL term, the step counter and
         the data-parallel all-gather belong to the stages before and run once)."""
         logits = self.fw_decode()
+        if self.bow_loss > 0 and self._train and not self.policy:   # behind the FIRST pass: the z step is the same in every pass
+            self.fw_bow()
         if self.sched_rate > 0 and self._train and not self.policy:
             self.fw_sched_mix()
             logits = self.fw_decode("dec_mix_t", "mix", init_done=True)
         return logits
+
+    def _count_labels(self):
+        """the CE denominator of main.py:156-157 into red[1]: the non-PAD labels of the (global) batch"""
+        lib, st = self.lib, _stream()
+        den = self.red[1:2]
+        if not (self.collectives and getattr(self, "_den_gathered", False)):  # (global Q1 mix: the count came with the all-gather)
+            lib.vc_count_nonzero_i32(st, P(self.buf["cap_enc_t"]), self.T * self.N, P(den))
+            if self.collectives:
+                self.reduce_fn(den)
+        return den
+
+    def fw_bow(self):
+        """The bag-of-words head of a training forward (DESIGN.md "Bag-of-words loss"): bow_logits [N, Vp] = Xd[zi] @ bow/kernel + bow/bias
+        on the decoder's z step, then vc_bow_xent_f32 against the bags of cap_enc_t with the cross-entropy's den and gscale * bow_loss --
+        d(bow term)/d(bow_logits) in place -- and the three reported numbers of this rank's rows.  The label count is taken here, in
+        front of fw_loss, which then does not repeat it."""
+        p, lib, st, S = self.p, self.lib, _stream(), self.store
+        N, T, E, V, Vp = self.N, self.T, p.embed_size, self.V, self.Vp
+        if T > 256:
+            raise ValueError("the bag-of-words loss takes captions of at most 256 positions (got %d)" % T)
+        zi = self.n_init_d - 1
+        bl = self._b("bow_logits", (N, Vp))
+        self.gemm(0, 0, N, Vp, E, self.buf["Xd"][zi], E, S.param(spec.BOW_KERNEL), Vp, bl, Vp, S.param(spec.BOW_BIAS))
+        den = self._count_labels()
+        self._den_early = True
+        gscale = dp.scales(N, self.world, self.enc and p.prior == "AG")[0] * self.bow_loss
+        labels = self.buf["cap_enc_t"]
+        rl, rm, rw = self._b("bow_row_loss", (N,)), self._b("bow_row_mass", (N,)), self._b("bow_row_words", (N,), torch.int32)
+        lib.vc_bow_xent_f32(st, P(bl), N, V, Vp, P(labels), T, N, P(den), gscale, P(rl), P(rm), P(rw), 1)
+        lib.vc_bow_stats_f32(st, N, V, P(labels), T, N, P(rl), P(rm), P(rw), P(self.bstat))
+        return bl
 
     def fw_sched_mix(self):
         """vc_sched_mix_f32 on the logits of the pass just run -> the persistent dec_mix_t [T, N], then the embedding-gradient index of
@@ -879,11 +937,8 @@ class CaptionEngine(object):
         ann = self.scal[1:2]
         kl_sum = self.kl_sum
         labels = self.buf["cap_enc_t"]
-        den = self.red[1:2]
-        if not (self.collectives and getattr(self, "_den_gathered", False)):  # (global Q1 mix: the count came with the all-gather)
-            lib.vc_count_nonzero_i32(st, P(labels), T * N, P(den))
-            if self.collectives:
-                self.reduce_fn(den)
+        den = self.red[1:2] if self._den_early else self._count_labels()   # (fw_bow of this forward has counted already)
+        self._den_early = False
         vector_loss = self.enc and p.prior == "AG"  # Q3
         Ng = N * self.world
         gscale = dp.scales(N, self.world, vector_loss)[0]
@@ -988,6 +1043,14 @@ class CaptionEngine(object):
             zi = nid - 1
             dz_dec = dXd[zi]
             z = self.buf["z"]
+            if self.bow_loss > 0 and not policy:
+                # the bag-of-words head: its weight gradient off the chain, its input gradient added to the z step's -- behind the
+                # BPTT that wrote dXd[zi], in front of z_rnn's weight gradient and the dz product that read it
+                dbow = self.buf["bow_logits"]
+                side(lambda: self.dense_bwd_w(self.buf["Xd"][zi], N, E, Vp, dbow, spec.BOW_KERNEL, spec.BOW_BIAS))  # padding columns of dbow are 0
+                d_in = self._b("bow_d_in", (N, E))
+                self.gemm(0, 1, N, E, Vp, dbow, Vp, S.param(spec.BOW_KERNEL), Vp, d_in, E)
+                lib.vc_axpy_f32(st, 1.0, P(d_in), N * E, P(dz_dec))
             side(lambda: self.dense_bwd_w(z, N, Sm * L, E, dz_dec, "decoder/net/z_rnn/kernel", "decoder/net/z_rnn/bias"))
         if self.enc and not policy:
             dz = self._b("dz", (Sm, N, L))
@@ -1266,8 +1329,10 @@ class CaptionEngine(object):
         Free bits (--kl_free_bits > 0): {"kl_raw": mean unclamped KL per caption row, "floored_share": share of the N * L latent
         dimensions held at the floor}.  Unlikelihood training (--unlikelihood > 0): {"ul": the unlikelihood loss per live row (before
         its weight), "ul_candidates": mean number of candidate words per live row, "repeat_mass": mean probability per live row on
-        the words the caption has already said} of the last TRAINING forward."""
-        if self.ostat is None and self.ustat is None:
+        the words the caption has already said} of the last TRAINING forward.  Bag-of-words loss (--bow_loss > 0): {"bow": the head's loss
+        in nats per bag word (before its weight), "bow_words": mean distinct words per non-empty caption, "bow_mass": mean probability
+        the head puts on a non-empty caption's distinct words} of the last TRAINING forward."""
+        if self.ostat is None and self.ustat is None and self.bstat is None:
             return None
         d = {}
         if self.ostat is not None:
@@ -1276,6 +1341,9 @@ class CaptionEngine(object):
         if self.ustat is not None:
             u = self.ustat.detach().cpu().numpy()
             d.update({"ul": float(u[0]), "ul_candidates": float(u[1]), "repeat_mass": float(u[2])})
+        if self.bstat is not None:
+            b = self.bstat.detach().cpu().numpy()
+            d.update({"bow": float(b[0]), "bow_words": float(b[1]), "bow_mass": float(b[2])})
         return d
 
     def sched_stats(self):

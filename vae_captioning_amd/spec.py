@@ -24,6 +24,14 @@ def uses_ci(p):
     return bool(p.use_c_v) or p.prior in ("GMM", "AG")
 
 
+BOW_KERNEL, BOW_BIAS = "bow/kernel", "bow/bias"
+
+
+def uses_bow(p):
+    """the bag-of-words head exists with --bow_loss > 0 on a model with an encoder (DESIGN.md "Bag-of-words loss")"""
+    return float(getattr(p, "bow_loss", 0.0)) > 0 and not p.no_encoder
+
+
 def head_scope(prior, k):
     return ("encoder/gmm_ll_%d/" if prior == "GMM" else "encoder/ag_ll_%d/") % k
 
@@ -60,6 +68,10 @@ def caption_variables(p, vocab):
                 s = head_scope(p.prior, k)
                 v += [(s + "dense/kernel", (He, L)), (s + "dense/bias", (L,)),
                       (s + "dense_1/kernel", (He, L)), (s + "dense_1/bias", (L,))]
+    if uses_bow(p):
+        # the bag-of-words head (--bow_loss > 0; not in the reference graph): LAST, so that with the flag off the list, the random
+        # stream of init_caption_params and every offset are what they were, and with it on every other variable draws what it drew
+        v += [(BOW_KERNEL, (E, vocab)), (BOW_BIAS, (vocab,))]
     return v
 
 

@@ -37,6 +37,8 @@ _DEFAULTS = dict(
     sched_sampling=0.0, sched_schedule="linear", sched_ramp_steps=10000, sched_pick="sample", sched_temperature=1.0,
     # unlikelihood training (off by default)
     unlikelihood=0.0, ul_window=128,
+    # bag-of-words auxiliary loss (off by default)
+    bow_loss=0.0,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -76,6 +78,7 @@ _FLAGS = [
     ("--sched_ramp_steps", "sched_ramp_steps", int, None), ("--sched_pick", "sched_pick", str, ["sample", "argmax"]),
     ("--sched_temperature", "sched_temperature", float, None),
     ("--unlikelihood", "unlikelihood", float, None), ("--ul_window", "ul_window", int, None),
+    ("--bow_loss", "bow_loss", float, None),
 ]
 _KL_FLAGS = ("kl_free_bits", "kl_weight", "kl_cycle_steps", "kl_cycle_ramp", "kl_cycles")
 _SCHED_FLAGS = ("sched_schedule", "sched_ramp_steps", "sched_pick", "sched_temperature")
@@ -162,6 +165,10 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                            "0 = off; validation losses and the reported rec_loss stay the cross-entropy; not with --scst)",
          "--ul_window": "--unlikelihood: how many earlier positions of the caption supply those words (1..128; default 128; a longer "
                         "caption is no error, the window bounds the look-back)",
+         "--bow_loss": "training objective: weight A of the bag-of-words auxiliary loss -- a head that sees the latent code alone (the "
+                       "decoder's z step) and must predict which words the caption contains, so that z has a reason of its own to carry "
+                       "the caption (finite, >= 0; default 0 = off; adds the variables bow/kernel and bow/bias; validation losses and the "
+                       "reported rec_loss stay as they are; not with --no_encoder, --scst or --mode inference)",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
@@ -318,6 +325,15 @@ class Parameters(object):
             ap.error("--ul_window belongs to --unlikelihood > 0")
         if self.unlikelihood > 0 and self.scst:
             ap.error("--unlikelihood shapes the cross-entropy objective, which --scst does not optimise")
+        if not (0.0 <= self.bow_loss < float("inf")):
+            ap.error("--bow_loss must be finite and >= 0 (0 = off; got %r)" % self.bow_loss)
+        if self.bow_loss > 0:
+            if self.no_encoder:
+                ap.error("--bow_loss trains the latent code through a head on it, and --no_encoder has none")
+            if self.scst:
+                ap.error("--bow_loss shapes the cross-entropy objective, which --scst does not optimise")
+            if self.mode != "training":
+                ap.error("--bow_loss is a way of training: not with --mode %s" % self.mode)
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.eval_self_cider and not self.eval_captions:
