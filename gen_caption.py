@@ -6,6 +6,7 @@
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
         [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam|constrained_beam|stochastic_beam] [--must_include "dog,puppy;frisbee"] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
         [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
+        [--typical_p 1.0] [--min_p 0] [--eta_cutoff 0]   (sampled decoding: locally typical / min-p / eta sampling; not with --top_k / --top_p)
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
 VGG16 fc2 features [1, 4096], imf_emb -> decoder (prior z) -> greedy / beam search, print the caption.
@@ -118,11 +119,12 @@ class Generator(object):
         return fc2.cpu().numpy(), img
 
     def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None, must_include=None,
-                         controls=None):
+                         controls=None, typical_p=None, min_p=None, eta=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
         "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
         the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
-        the params unless given.  gen_method "marginal_greedy" / "marginal_beam" (additive): the search under the mixture of
+        the params unless given; typical_p / min_p / eta (additive): the entropy- and peak-following cuts of sampled decoding, taken in
+        the same way (not together with top_k / top_p).  gen_method "marginal_greedy" / "marginal_beam" (additive): the search under the mixture of
         `marginal_draws` latent draws (beam_size hypotheses for marginal_beam); the record also holds "marginal" and "draws".
         gen_method "constrained_beam" (additive): beam search whose caption mentions the words of `must_include` ("dog,puppy;frisbee":
         ';' separates sets, ',' the words of a set, any of which satisfies it); the record also holds "constraints", "satisfied", "score".
@@ -134,6 +136,9 @@ class Generator(object):
             self.params.top_k = int(top_k)
         if top_p is not None:
             self.params.top_p = float(top_p)
+        for name, val in (("typical_p", typical_p), ("min_p", min_p), ("eta", eta)):
+            if val is not None:
+                setattr(self.params, name, float(val))
         from vae_captioning_amd.vae_model.decoder import Decoder
         if not img_path or not os.path.exists(img_path):
             raise ValueError("Image not found")
@@ -175,6 +180,13 @@ if __name__ == "__main__":
     parser.add_argument("--top_k", type=int, default=None, help="sampled decoding: draw from the k most likely words (0 = all; default: the params')")
     parser.add_argument("--top_p", type=float, default=None, help="sampled decoding: draw from the nucleus holding this share of the probability "
                                                                   "((0, 1], 1 = all; default: the params')")
+    parser.add_argument("--typical_p", type=float, default=None, help="sampled decoding: locally typical sampling, the words closest in surprisal "
+                                                                      "to the prediction's entropy that hold this share ((0, 1], 1 = all; "
+                                                                      "default: the params'; not with --top_k / --top_p)")
+    parser.add_argument("--min_p", type=float, default=None, help="sampled decoding: the words at least this fraction as likely as the most "
+                                                                  "likely one ([0, 1], 0 = all; default: the params')")
+    parser.add_argument("--eta_cutoff", type=float, default=None, help="sampled decoding: eta sampling, the words with probability >= min(eta, "
+                                                                       "sqrt(eta) * exp(-entropy)) ([0, 1), 0 = all; default: the params')")
     parser.add_argument("--marginal_draws", type=int, default=None, help="--gen_method marginal_greedy / marginal_beam: latent draws whose "
                                                                          "mixture is searched (1..256; default: the params' marginal_draws)")
     parser.add_argument("--must_include", default=None, help="--gen_method constrained_beam: words the caption must mention, e.g. "
@@ -203,6 +215,12 @@ if __name__ == "__main__":
         parser.error("--top_k must be >= 0 (got %d)" % args.top_k)
     if args.top_p is not None and not (0.0 < args.top_p <= 1.0):
         parser.error("--top_p must be in (0, 1] (got %r)" % args.top_p)
+    if args.typical_p is not None and not (0.0 < args.typical_p <= 1.0):
+        parser.error("--typical_p must be in (0, 1] (got %r)" % args.typical_p)
+    if args.min_p is not None and not (0.0 <= args.min_p <= 1.0):
+        parser.error("--min_p must be in [0, 1] (got %r)" % args.min_p)
+    if args.eta_cutoff is not None and not (0.0 <= args.eta_cutoff < 1.0):
+        parser.error("--eta_cutoff must be in [0, 1) (got %r)" % args.eta_cutoff)
     if args.gen_method == "stochastic_beam" and not 1 <= int(args.beam_size) <= 32:
         parser.error("--beam_size must be 1..32 with --gen_method stochastic_beam (got %s)" % args.beam_size)
     if args.gpu != "":
@@ -215,7 +233,7 @@ if __name__ == "__main__":
         words = [int(w) if w.lstrip("-").isdigit() else w for w in (x.strip() for x in (args.must_exclude or "").split(",")) if w]
         controls = DecodeControls(args.no_repeat_ngram, args.min_len, args.repetition_penalty, parse_banned(words, generator.data_dict))
     caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws, args.must_include,
-                                         controls)
+                                         controls, args.typical_p, args.min_p, args.eta_cutoff)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

@@ -52,6 +52,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the mutual-information entry vc_gauss_mix_lse_f64.
  *      Added within 4 (additive, no layout change): the unlikelihood-training entries vc_softmax_xent_ul_f32, vc_ul_stats_f32.
  *      Added within 4 (additive, no layout change): the bag-of-words loss entries vc_bow_xent_f32, vc_bow_stats_f32.
+ *      Added within 4 (additive, no layout change): the typical / min-p / eta sampling entry vc_decode_pick_typical_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -671,6 +672,14 @@ int vc_eos_track_i32(void* stream, const int32_t* tok, int B, int eos, int32_t* 
  *                    does not depend on rows, on the row's place in the launch or on the call.  logprob is decode_pick's: the
  *                    log-softmax at temperature 1 over the FULL vocabulary (the model's likelihood, not the sampler's).  kept (NULL or
  *                    [rows]): the number of words kept.  top_k 0 / >= V with top_p 1 is decode_pick itself, bit for bit.
+ *   decode_pick_typical decode_pick's sampled round with cuts that follow the row's entropy or peak (u is required).  y as above, p =
+ *                    softmax(y) over the FULL vocabulary, H = -sum p log p (nats; a word of zero mass adds 0).  typical_p = tau < 1: order by
+ *                    d = |-log p - H| ascending, equal d by lower index, and keep the shortest prefix whose mass is >= tau (at least one
+ *                    word; 1 = off).  min_p, eta: keep p >= max(min_p * p_max, min(eta, sqrt(eta) * exp(-H))) (0 = off; min_p = 1 keeps the
+ *                    maxima of y).  Kept = typical set AND floor set, both taken on the full distribution (no cut renormalises for the
+ *                    next); an empty intersection keeps the first maximum of y; a word of zero mass is never kept.  The draw, the integer
+ *                    masses, logprob and kept are decode_pick_trunc's.  entropy (NULL or [rows]): H of every row.  All cuts off
+ *                    (1, 0, 0) is decode_pick itself, bit for bit, with kept = V and entropy left UNTOUCHED.
  *   decode_round_end pending[0] = rows with done == 0 (float); round[0] += 1 when round is not NULL.  One workgroup.
  *   diverse_rank     per image (one workgroup, K <= 256, rows == B*K): score = logprob / (1 + len)^len_norm_f; candidates with equal token
  *                    sequences merged (best score kept, ties: lower draw); ranked <EOS>-ended first, then score descending, then lower
@@ -683,6 +692,9 @@ int vc_decode_pick_f32(void* stream, const float* logits, long rows, int V, long
 int vc_decode_pick_trunc_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, int top_k, float top_p,
                              const float* u, int u_rounds, const int32_t* round, int eos, int32_t* tok, int32_t* done, int32_t* seq, int Lmax,
                              int32_t* len, double* logprob, int32_t* kept);
+int vc_decode_pick_typical_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, float typical_p, float min_p,
+                               float eta, const float* u, int u_rounds, const int32_t* round, int eos, int32_t* tok, int32_t* done,
+                               int32_t* seq, int Lmax, int32_t* len, double* logprob, int32_t* kept, float* entropy);
 int vc_decode_round_end_i32(void* stream, const int32_t* done, long rows, float* pending, int32_t* round);
 int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32_t* seq, const int32_t* len, const int32_t* ended,
                     const double* logprob, double len_norm_f, int32_t* n_distinct, int32_t* rep, int32_t* count, double* score);

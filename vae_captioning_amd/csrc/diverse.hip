@@ -9,6 +9,8 @@
 //                            for bit: row_ops.h
 //   vc_decode_pick_trunc_f32 the same round with the distribution truncated before the draw: the top_k best words and / or the smallest
 //                            set of best words holding a share top_p of the probability, found by a radix select (no sort of V words)
+//   vc_decode_pick_typical_f32 the same round with cuts that follow the row's entropy or peak: locally typical sampling (the words whose
+//                            surprisal is closest to the entropy, by the same radix select over another key), min-p and eta floors
 //   vc_decode_round_end_i32  pending = rows without <EOS>, round += 1 (the device round counter keys the next round's uniforms)
 //   vc_diverse_rank          one workgroup per image: scores, 64-bit hashes confirmed by full compares, duplicates merged, ranked
 #include "row_ops.h"
@@ -136,12 +138,19 @@ struct PickSel {
     int bin, found;
 };
 
+// The key of word c that radix_select orders by, and the mass of a word with that key.  LogitKey: the truncation's order, descending y.
+struct LogitKey {
+    const float* p;
+    float inv_temp, my;
+    __device__ __forceinline__ uint32_t key(int c) const { return pick_key(p[c], inv_temp); }
+    __device__ __forceinline__ unsigned long long mass(int, uint32_t k) const { return key_mass(k, my); }
+};
+
 // MSB-first radix select, 8 bits per pass, over the words with key > lo: the key T at which the running quantity (MASS: the words' masses,
 // else their number), summed from the best word down, first reaches thr; above = the quantity of the keys > T.  false: the eligible
 // words together stay below thr.  Each pass: a 256-bin histogram of the words that share the prefix found so far, scanned from the top.
-template <bool MASS>
-__device__ bool radix_select(const float* p, int V, float inv_temp, float my, long long lo, double thr, PickSel& S, uint32_t& T,
-                             unsigned long long& above) {
+template <bool MASS, class KeyF>
+__device__ bool radix_select(const KeyF& key, int V, long long lo, double thr, PickSel& S, uint32_t& T, unsigned long long& above) {
     const int t = threadIdx.x;
     uint32_t prefix = 0;
     unsigned long long ab = 0;
@@ -152,9 +161,9 @@ __device__ bool radix_select(const float* p, int V, float inv_temp, float my, lo
         if (t == 0) { S.found = 0; S.bin = 0; S.above = ab; }
         __syncthreads();
         for (int c = t; c < V; c += 256) {
-            const uint32_t k = pick_key(p[c], inv_temp);
+            const uint32_t k = key.key(c);
             const bool in = pass == 0 || (k >> (shift + 8)) == prefix;
-            if ((long long)k > lo && in) atomicAdd(&S.hist[((k >> shift) & 255u) * PICK_HIST_COPIES + (t & (PICK_HIST_COPIES - 1))], MASS ? key_mass(k, my) : 1ull);
+            if ((long long)k > lo && in) atomicAdd(&S.hist[((k >> shift) & 255u) * PICK_HIST_COPIES + (t & (PICK_HIST_COPIES - 1))], MASS ? key.mass(c, k) : 1ull);
         }
         __syncthreads();
         unsigned long long v = 0;   // thread t holds the t-th bin from the top
@@ -215,7 +224,7 @@ __global__ __launch_bounds__(256) void decode_pick_trunc_kernel(const float* __r
     unsigned long long ab;
     const bool by_k = top_k > 0 && top_k < V;
     if (by_k) {
-        radix_select<false>(p, V, inv_temp, my, -1, (double)top_k, S, T, ab);
+        radix_select<false>(LogitKey{p, inv_temp, my}, V, -1, (double)top_k, S, T, ab);
         j = jcap = (long)top_k - (long)ab;
         lo = (long long)T;
     }
@@ -231,7 +240,7 @@ __global__ __launch_bounds__(256) void decode_pick_trunc_kernel(const float* __r
         zk += (unsigned long long)j * mk * (by_k ? 1ull : 0ull);
         const double thr = (double)top_p * (double)zk;
         uint32_t Tp;
-        if (radix_select<true>(p, V, inv_temp, my, lo, thr, S, Tp, ab)) {
+        if (radix_select<true>(LogitKey{p, inv_temp, my}, V, lo, thr, S, Tp, ab)) {
             T = Tp;
             jcap = V;
             j = tie_count(thr, ab, key_mass(T, my), V);
@@ -287,6 +296,170 @@ __global__ __launch_bounds__(256) void decode_pick_trunc_kernel(const float* __r
         const int w = min(max(s_tok >= 0 ? s_tok : s_last, 0), V - 1);
         tok[r] = w;
         if (kept) kept[r] = (int32_t)(n_gt + j);
+        const int n = len[r];
+        if (!done[r] && n >= 0 && n < Lmax) {
+            const float lp = lsm_term(p[w], mx1, logf(s1));   // over the full vocabulary
+            seq[r * Lmax + n] = w;
+            len[r] = n + 1;
+            logprob[r] += (double)lp;
+            if (w == eos) done[r] = 1;
+        }
+    }
+}
+
+// ---- typical / min-p / eta pick.  Cuts that follow the row's entropy H or its peak, all taken on the FULL distribution p = softmax(y):
+//   typical_p tau: order by d = |-log p - H| ascending, equal d by lower index; the shortest prefix whose mass is >= tau
+//   min_p, eta:    p >= max(min_p * p_max, min(eta, sqrt(eta) * exp(-H)))
+// and the kept set is their intersection (empty: the first maximum of y).  With g = max y - y >= 0, the integer masses m (key_mass) and
+// their exact sums Z = sum m, E = sum round(m * g):  A = E / Z,  -log p - H = g - A (log Z cancels),  H = log(Z 2^-32) + A,  and a floor
+// f on p is the threshold g <= -log f - log(Z 2^-32) (min_p alone: g <= -log min_p, so min_p = 1 keeps exactly the maxima of y).
+// A word of zero mass (a banned word's -FLT_MAX scaled to -inf has g = +inf) adds nothing to E and is never kept.  A and the threshold
+// are formed in float64 from the integer sums and rounded once to f32; d = |g - A| is one f32 subtraction (monotone in g, equal for
+// equal y), far inside the margin the reference leaves around a cut.
+// The select needs a word's mass only where its key falls into the prefix found so far, so the mass (an exponential and a 64-bit
+// conversion) is formed on demand.  A word of zero mass needs no key of its own: it adds 0 to every histogram bin and to every running
+// mass, so no cut can fall on it, and the kept test asks for m != 0.
+struct TypWord {
+    uint32_t yk;   // pick_key of the word
+    uint32_t dk;   // order-preserving image of -d: ~bits(d), d = |g - A| >= 0 in f32 (the radix select runs from the largest key down)
+    float g;
+};
+struct TypKey {
+    const float* p;
+    float inv_temp, my, A;
+    __device__ __forceinline__ TypWord word(int c) const {
+        TypWord w;
+        w.yk = pick_key(p[c], inv_temp);
+        w.g = my - key_value(w.yk);
+        w.dk = ~__float_as_uint(fabsf(w.g - A));   // (g = +inf: d = +inf, the smallest key)
+        return w;
+    }
+    __device__ __forceinline__ uint32_t key(int c) const { return word(c).dk; }
+    __device__ __forceinline__ unsigned long long mass(int c, uint32_t) const { return key_mass(pick_key(p[c], inv_temp), my); }
+};
+
+// One workgroup per row, the row staged in LDS (STAGE) or re-read.  At least one cut is on (the entry dispatches the rest).
+template <bool STAGE>
+__global__ __launch_bounds__(256) void decode_pick_typical_kernel(const float* __restrict__ logits, long rows, int V, long ld, float inv_temp,
+                                                                  float typical_p, float min_p, float eta, const float* __restrict__ u,
+                                                                  int u_rounds, const int32_t* __restrict__ round, int eos,
+                                                                  int32_t* __restrict__ tok, int32_t* __restrict__ done,
+                                                                  int32_t* __restrict__ seq, int Lmax, int32_t* __restrict__ len,
+                                                                  double* __restrict__ logprob, int32_t* __restrict__ kept,
+                                                                  float* __restrict__ entropy) {
+    extern __shared__ float srow[];
+    __shared__ PickSel S;
+    __shared__ float sh[4];
+    __shared__ int s_tok, s_last, s_first, s_j;
+    const long r = blockIdx.x;
+    const int t = threadIdx.x;
+    const float* p = stage_row<STAGE>(logits + r * ld, V, srow);
+    if (t == 0) { s_tok = -1; s_last = 0; s_first = 0x7fffffff; s_j = 0; }
+    int c0, c1;
+    row_chunk(V, c0, c1);
+    float bv = -INFINITY;
+    for (int c = t; c < V; c += 256) bv = fmaxf(bv, p[c]);
+    const float mx1 = block_max<256>(bv, sh);
+    const float s1 = row_exp_sum(p, c0, c1, mx1, sh);
+    const uint32_t kmy = pick_key(mx1, inv_temp);
+    const float my = key_value(kmy);
+
+    // ---- the row's statistics: Z, E (exact integer sums) and the first maximum of y
+    unsigned long long z = 0, e = 0, Z, E;
+    int first = 0x7fffffff;
+    for (int c = t; c < V; c += 256) {
+        const uint32_t k = pick_key(p[c], inv_temp);
+        if (k == kmy) first = min(first, c);
+        const unsigned long long m = key_mass(k, my);
+        if (m) {   // (zero mass: g may be +inf, and 0 * inf would poison the sum)
+            z += m;
+            // round(m * g) as the mantissa of m * g + 2^52: m <= 2^32 and g < 24 where m > 0, so the product stays below 2^37
+            e += (unsigned long long)__double_as_longlong((double)m * (double)(my - key_value(k)) + 4503599627370496.0) & 0xfffffffffffffull;
+        }
+    }
+    if (first != 0x7fffffff) atomicMin(&s_first, first);
+    block_scan_u64(z, S.ws, Z);
+    block_scan_u64(e, S.ws, E);
+    const double Zd = (double)Z, A = (double)E / Zd, lz = log(Zd * (1.0 / 4294967296.0)), H = lz + A;
+    double gm = INFINITY;   // the floors as one threshold on g
+    if (min_p > 0.f) gm = -log((double)min_p);
+    if (eta > 0.f) gm = fmin(gm, -log(fmin((double)eta, sqrt((double)eta) * exp(-H))) - lz);
+    const float gmax = (float)gm;   // (min_p = 1: -0, and g <= -0 holds for g = 0 alone)
+
+    // ---- the typical cut: words with dk > Td, and the first j (index order) of the words with dk == Td
+    const bool typ = typical_p < 1.0f;
+    const TypKey key{p, inv_temp, my, (float)A};
+    uint32_t Td = 0;
+    long j = 0, eq0 = 0;
+    if (typ) {
+        const double thr = (double)typical_p * Zd;
+        unsigned long long ab;
+        if (!radix_select<true>(key, V, -1, thr, S, Td, ab)) { Td = 0xffffffffu; ab = 0; }   // (a row without a finite maximum: nothing is kept)
+        unsigned long long eqm = 0, eqc = 0, tot;
+        for (int c = c0; c < c1; ++c) {
+            const TypWord w = key.word(c);
+            if (w.dk == Td) { eqm += key_mass(w.yk, my); ++eqc; }
+        }
+        const unsigned long long incl = ab + block_scan_u64(eqm, S.ws, tot);
+        eq0 = (long)(block_scan_u64(eqc, S.ws, tot) - eqc);   // equal words before this chunk
+        if ((double)incl >= thr && !((double)(incl - eqm) >= thr)) {   // the chunk in which the running mass reaches tau * Z
+            unsigned long long run = incl - eqm;
+            long n = eq0;
+            for (int c = c0; c < c1; ++c) {
+                const TypWord w = key.word(c);
+                if (w.dk != Td) continue;
+                run += key_mass(w.yk, my);
+                ++n;
+                if ((double)run >= thr) break;
+            }
+            s_j = (int)n;
+        }
+        __syncthreads();
+        j = s_j;
+    }
+    // eq: the number of words with dk == Td met so far, in index order
+    auto is_kept = [&](const TypWord& w, long& eq, unsigned long long& m) {
+        const bool in = !typ || w.dk > Td || (w.dk == Td && eq++ < j);
+        if (!(in && w.g <= gmax)) return false;
+        m = key_mass(w.yk, my);
+        return m != 0;
+    };
+    // ---- kept words per chunk: their number and mass; the draw
+    unsigned long long part = 0, cnt = 0, z_kept, n_kept, m;
+    long eq = eq0;
+    for (int c = c0; c < c1; ++c)
+        if (is_kept(key.word(c), eq, m)) { part += m; ++cnt; }
+    const unsigned long long run_incl = block_scan_u64(part, S.ws, z_kept);
+    block_scan_u64(cnt, S.ws, n_kept);
+    const int rd = round ? min(max(round[0], 0), u_rounds - 1) : 0;
+    const double target = (double)u[(long)rd * rows + r] * (double)z_kept;
+    if (n_kept && (double)run_incl > target && !((double)(run_incl - part) > target)) {   // inverse CDF over the kept words in index order
+        unsigned long long run = run_incl - part;
+        int idx = -1;
+        eq = eq0;
+        for (int c = c0; c < c1; ++c) {
+            if (is_kept(key.word(c), eq, m)) {
+                run += m;
+                idx = c;
+                if ((double)run > target) break;
+            }
+        }
+        s_tok = idx;
+    }
+    __syncthreads();
+    if (n_kept && s_tok < 0) {   // no running mass exceeds the target (u >= 1): the last kept word
+        int last = -1;
+        eq = eq0;
+        for (int c = c0; c < c1; ++c)
+            if (is_kept(key.word(c), eq, m)) last = c;
+        if (last >= 0) atomicMax(&s_last, last);
+        __syncthreads();
+    }
+    if (t == 0) {
+        const int w = min(max(!n_kept ? s_first : s_tok >= 0 ? s_tok : s_last, 0), V - 1);   // an empty intersection: the first maximum of y
+        tok[r] = w;
+        if (kept) kept[r] = n_kept ? (int32_t)n_kept : 1;
+        if (entropy) entropy[r] = (float)H;
         const int n = len[r];
         if (!done[r] && n >= 0 && n < Lmax) {
             const float lp = lsm_term(p[w], mx1, logf(s1));   // over the full vocabulary
@@ -436,6 +609,36 @@ extern "C" int vc_decode_pick_trunc_f32(void* stream, const float* logits, long 
     else
         hipLaunchKernelGGL(decode_pick_trunc_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, logits, rows, V, ld, inv_temp, top_k,
                            top_p, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob, kept);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_decode_pick_typical_f32(void* stream, const float* logits, long rows, int V, long ld, float temperature, float typical_p,
+                                          float min_p, float eta, const float* u, int u_rounds, const int32_t* round, int eos, int32_t* tok,
+                                          int32_t* done, int32_t* seq, int Lmax, int32_t* len, double* logprob, int32_t* kept,
+                                          float* entropy) {
+    VC_CHECK_ARG(logits && tok && done && seq && len && logprob, "null pointer");
+    VC_CHECK_ARG(rows > 0 && V > 0 && ld >= V && Lmax > 0, "bad shape");
+    VC_CHECK_ARG(u && u_rounds > 0, "typical / min-p / eta sampling needs uniforms (u, u_rounds > 0): without a draw it is the argmax");
+    VC_CHECK_ARG(temperature > 0.f && temperature < INFINITY, "temperature must be finite and > 0");
+    VC_CHECK_ARG(typical_p > 0.f && typical_p <= 1.0f, "typical_p must be in (0, 1] (1 = off)");
+    VC_CHECK_ARG(min_p >= 0.f && min_p <= 1.0f, "min_p must be in [0, 1] (0 = off)");
+    VC_CHECK_ARG(eta >= 0.f && eta < 1.0f, "eta must be in [0, 1) (0 = off)");
+    const hipStream_t st = (hipStream_t)stream;
+    if (typical_p == 1.0f && min_p == 0.f && eta == 0.f) {   // nothing to cut: the plain draw, bit for bit (entropy is left untouched)
+        const int rc = vc_decode_pick_f32(stream, logits, rows, V, ld, temperature, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob);
+        if (rc) return rc;
+        if (kept) hipLaunchKernelGGL(fill_kept_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, kept, rows, V);
+        VC_LAUNCH_CHECK();
+        return 0;
+    }
+    const float inv_temp = 1.0f / temperature;
+    if (V <= ROW_LDS_MAX)
+        hipLaunchKernelGGL(decode_pick_typical_kernel<true>, dim3((unsigned)rows), dim3(256), (size_t)V * sizeof(float), st, logits, rows, V, ld,
+                           inv_temp, typical_p, min_p, eta, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob, kept, entropy);
+    else
+        hipLaunchKernelGGL(decode_pick_typical_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, logits, rows, V, ld, inv_temp, typical_p,
+                           min_p, eta, u, u_rounds, round, eos, tok, done, seq, Lmax, len, logprob, kept, entropy);
     VC_LAUNCH_CHECK();
     return 0;
 }

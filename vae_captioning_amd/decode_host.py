@@ -148,7 +148,28 @@ def check_truncation(top_k, top_p, method="sample"):
     return int(top_k), top_p
 
 
-CBS_MAX_SETS, CBS_MAX_WORDS = 3, 4   # constrained beam search: constraints per image, words per constraint (vc_beam_update_constrained)
+def check_typical(typical_p, min_p, eta, method="sample", top_k=0, top_p=1.0):
+    """(typical_p, min_p, eta) of typical / min-p / eta sampling as floats; ValueError for values outside 0 < typical_p <= 1,
+    0 <= min_p <= 1, 0 <= eta < 1, for a cut asked of a greedy decode (it has no draw to cut) and for a cut together with top_k / top_p
+    (the two families would need a stated order of renormalisation: DESIGN.md "Typical / min-p / eta sampling").  (1.0, 0.0, 0.0) = off."""
+    typical_p, min_p, eta = float(typical_p), float(min_p), float(eta)
+    if not (0.0 < typical_p <= 1.0):
+        raise ValueError("typical_p must be in (0, 1] (1 = off; got %r)" % (typical_p,))
+    if typical_p < 1.0 and float(np.float32(typical_p)) >= 1.0:
+        raise ValueError("typical_p = %r is 1 in float32: pass 1.0 for no typical cut" % (typical_p,))
+    if not (0.0 <= min_p <= 1.0):
+        raise ValueError("min_p must be in [0, 1] (0 = off; got %r)" % (min_p,))
+    if not (0.0 <= eta < 1.0) or float(np.float32(eta)) >= 1.0:
+        raise ValueError("eta must be in [0, 1) (0 = off; got %r)" % (eta,))
+    if typical_p != 1.0 or min_p != 0.0 or eta != 0.0:
+        if method != "sample":
+            raise ValueError("typical_p / min_p / eta cut the draw of method='sample'; method=%r has none" % (method,))
+        if int(top_k) != 0 or float(top_p) != 1.0:
+            raise ValueError("typical_p / min_p / eta do not combine with top_k / top_p: give one family of cuts")
+    return typical_p, min_p, eta
+
+
+CBS_MAX_SETS, CBS_MAX_WORDS = 3, 4  # constrained beam search: constraints per image, words per constraint (vc_beam_update_constrained)
 
 
 def check_constraints(constraints, B, V, bos, eos, beam_size):

@@ -22,7 +22,7 @@ from . import spec
 from .abi import ptr as P
 from .controls import MAX_BANNED, active as active_controls
 from .decode_host import (CBS_MAX_SETS, CBS_MAX_WORDS, DIVERSE_MAX_DRAWS, SCORE_MAX_TOKENS, FieldLayout, beam_fields, beams_from_host,  # noqa: F401 (re-exported)
-                          check_constraints, check_truncation, diverse_fields, diverse_from_host, marginal_greedy_from_host, merge_groups,
+                          check_constraints, check_truncation, check_typical, diverse_fields, diverse_from_host, marginal_greedy_from_host, merge_groups,
                           rerank_by_marginal, sbs_from_host, sbs_weights, select_bank)
 from .engine import K_CL, _stream
 
@@ -438,11 +438,15 @@ class CaptionGenerator(object):
         return types.SimpleNamespace(seq=self._b(tag + "seq", (rows, max_len), i32), len=self._b(tag + "len", (rows,), i32),
                                      ended=self._b(tag + "ended", (rows,), i32), logprob=self._b(tag + "lp", (rows,), torch.float64))
 
-    def _pick(self, logits, rows, cand, tok, eos, temp=1.0, u=None, u_ld=1, rnd=None, top_k=0, top_p=1.0):
+    def _pick(self, logits, rows, cand, tok, eos, temp=1.0, u=None, u_ld=1, rnd=None, top_k=0, top_p=1.0, typical_p=1.0, min_p=0.0, eta=0.0):
         """A round's pick from its logits [rows, V] into tok and the rows' candidates: the argmax (u None) or the inverse-CDF draw at u
-        [.., u_ld] (row `rnd` of it, a device counter, or row 0) from softmax(logits / temp), truncated to top_k / top_p when asked."""
+        [.., u_ld] (row `rnd` of it, a device counter, or row 0) from softmax(logits / temp), truncated to top_k / top_p or cut by
+        typical_p / min_p / eta when asked (one family: check_typical)."""
         V, c = self.e.V, cand
-        if top_k != 0 or top_p != 1.0:
+        if typical_p != 1.0 or min_p != 0.0 or eta != 0.0:
+            self.lib.vc_decode_pick_typical_f32(_stream(), P(logits), rows, V, V, temp, typical_p, min_p, eta, P(u), u_ld, P(rnd), int(eos), P(tok),
+                                                P(c.ended), P(c.seq), c.seq.shape[1], P(c.len), P(c.logprob), None, None)
+        elif top_k != 0 or top_p != 1.0:
             self.lib.vc_decode_pick_trunc_f32(_stream(), P(logits), rows, V, V, temp, top_k, top_p, P(u), u_ld, P(rnd), int(eos), P(tok), P(c.ended),
                                               P(c.seq), c.seq.shape[1], P(c.len), P(c.logprob), None)
         else:
@@ -524,14 +528,18 @@ class CaptionGenerator(object):
         return self._trim(ids[:steps], eos)
 
     def sample(self, features, c_v=None, eps=None, bos=1, eos=2, max_len=None, uniforms=None, check_every=4, top_k=0, top_p=1.0,
-               controls=None):
+               controls=None, typical_p=1.0, min_p=0.0, eta=0.0):
         """decoder.py:145-201 with sample_gen='sample': tokens drawn from softmax(logits / temperature)
         (tf.multinomial).  uniforms [max_len, B] in [0,1) may be injected; otherwise Philox.
         top_k > 0 / top_p < 1: the draw is truncated to the top_k best words and / or the smallest set of best words holding a share
         top_p of the probability (vc_decode_pick_trunc_f32; DESIGN.md "Truncated sampling"); the defaults leave it as it is.
+        typical_p < 1 / min_p > 0 / eta > 0: the draw is cut to the words whose surprisal is closest to the row's entropy (the smallest such
+        set holding a share typical_p) and / or to the words with p >= max(min_p * p_max, min(eta, sqrt(eta) * exp(-entropy)))
+        (vc_decode_pick_typical_f32; DESIGN.md "Typical / min-p / eta sampling"); not together with top_k / top_p.
         controls: a controls.DecodeControls; the draw is from the softmax of the processed logits (then truncated, if asked).  The
         rows' candidates are then always kept, and an untruncated draw is vc_decode_pick_f32's (vc_multinomial_rows_f32's token)."""
         top_k, top_p = check_truncation(top_k, top_p)
+        typical_p, min_p, eta = check_typical(typical_p, min_p, eta, "sample", top_k, top_p)
         max_len = max_len or self.p.gen_max_len
         ctl = self._checked_controls(controls, eos, max_len)
         c, h = self.init_state(features, c_v, eps)
@@ -541,7 +549,7 @@ class CaptionGenerator(object):
         u = torch.empty((B,), dtype=torch.float32, device=self.e.dev)
         ud = self._dev(uniforms, np.float32) if uniforms is not None else None
         steps = 0
-        trunc = top_k != 0 or top_p != 1.0
+        trunc = top_k != 0 or top_p != 1.0 or typical_p != 1.0 or min_p != 0.0 or eta != 0.0
         if trunc or ctl is not None:   # the pick keeps a candidate per row: scratch here, the ids are what sample() returns
             cand = self._candidates("st_", B, max_len)
             cand.ended.zero_(); cand.len.zero_(); cand.logprob.zero_()
@@ -556,7 +564,7 @@ class CaptionGenerator(object):
                 self.lib.vc_philox_uniform_f32(_stream(), P(u), B, self.e.seed * 1000003 + 29, (16 + it) << 32, P(self.e.step))
             tok = ids[it]
             if trunc or ctl is not None:
-                self._pick(logits, B, cand, tok, eos, float(self.p.temperature), u, 1, None, top_k, top_p)
+                self._pick(logits, B, cand, tok, eos, float(self.p.temperature), u, 1, None, top_k, top_p, typical_p, min_p, eta)
             else:
                 self.lib.vc_multinomial_rows_f32(_stream(), P(logits), B, self.e.V, self.e.V, float(self.p.temperature), P(u), P(tok))
             steps = it + 1
@@ -600,7 +608,7 @@ class CaptionGenerator(object):
         return cs1[1], hs1[1]
 
     def _diverse_pass(self, features, c_v, eps, K, method, bos, eos, max_len, len_norm_f, n_best, uniforms, check_every, rerank="likelihood",
-                      top_k=0, top_p=1.0, ctl=None):
+                      top_k=0, top_p=1.0, ctl=None, typical_p=1.0, min_p=0.0, eta=0.0):
         """One pass of diverse(): the B*K candidate rows of B images decoded together, ranked per image on device (vc_diverse_rank),
         results in two flat buffers brought back by two copies into pinned memory."""
         lib, e, p = self.lib, self.e, self.p
@@ -634,11 +642,13 @@ class CaptionGenerator(object):
             logits, _, _ = self.step(tok, src["c2"], src["h2"], want="logits", bufs=dst, timed=timed)
             if ctl is not None:   # the candidates so far are the histories
                 self._apply_controls(ctl, table, logits, M, cand.seq, max_len, 0, cand.len, cand.ended, eos)
-            self._pick(logits, M, cand, tok, eos, temp, ud, max_len, rnd, top_k, top_p)
+            self._pick(logits, M, cand, tok, eos, temp, ud, max_len, rnd, top_k, top_p, typical_p, min_p, eta)
             lib.vc_decode_round_end_i32(_stream(), P(cand.ended), M, P(pending), P(rnd))
 
         Kc = self._chunk_rounds(check_every)
-        self._run_chunks(("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p) + (ctl.key() if ctl is not None else ()),   # (a captured chunk bakes the truncation and the controls)
+        cuts = (typical_p, min_p, eta)
+        self._run_chunks(("diverse", B, K, Kc, max_len, int(eos), method, temp, top_k, top_p) + (("typical",) + cuts if cuts != (1.0, 0.0, 0.0) else ())
+                         + (ctl.key() if ctl is not None else ()),   # (a captured chunk bakes the truncation, the cuts and the controls)
                          [tok, rnd, pending, ibuf, dbuf, ud] + ([table] if ctl is not None else []) + state, one, reset, Kc, max_len, check_every, pending)
         lib.vc_diverse_rank(_stream(), M, B, K, max_len, P(cand.seq), P(cand.len), P(cand.ended), P(logprob), float(len_norm_f),
                             P(f["n_distinct"]), P(f["rep"]), P(f["count"]), P(score))
@@ -992,7 +1002,7 @@ class CaptionGenerator(object):
         return res
 
     def diverse(self, features, c_v=None, eps=None, bos=1, eos=2, draws=20, method="greedy", n_best=None, max_len=None, len_norm_f=0.7,
-                uniforms=None, check_every=4, rerank="likelihood", top_k=0, top_p=1.0, controls=None):
+                uniforms=None, check_every=4, rerank="likelihood", top_k=0, top_p=1.0, controls=None, typical_p=1.0, min_p=0.0, eta=0.0):
         """Diverse captioning (the AG-CVAE paper's purpose of z): per image `draws` = K independent latent draws, each decoded with
         `greedy` (argmax) or `sample` (inverse CDF at params.temperature) up to and including its first <EOS> (at most max_len tokens),
         log-likelihood = sum of the emitted tokens' log-softmax at temperature 1 (f32 terms, f64 sum), score = logprob / (1 + n)**len_norm_f
@@ -1011,6 +1021,9 @@ class CaptionGenerator(object):
         top_k > 0 / top_p < 1 (method="sample" only): every draw's tokens come from the truncated distribution (the top_k best words and /
         or the smallest set of best words holding a share top_p of the probability; DESIGN.md "Truncated sampling"); log-likelihoods stay
         the model's, over the full vocabulary, so score() of a candidate under its own draw still returns its logprob.
+        typical_p < 1 / min_p > 0 / eta > 0 (method="sample" only, not with top_k / top_p): every draw's tokens come from the words closest
+        in surprisal to the round's entropy and / or above the min-p / eta floor (DESIGN.md "Typical / min-p / eta sampling"); the
+        log-likelihoods stay the model's in the same way.
         controls: a controls.DecodeControls; every draw is decoded from the softmax of its PROCESSED logits and `logprob` is taken
         under it (DESIGN.md "Decoding controls": a penalty has no "model's own" reading); rerank="marginal" still re-scores under the
         unprocessed model.  None or a no-op value: the launches and graph keys of a call without the keyword."""
@@ -1021,6 +1034,7 @@ class CaptionGenerator(object):
         if rerank not in ("likelihood", "marginal"):
             raise ValueError("rerank must be 'likelihood' or 'marginal' (got %r)" % (rerank,))
         top_k, top_p = check_truncation(top_k, top_p, method)
+        typical_p, min_p, eta = check_typical(typical_p, min_p, eta, method, top_k, top_p)
         max_len = int(max_len or self.p.gen_max_len)
         ctl = self._checked_controls(controls, eos, max_len)
         if uniforms is not None and tuple(np.shape(uniforms)) != (K, max_len, B):
@@ -1029,7 +1043,7 @@ class CaptionGenerator(object):
         res, cands = [], []
         for sl in self._marginal_passes(B, K):
             r, c = self._diverse_pass(features[sl], _cut(c_v, sl), _cut(eps, sl, 2), K, method, bos, eos, max_len, len_norm_f, n_best,
-                                      _cut(uniforms, sl, 2), check_every, rerank, top_k, top_p, ctl)
+                                      _cut(uniforms, sl, 2), check_every, rerank, top_k, top_p, ctl, typical_p, min_p, eta)
             res += r
             cands += c
         self.last_candidates = cands

@@ -144,7 +144,7 @@ def store_bounds(params, bound_records, stats):
 
 
 EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
-              "beam_diversity", "top_k", "top_p", "marginal_draws", "constraints", "cbs_width",
+              "beam_diversity", "top_k", "top_p", "typical_p", "min_p", "eta", "marginal_draws", "constraints", "cbs_width",
               "no_repeat_ngram", "min_len", "repetition_penalty", "banned_words")
 
 

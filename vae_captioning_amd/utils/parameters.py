@@ -26,7 +26,7 @@ _DEFAULTS = dict(
     # additive (not in the reference)
     synthetic=False, seed=1234, max_steps=0, captions_json=None, features_pickle=None, cluster_pickle=None, ckpt_format="tf",
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
-    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, eval_captions=False, eval_self_cider=False,
+    score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, typical_p=1.0, min_p=0.0, eta=0.0, eval_captions=False, eval_self_cider=False,
     bound_draws=0, bound_mi=0, marginal_draws=20, constraints=None, cbs_width=0,
     no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
     # training objective options (every one off by default: the reference's objective)
@@ -62,7 +62,8 @@ _FLAGS = [
     ("--diverse_rerank", "diverse_rerank", str, ["likelihood", "consensus", "marginal", "mbr"]), ("--consensus_k", "consensus_k", int, None),
     ("--consensus_m", "consensus_m", int, None), ("--score_draws", "score_draws", int, None),
     ("--beam_size", "beam_size", int, None), ("--beam_groups", "beam_groups", int, None), ("--beam_diversity", "beam_diversity", float, None),
-    ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--eval_captions", "eval_captions", "flag", None),
+    ("--top_k", "top_k", int, None), ("--top_p", "top_p", float, None), ("--typical_p", "typical_p", float, None),
+    ("--min_p", "min_p", float, None), ("--eta_cutoff", "eta", float, None), ("--eval_captions", "eval_captions", "flag", None),
     ("--eval_self_cider", "eval_self_cider", "flag", None),
     ("--bound_draws", "bound_draws", int, None), ("--bound_mi", "bound_mi", int, None), ("--marginal_draws", "marginal_draws", int, None),
     ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
@@ -106,6 +107,14 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--top_k": "--sample_gen sample / --diverse_method sample: draw each word from the k most likely only (>= 0; default 0 = all)",
          "--top_p": "--sample_gen sample / --diverse_method sample: draw each word from the smallest set of most likely words that holds "
                     "this share of the probability (nucleus sampling; in (0, 1]; default 1.0 = all)",
+         "--typical_p": "--sample_gen sample / --diverse_method sample: locally typical sampling -- draw each word from the words whose "
+                        "surprisal is closest to the entropy of the prediction, the smallest such set that holds this share of the "
+                        "probability (in (0, 1]; default 1.0 = all; not with --top_k / --top_p / --scst)",
+         "--min_p": "--sample_gen sample / --diverse_method sample: draw each word from the words at least this fraction as likely as "
+                    "the most likely one (in [0, 1]; default 0 = all; 1 = the most likely word; not with --top_k / --top_p / --scst)",
+         "--eta_cutoff": "--sample_gen sample / --diverse_method sample: eta sampling -- draw each word from the words with probability "
+                         ">= min(eta, sqrt(eta) * exp(-entropy)), a floor that drops when the prediction is uncertain (in [0, 1); "
+                         "default 0 = all; try 3e-4 .. 4e-3; not with --top_k / --top_p / --scst)",
          "--eval_captions": "--mode inference: also evaluate the validation captions against the images' human captions on the GPU (BLEU, "
                             "CIDEr-D, oracle CIDEr-D, ROUGE-L, distinct / novel / Div-1 / Div-2 / mBLEU-4) and write ./val_{gen_name}_metrics.json",
          "--eval_self_cider": "--eval_captions: also report self_cider (Self-CIDEr diversity of each image's caption set, from the "
@@ -261,6 +270,21 @@ class Parameters(object):
             ap.error("--top_k must be >= 0 (got %d)" % self.top_k)
         if not (0.0 < self.top_p <= 1.0):
             ap.error("--top_p must be in (0, 1] (got %r)" % self.top_p)
+        if not (0.0 < self.typical_p <= 1.0):
+            ap.error("--typical_p must be in (0, 1] (got %r)" % self.typical_p)
+        if not (0.0 <= self.min_p <= 1.0):
+            ap.error("--min_p must be in [0, 1] (got %r)" % self.min_p)
+        if not (0.0 <= self.eta < 1.0):
+            ap.error("--eta_cutoff must be in [0, 1) (got %r)" % self.eta)
+        if self.typical_p != 1.0 or self.min_p != 0.0 or self.eta != 0.0:
+            if self.top_k != 0 or self.top_p != 1.0:
+                ap.error("--typical_p / --min_p / --eta_cutoff do not go with --top_k / --top_p: give one family of cuts (their order "
+                         "of renormalisation is not defined)")
+            if self.sample_gen == "diverse" and self.diverse_method != "sample":
+                ap.error("--typical_p / --min_p / --eta_cutoff cut the draw of --diverse_method sample; --diverse_method %s has none"
+                         % self.diverse_method)
+            if self.scst:
+                ap.error("--typical_p / --min_p / --eta_cutoff do not go with --scst: its samples come from the untruncated distribution")
         if not (0.0 <= self.kl_free_bits < float("inf")):
             ap.error("--kl_free_bits must be finite and >= 0 (0 = off; got %r)" % self.kl_free_bits)
         if not (0.0 < self.kl_weight < float("inf")):

@@ -119,13 +119,17 @@ class Decoder(object):
             overrides["beam_size"] = self.params.beam_size
         return getattr(self, name)(sess, picture_ids, in_pictures, placeholder, c_v, **overrides)
 
+    def _cuts(self):
+        """params.typical_p / min_p / eta as sample()'s and diverse()'s keywords (a params object pickled by an older run has none: off)"""
+        return dict(typical_p=getattr(self.params, "typical_p", 1.0), min_p=getattr(self.params, "min_p", 0.0), eta=getattr(self.params, "eta", 0.0))
+
     def online_inference(self, sess, picture_ids, in_pictures, image_f_inputs, stop_word="<EOS>", c_v=None):
         """decoder.py:145-201.  Returns (cap_list, cap_raw)."""
         self.last_token_ids = None
         bos, eos, use_cv = self._call(c_v, stop_word)
         if self.params.sample_gen == "sample":  # tf.multinomial(logits / temperature): same distribution, own Philox stream
             raw = self._gen().sample(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len,
-                                     top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
+                                     top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls, **self._cuts())
         else:
             raw = self._gen().greedy(self._features(in_pictures), use_cv, None, bos, eos, self.params.gen_max_len, controls=self.controls)
         cap_list = [{"image_id": pid, "caption": self._text(toks, (bos, eos))} for pid, toks in zip(picture_ids, raw)]
@@ -149,7 +153,7 @@ class Decoder(object):
     def diverse_inference(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, draws=None, method=None, n_best=None,
                           len_norm_f=0.7):
         """Diverse captioning (the purpose of z in the AG-CVAE paper): `draws` latent draws per image (params.diverse_draws), each decoded
-        with `method` (params.diverse_method: greedy or sample; sample honours params.top_k / params.top_p), identical captions merged and
+        with `method` (params.diverse_method: greedy or sample; sample honours params.top_k / params.top_p or params.typical_p / min_p / eta), identical captions merged and
         ranked (generate.py: diverse).  Returns
         cap_list: per image {"image_id", "caption": the best text, "captions": [texts], "scores": [...], "counts": [...]}.
         params.diverse_rerank == "consensus": every distinct caption is re-ranked by its consensus against the attached
@@ -168,7 +172,7 @@ class Decoder(object):
         feats = self._features(in_pictures)
         res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus or mbr else n_best,
                                   max_len=self.params.gen_max_len, len_norm_f=len_norm_f, rerank="marginal" if marginal else "likelihood",
-                                  top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls)
+                                  top_k=getattr(self.params, "top_k", 0), top_p=getattr(self.params, "top_p", 1.0), controls=self.controls, **self._cuts())
         if consensus:
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
         if mbr:
