@@ -43,9 +43,10 @@ class _ParamsUnpickler(pickle.Unpickler):
 class Generator(object):
     """Generate caption, given the image (gen_caption.py:19)."""
 
-    def __init__(self, checkpoint_path, params_path, vocab_path, gen_method="greedy", vgg_weights=None):
+    def __init__(self, checkpoint_path, params_path, vocab_path, gen_method="greedy", vgg_weights=None, use_ema=False):
         from vae_captioning_amd.utils.captions import Dictionary
         self.checkpoint_path = checkpoint_path
+        self.use_ema = bool(use_ema)   # (additive) caption with the averaged weights a run with --ema_decay wrote
         self.params = self._load_params(params_path)
         self.gen_method = gen_method
         self.vgg_weights = vgg_weights
@@ -94,7 +95,15 @@ class Generator(object):
         p = self.params
         p.sample_gen = self.gen_method                     # gen_caption.py:83
         p.mode, p.fine_tune = "inference", False            # features are fed, as images_ps [None, 4096]
+        p.ema_decay = 0.0                                   # (a training run's pickle may carry it: nothing is averaged here)
         tensors = self._checkpoint_tensors()
+        if self.use_ema:   # every <name>/ExponentialMovingAverage as <name> (Trainer.restore(use_ema=True))
+            from vae_captioning_amd.engine import EMA_SUFFIX, split_averages
+            avg = split_averages(tensors)
+            if not avg:
+                raise KeyError("--use_ema: checkpoint %s holds no averaged weights (<name>%s): it was written without --ema_decay"
+                               % (self.checkpoint_path, EMA_SUFFIX))
+            tensors = dict({k: v for k, v in tensors.items() if not k.endswith(EMA_SUFFIX)}, **avg)
         tr = Trainer(p, p.vocab_size)
         tr.load_state_dict(tensors)
         p._vc_trainer = tr
@@ -197,6 +206,8 @@ if __name__ == "__main__":
     parser.add_argument("--repetition_penalty", type=float, default=1.0, help="the logit of every word already in the caption is divided "
                                                                               "(positive) or multiplied (negative) by this (1..10; 1 = off)")
     parser.add_argument("--must_exclude", default=None, help="words the caption must not hold, e.g. \"a,the\" (vocabulary words or token ids)")
+    parser.add_argument("--use_ema", action="store_true", help="caption with the averaged weights (<name>/ExponentialMovingAverage) that a "
+                                                               "run with --ema_decay wrote into the checkpoint")
     args = parser.parse_args()
     if not 0 <= args.no_repeat_ngram <= 8:
         parser.error("--no_repeat_ngram must be 0..8 (got %d)" % args.no_repeat_ngram)
@@ -226,7 +237,7 @@ if __name__ == "__main__":
     if args.gpu != "":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
-                          gen_method=args.gen_method, vgg_weights=args.vgg_weights)
+                          gen_method=args.gen_method, vgg_weights=args.vgg_weights, use_ema=args.use_ema)
     controls = None
     if controlled:
         from vae_captioning_amd.controls import DecodeControls, parse_banned

@@ -369,6 +369,8 @@ int vc_tile_rows_f32(void* stream, const float* x, long B, int nc, int E, float*
 int vc_segment_sum_rows_f32(void* stream, const float* y, long B, int nc, int E, float* x, int accumulate);
 int vc_exp_f32(void* stream, const float* x, long n, float* y);
 int vc_axpy_f32(void* stream, float a, const float* x, long n, float* y);
+/* a <-> b in place over n floats (16-byte aligned, not overlapping; n == 0 returns 0). */
+int vc_swap_f32(void* stream, float* a, float* b, long n);
 int vc_reduce_sum_f32(void* stream, const float* x, long n, float scale, float* out, int accumulate);
 int vc_count_nonzero_i32(void* stream, const int32_t* x, long n, float* out);
 
@@ -399,6 +401,17 @@ int vc_adam_f32(void* stream, float* p, const float* g, float* m, float* v, long
 int vc_adam_blocks(long n);
 int vc_adam_sumsq_f32(void* stream, float* p, const float* g, float* m, float* v, long n, const float* lr_t, const float* scale,
                       float beta1, float beta2, float eps, float l2, float* sumsq_partial);
+/* Weight averaging (DESIGN.md "Weight averaging"): ema += w * (p_new - ema), w = max(omd, 9 / (10 + step[0])) -- the num_updates warm-up
+ * of tf.train.ExponentialMovingAverage, step[0] = the device counter behind vc_step_update = updates including this one -- or w = omd
+ * with step NULL.  omd = 1 - decay in (0, 1], computed by the caller in double.  vc_adam_ema_f32 / vc_adam_sumsq_ema_f32: the Adam
+ * entries above with the average folded into the same pass (p, m, v and the sums equal theirs bit for bit; 36 B per parameter instead
+ * of 28 + 12).  vc_ema_update_f32: the average alone, behind any other update; the same bits as the fused form.  Buffers 16-byte
+ * aligned; ema must not overlap p, m or v; n == 0 returns 0 (the sumsq form needs n > 0 like vc_adam_sumsq_f32). */
+int vc_adam_ema_f32(void* stream, float* p, const float* g, float* m, float* v, float* ema, long n, const float* lr_t, const float* scale,
+                    float beta1, float beta2, float eps, float l2, float omd, const int32_t* step);
+int vc_adam_sumsq_ema_f32(void* stream, float* p, const float* g, float* m, float* v, float* ema, long n, const float* lr_t, const float* scale,
+                          float beta1, float beta2, float eps, float l2, float omd, const int32_t* step, float* sumsq_partial);
+int vc_ema_update_f32(void* stream, float* ema, const float* p, long n, float omd, const int32_t* step);
 int vc_sgd_f32(void* stream, float* p, const float* g, long n, const float* lr, const float* scale, float l2);
 int vc_momentum_f32(void* stream, float* p, const float* g, float* accum, long n, const float* lr, const float* scale,
                     float momentum, float l2, const float* row_mask, int E);

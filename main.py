@@ -204,7 +204,7 @@ def main(params):
         if not os.path.exists(have):  # saver.restore raises NotFoundError (main.py:209-212, ops/inference.py:6-7)
             raise FileNotFoundError("checkpoint %s not found (--restore / --mode inference need ./checkpoints/%s.ckpt*)" % (have, params.checkpoint))
         print("Restoring from checkpoint")
-        tr.restore(ckpt)
+        tr.restore(ckpt, use_ema=bool(params.use_ema))   # --use_ema: the averaged weights in place of the last iterate
     steps_per_epoch = params.max_steps or (params.num_ex_per_epoch // (params.batch_size * world) + 1)  # main.py:217-221, global batch
     say = print if rank == 0 else (lambda *a, **k: None)
 
@@ -216,6 +216,9 @@ def main(params):
         optimize_cnn = (lambda: 0.0)
         if params.fine_tune:
             optimize_cnn, _ = optimizers.cnn_optimizer(None, params)
+        if params.ema_decay > 0:   # --ema_decay: averaged inside the optimiser pass, validated and saved beside the last iterate
+            say("Weight averaging: decay {} ({}), averages of {} variables".format(
+                params.ema_decay, "with warm-up" if cap.ema_warmup else "constant", sum(len(e.store.names()) for e in tr._ema_engines())))
         gs = 0  # host mirror of global_step (it restarts at 0 on --restore, Q11): no device sync on non-print steps
         # --word_drop: decoder input words replaced by <UNK> on the host, before the upload (the embedding-gradient index is built from
         # the replaced ids; nothing on the device changes); training batches only
@@ -332,6 +335,16 @@ def main(params):
                 tr.set_batch(batch)
                 val.append(tr.eval_rec_loss())
             say("Validation reconstruction loss: {}".format(np.mean(val)))
+            if params.ema_decay > 0:   # the same loop over the same held-out batches on the averaged weights
+                val = []
+                held_out = coco_batches(coco_val, params) if coco_val is not None else SyntheticBatches(params, 4, params.seed + 99991 + rank).next_batch()
+                with tr.ema_weights():
+                    for batch in held_out:
+                        if batch["cap_dec"].shape[0] != params.batch_size * params.num_captions:
+                            continue
+                        tr.set_batch(batch)
+                        val.append(tr.eval_rec_loss())
+                say("Validation reconstruction loss (averaged weights, decay {}): {}".format(params.ema_decay, np.mean(val)))
             say("-----------------------------------------------")
             if rank == 0:
                 os.makedirs("./checkpoints", exist_ok=True)

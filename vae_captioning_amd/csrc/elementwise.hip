@@ -639,6 +639,23 @@ __global__ __launch_bounds__(256) void fill_kernel(float* __restrict__ x, long n
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] = v;
 }
 
+// a <-> b in place (Trainer.ema_weights: the parameters and their averages change places without a temporary of the store's size)
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    const long n4 = n >> 2;
+    float4* a4 = reinterpret_cast<float4*>(a);
+    float4* b4 = reinterpret_cast<float4*>(b);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const float x = a[i];
+        a[i] = b[i];
+        b[i] = x;
+    }
+}
+
 }  // namespace vc
 
 using namespace vc;
@@ -846,6 +863,16 @@ extern "C" int vc_exp_f32(void* stream, const float* x, long n, float* y) {
     VC_CHECK_ARG(x && y && n >= 0, "bad argument");
     if (n == 0) return 0;
     hipLaunchKernelGGL(exp_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, n, y);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_swap_f32(void* stream, float* a, float* b, long n) {
+    VC_CHECK_ARG(a && b && n >= 0, "bad argument (null pointer or n < 0)");
+    VC_CHECK_ARG((((uintptr_t)a | (uintptr_t)b) & 15) == 0, "buffers must be 16-byte aligned");
+    VC_CHECK_ARG(!((uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n)), "a must not alias b");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(swap_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, n);
     VC_LAUNCH_CHECK();
     return 0;
 }

@@ -3,7 +3,8 @@
 // replayed without host-side argument changes), and the Philox4x32-10 generator that
 // replaces TF's random_normal / dropout streams.
 //
-// HBM-bound: Adam touches 4 reads + 3 writes x 4 B = 28 B per parameter.
+// HBM-bound: Adam touches 4 reads + 3 writes x 4 B = 28 B per parameter; with the parameter average folded in (EMA) one more
+// stream is read and written: 36 B.  A stand-alone averaging pass behind the update moves 12 B of its own (40 B for the pair).
 #include "common.h"
 #include <stdlib.h>
 #include "vaecap.h"
@@ -85,18 +86,37 @@ __global__ void cyclical_ann_kernel(const int32_t* step, float* s, int period, f
     s[1] = a;
 }
 
+// Exponential moving average of the parameters (tf.train.ExponentialMovingAverage with num_updates): the weight of the new value is
+//   w = max(1 - decay, 9 / (10 + t))      [= 1 - min(decay, (1 + t) / (10 + t))],  t = step[0] = updates including this one
+// (step_update_kernel has already incremented the counter when an optimiser runs), or 1 - decay with a null step.  The host passes
+// omd = 1 - decay computed in double: 1.f - 0.9999f is off by 1.7e-4 relative.  Read from the device counter, so a captured step replays.
+__device__ __forceinline__ float ema_weight(float omd, const int32_t* __restrict__ step) {
+    return step ? fmaxf(omd, 9.f / (10.f + (float)step[0])) : omd;
+}
+// e += w * (p_new - e) with an explicit fma: every kernel that applies it (adam_kernel<., true>, ema_kernel) produces the same bits
+__device__ __forceinline__ float ema_apply(float w, float p_new, float e) { return fmaf(w, p_new - e, e); }
+__device__ __forceinline__ void ema_apply4(float w, const float4& p, float4& e) {
+    e.x = ema_apply(w, p.x, e.x); e.y = ema_apply(w, p.y, e.y);
+    e.z = ema_apply(w, p.z, e.z); e.w = ema_apply(w, p.w, e.w);
+}
+
 // tf.train.AdamOptimizer.apply_gradients (ops/optimizers.py:37-40,72-75; TF-sem.):
 //   g' = g*scale (+ l2*p);  m = b1*m + (1-b1)*g';  v = b2*v + (1-b2)*g'^2;  p -= lr_t*m/(sqrt(v)+eps)
 // SUMSQ: also leaves sum(p_new^2) of the block in sumsq_partial[blockIdx.x] -- the regulariser's loss term of the NEXT step
 // (main.py:69-74 sums w^2 over the cnn/* variables) without another 0.5 GB pass over the parameters.
-template <bool SUMSQ>
+// EMA: also folds the new parameters into their moving average `ema` (ema_apply above): one more float4 stream, read and written, in
+// each of the three loops; p, m, v and the sums are those of the EMA = false instantiation to the bit (the same `upd` on the same data).
+template <bool SUMSQ, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long n, const float* __restrict__ lr_t,
                                                    const float* __restrict__ scale, float beta1, float beta2, float eps,
-                                                   float l2, float* __restrict__ sumsq_partial) {
+                                                   float l2, float* __restrict__ sumsq_partial, float* __restrict__ ema, float omd,
+                                                   const int32_t* __restrict__ step) {
     __shared__ float sh[4];
     float s2 = 0.f;
     const float lr = lr_t[0];
+    const float w = EMA ? ema_weight(omd, step) : 0.f;
+    float4* e4 = reinterpret_cast<float4*>(ema);
     const float sc = scale ? scale[0] : 1.f;
     const long n4 = n >> 2;
     float4* p4 = reinterpret_cast<float4*>(p);
@@ -119,25 +139,57 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         const float4 ga = g4[i];
         float4 pb = p4[j], mb = m4[j], vb = v4[j];
         const float4 gb = g4[j];
+        float4 ea, eb;
+        if (EMA) { ea = e4[i]; eb = e4[j]; }
         upd(pa.x, ga.x, ma.x, va.x); upd(pa.y, ga.y, ma.y, va.y);
         upd(pa.z, ga.z, ma.z, va.z); upd(pa.w, ga.w, ma.w, va.w);
         upd(pb.x, gb.x, mb.x, vb.x); upd(pb.y, gb.y, mb.y, vb.y);
         upd(pb.z, gb.z, mb.z, vb.z); upd(pb.w, gb.w, mb.w, vb.w);
         p4[i] = pa; m4[i] = ma; v4[i] = va;
         p4[j] = pb; m4[j] = mb; v4[j] = vb;
+        if (EMA) {
+            ema_apply4(w, pa, ea); ema_apply4(w, pb, eb);
+            e4[i] = ea; e4[j] = eb;
+        }
     }
     if (i < n4) {
         float4 pp = p4[i], mm = m4[i], vv = v4[i];
         const float4 gg = g4[i];
+        float4 ee;
+        if (EMA) ee = e4[i];
         upd(pp.x, gg.x, mm.x, vv.x); upd(pp.y, gg.y, mm.y, vv.y);
         upd(pp.z, gg.z, mm.z, vv.z); upd(pp.w, gg.w, mm.w, vv.w);
         p4[i] = pp; m4[i] = mm; v4[i] = vv;
+        if (EMA) {
+            ema_apply4(w, pp, ee);
+            e4[i] = ee;
+        }
     }
-    for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) upd(p[i], g[i], m[i], v[i]);
+    for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        upd(p[i], g[i], m[i], v[i]);
+        if (EMA) ema[i] = ema_apply(w, p[i], ema[i]);
+    }
     if (SUMSQ) {
         s2 = block_sum<256>(s2, sh);
         if (threadIdx.x == 0) sumsq_partial[blockIdx.x] = s2;
     }
+}
+
+// The average as a pass of its own (SGD / Momentum, whose update kernels are not fused with it; the A/B partner of adam_kernel<., true>):
+// 2 reads + 1 write x 4 B = 12 B per parameter.
+__global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long n, float omd,
+                                                  const int32_t* __restrict__ step) {
+    const float w = ema_weight(omd, step);
+    const long n4 = n >> 2;
+    float4* e4 = reinterpret_cast<float4*>(ema);
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 pp = p4[i];
+        float4 ee = e4[i];
+        ema_apply4(w, pp, ee);
+        e4[i] = ee;
+    }
+    for (long i = (n4 << 2) + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) ema[i] = ema_apply(w, p[i], ema[i]);
 }
 
 // GradientDescentOptimizer: p -= lr * (g*scale + l2*p)
@@ -240,7 +292,7 @@ extern "C" int vc_adam_f32(void* stream, float* p, const float* g, float* m, flo
     VC_CHECK_ARG(p && g && m && v && lr_t && n >= 0, "bad argument");
     VC_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "buffers must be 16-byte aligned");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_t, scale, beta1, beta2, eps, l2, nullptr);
+    hipLaunchKernelGGL((adam_kernel<false, false>), dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_t, scale, beta1, beta2, eps, l2, nullptr, nullptr, 0.f, nullptr);
     VC_LAUNCH_CHECK();
     return 0;
 }
@@ -251,7 +303,47 @@ extern "C" int vc_adam_sumsq_f32(void* stream, float* p, const float* g, float* 
                                  const float* scale, float beta1, float beta2, float eps, float l2, float* sumsq_partial) {
     VC_CHECK_ARG(p && g && m && v && lr_t && sumsq_partial && n > 0, "bad argument");
     VC_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_t, scale, beta1, beta2, eps, l2, sumsq_partial);
+    hipLaunchKernelGGL((adam_kernel<true, false>), dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_t, scale, beta1, beta2, eps, l2, sumsq_partial, nullptr, 0.f, nullptr);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+// [a, a + n) and [b, b + n) share an element
+static inline bool ranges_overlap(const float* a, const float* b, long n) {
+    return (uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n);
+}
+
+extern "C" int vc_adam_ema_f32(void* stream, float* p, const float* g, float* m, float* v, float* ema, long n, const float* lr_t,
+                               const float* scale, float beta1, float beta2, float eps, float l2, float omd, const int32_t* step) {
+    VC_CHECK_ARG(p && g && m && v && ema && lr_t && n >= 0, "bad argument (null pointer or n < 0)");
+    VC_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0, "buffers must be 16-byte aligned");
+    VC_CHECK_ARG(omd > 0.f && omd <= 1.f, "omd = 1 - decay must be in (0, 1]");
+    VC_CHECK_ARG(!ranges_overlap(ema, p, n) && !ranges_overlap(ema, m, n) && !ranges_overlap(ema, v, n), "ema must not alias p, m or v");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL((adam_kernel<false, true>), dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_t, scale, beta1, beta2, eps, l2, nullptr, ema, omd, step);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_adam_sumsq_ema_f32(void* stream, float* p, const float* g, float* m, float* v, float* ema, long n, const float* lr_t,
+                                     const float* scale, float beta1, float beta2, float eps, float l2, float omd, const int32_t* step,
+                                     float* sumsq_partial) {
+    VC_CHECK_ARG(p && g && m && v && ema && lr_t && sumsq_partial && n > 0, "bad argument (null pointer or n <= 0)");
+    VC_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0, "buffers must be 16-byte aligned");
+    VC_CHECK_ARG(omd > 0.f && omd <= 1.f, "omd = 1 - decay must be in (0, 1]");
+    VC_CHECK_ARG(!ranges_overlap(ema, p, n) && !ranges_overlap(ema, m, n) && !ranges_overlap(ema, v, n), "ema must not alias p, m or v");
+    hipLaunchKernelGGL((adam_kernel<true, true>), dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr_t, scale, beta1, beta2, eps, l2, sumsq_partial, ema, omd, step);
+    VC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vc_ema_update_f32(void* stream, float* ema, const float* p, long n, float omd, const int32_t* step) {
+    VC_CHECK_ARG(ema && p && n >= 0, "bad argument (null pointer or n < 0)");
+    VC_CHECK_ARG((((uintptr_t)ema | (uintptr_t)p) & 15) == 0, "buffers must be 16-byte aligned");
+    VC_CHECK_ARG(omd > 0.f && omd <= 1.f, "omd = 1 - decay must be in (0, 1]");
+    VC_CHECK_ARG(!ranges_overlap(ema, p, n), "ema must not alias p");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(ema_kernel, dim3(adam_grid(n)), dim3(256), 0, (hipStream_t)stream, ema, p, n, omd, step);
     VC_LAUNCH_CHECK();
     return 0;
 }

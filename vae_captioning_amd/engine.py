@@ -129,6 +129,28 @@ class FlatStore(object):
     def names(self):
         return [n for n, _ in self.entries]
 
+    def average(self, name):
+        """The view of `name` in the slot "ema" (weight averaging)."""
+        return self._view(self.slots["ema"], name)
+
+
+# Weight averaging (DESIGN.md "Weight averaging"): what a checkpoint calls the moving average of variable <name> -- TensorFlow's own
+# naming (tf.train.ExponentialMovingAverage.average_name), so that variables_to_restore() would map it
+EMA_SUFFIX = "/ExponentialMovingAverage"
+
+
+def ema_omd(decay):
+    """(decay checked, 1 - decay) -- the kernels take 1 - decay, computed here in double: 1.f - 0.9999f is off by 1.7e-4 relative."""
+    decay = float(decay)
+    if not (0.0 <= decay < 1.0):
+        raise ValueError("ema_decay must be in [0, 1) (0 = off; got %r)" % (decay,))
+    return decay, 1.0 - decay
+
+
+def split_averages(named):
+    """{name: array} of the <name>/ExponentialMovingAverage entries of a loaded dict."""
+    return {k[:-len(EMA_SUFFIX)]: v for k, v in named.items() if k.endswith(EMA_SUFFIX)}
+
 
 def internal_caption_variables(p, vocab):
     """spec.caption_variables with (a) the 360 head tensors fused into two and (b) the
@@ -261,6 +283,15 @@ class CaptionEngine(object):
             # before the head lacks bow/*
             k0 = spec._glorot(np.random.default_rng([int(seed), 0xB0]), (p.embed_size, self.V))
             self.store.param(spec.BOW_KERNEL)[:, :self.V].copy_(torch.from_numpy(k0))
+        # Weight averaging (DESIGN.md "Weight averaging"): decay > 0 = the store has a slot "ema" that apply_gradients folds the new
+        # parameters into (Adam: inside the update's own pass, vc_adam_ema_f32; SGD / Momentum: vc_ema_update_f32 behind it).  0 = off:
+        # no slot, none of these entries resolved, every launch as before.  ema_warmup: the averages were initialised from the
+        # parameters in this process, so the kernels take the num_updates warm-up from the device step counter; False = they came
+        # from a checkpoint (constant decay: the counter restarts at 0 on --restore, Q11, and a restarted warm-up would forget them)
+        self.ema_decay, self.ema_omd = ema_omd(getattr(p, "ema_decay", 0.0))
+        self.ema_warmup = True
+        if self.ema_decay > 0:
+            self.store.slot("ema").copy_(self.store.p)
         self._den_early = False               # the label count of this forward is already in red[1] (fw_bow needs it in front of fw_loss)
         # Self-critical training (DESIGN.md "Self-critical training"): True while a policy step prepares its forward -- z is GIVEN (no eps,
         # no GMM draw); everything else off = the training step as it was
@@ -327,6 +358,22 @@ class CaptionEngine(object):
         if missing:  # tf.train.Saver.restore raises NotFoundError for the same situation
             raise KeyError("checkpoint lacks %d variable(s) of this model (prior=%s, no_encoder=%s, c_v=%s), e.g. %s -- was it saved "
                            "with different options?" % (len(missing), p.prior, p.no_encoder, p.use_c_v, missing[0]))
+        self._load_into(self.store.param, named, keep)
+        if self.ema_decay > 0:
+            # the averages start from the parameters (warm-up on) unless the dict carries them: then they go through the same
+            # mapping (fused heads, padded vocabulary columns), and a head that kept its fresh initialisation averages from there
+            self.store.slot("ema").copy_(self.store.p)
+            avg = {k: v for k, v in split_averages(named).items() if not k.startswith("cnn/")}
+            lacking = [n for n in need if n not in avg and n not in keep]
+            if avg and lacking:
+                raise KeyError("checkpoint carries averaged weights but lacks %d of them, e.g. %s%s" % (len(lacking), lacking[0], EMA_SUFFIX))
+            self.ema_warmup = not avg
+            if avg:
+                self._load_into(self.store.average, avg, keep)
+
+    def _load_into(self, view, named, keep):
+        """named (reference variable names) -> the views view(name) of the store's own layout; the names in `keep` stay as they are."""
+        p = self.p
         for name in self.store.names():
             if name == "encoder/heads/kernel":
                 ks = [named[spec.head_scope(p.prior, k) + "dense/kernel"] for k in range(K_CL)]
@@ -342,10 +389,15 @@ class CaptionEngine(object):
                 arr = named[name]
             if name.startswith(("decoder/rnn_logits/", "bow/")) and np.shape(arr)[-1] == self.V != self.Vp:  # zero-pad the vocabulary columns
                 arr = np.concatenate([arr, np.zeros(np.shape(arr)[:-1] + (self.Vp - self.V,), np.float32)], axis=-1)
-            dst = self.store.param(name)
+            dst = view(name)
             if tuple(np.shape(arr)) != tuple(dst.shape):
                 raise ValueError("%s: checkpoint shape %s, model shape %s" % (name, tuple(np.shape(arr)), tuple(dst.shape)))
             dst.copy_(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)))
+
+    def averages_dict(self):
+        """The moving averages under the reference's variable names (the mapping of state_dict); needs ema_decay > 0."""
+        torch.cuda.synchronize()
+        return self._export(self.store.average)
 
     def _export(self, getter):
         p = self.p
@@ -1239,6 +1291,8 @@ class CaptionEngine(object):
         term of dec_embeddings, Q5) and the optimiser on those ranges of the flat store alone -- tf.train.Optimizer skips a variable
         whose gradient is None, so the parameters and the slots of encoder/* stay as they are, bit for bit."""
         p, lib, st, S, nb = self.p, self.lib, _stream(), self.store, self.nb
+        if self.ema_decay > 0:
+            raise RuntimeError("weight averaging (ema_decay > 0) is not built for the policy step, which updates ranges of the store only")
         self.param_updates += 1
         (lo, n), (eo, en) = self.policy_ranges()
         at = lambda t, o: t.data_ptr() + o * 4
@@ -1294,7 +1348,14 @@ class CaptionEngine(object):
         self.part[nb:nb + 1].copy_(S.g[S.n:S.n + 1])
         lib.vc_clip_finalize_f32(st, P(self.part), nb + 1, float(p.lstm_clip_by_norm), P(self.ns))
         scale = self.ns.data_ptr() + 4
-        if p.optimizer == "Adam":
+        ema = self.ema_decay > 0
+        if ema:
+            e_args = (self.ema_omd, P(self.step) if self.ema_warmup else None)
+        if p.optimizer == "Adam" and ema:
+            self._timed("hbm_adam", 36.0 * S.n,  # p, g, m, v, ema read; p, m, v, ema written
+                        lambda: lib.vc_adam_ema_f32(st, P(S.p), P(S.g), P(S.slot("m")), P(S.slot("v")), P(S.slot("ema")), S.n, P(self.scal), scale,
+                                                    0.8, 0.999, 1e-8, 0.0, *e_args))
+        elif p.optimizer == "Adam":
             self._timed("hbm_adam", 28.0 * S.n,  # p, g, m, v read; p, m, v written
                         lambda: lib.vc_adam_f32(st, P(S.p), P(S.g), P(S.slot("m")), P(S.slot("v")), S.n, P(self.scal), scale, 0.8, 0.999, 1e-8, 0.0))
         elif p.optimizer == "SGD":
@@ -1312,6 +1373,8 @@ class CaptionEngine(object):
                 n = shape[0] * shape[1]
                 lib.vc_momentum_f32(st, S.p.data_ptr() + off * 4, S.g.data_ptr() + off * 4, a.data_ptr() + off * 4, n, lr, scale, 0.9, 0.0,
                                     P(touched), shape[1])
+        if ema and p.optimizer != "Adam":   # once over the whole store, behind the dense and the sparse-row launches
+            lib.vc_ema_update_f32(st, P(S.slot("ema")), P(S.p), S.n, *e_args)
 
     def losses(self):
         """(kld, rec_loss, lower_bound, annealing) as Python floats -- the fetches of main.py:241-244."""

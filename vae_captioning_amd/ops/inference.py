@@ -159,6 +159,8 @@ def store_metrics(params, metrics, images, captions):
     out.update({k: getattr(params, k) for k in EVAL_FLAGS if hasattr(params, k)})
     if len(names) > len(METRICS):
         out["eval_self_cider"] = True
+    if getattr(params, "use_ema", False):   # --use_ema: the captions come from the averaged weights
+        out["use_ema"] = True
     path = "./val_{}_metrics.json".format(params.gen_name)
     if os.path.exists(path):
         os.remove(path)

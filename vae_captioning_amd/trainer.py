@@ -6,6 +6,7 @@ the single flat gradient buffer (caption-side grads | reduction scalars | VGG gr
 plus a 4-byte all-reduce of the non-PAD token count that the CE gradient scale needs
 before backward (main.py:156-157 divides by the GLOBAL count).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -13,7 +14,7 @@ import torch
 
 from . import abi, spec
 from .abi import ptr as P
-from .engine import TAIL, CaptionEngine, FlatStore, _stream, internal_caption_variables, _round
+from .engine import EMA_SUFFIX, TAIL, CaptionEngine, FlatStore, _stream, ema_omd, internal_caption_variables, split_averages, _round
 from .vgg_plan import WINO, conv_plan
 
 
@@ -118,6 +119,13 @@ class VggEngine(object):
         self.w2_valid = False
         self.w2_cache = True     # False: always recompute sum(w^2) (a captured step: parameters restored behind the graph's back would go unnoticed)
         self._w2_version = -1
+        # Weight averaging (CaptionEngine.ema_decay): only a VGG16 that is trained has averages.  `step` is the device step counter
+        # the warm-up reads (the caption engine's: the Trainer hands it over); ema_warmup as CaptionEngine.ema_warmup.
+        self.ema_decay, self.ema_omd = ema_omd(getattr(p, "ema_decay", 0.0) if self.train else 0.0)
+        self.ema_warmup = True
+        self.step = None
+        if self.ema_decay > 0:
+            self.store.slot("ema").copy_(self.store.p)
 
     @property
     def side(self):
@@ -264,8 +272,20 @@ class VggEngine(object):
         if missing:  # tf.train.Saver.restore raises NotFoundError for the same situation
             raise KeyError("checkpoint lacks %d cnn/* variable(s), e.g. %s -- it was written without the VGG16 variables" % (len(missing), missing[0]))
         self.w2_valid = False
+        self._load_into(self.store.param, named)
+        if self.ema_decay > 0:   # the averages start from the parameters (warm-up on) unless the dict carries them
+            self.store.slot("ema").copy_(self.store.p)
+            avg = {k: v for k, v in split_averages(named).items() if k.startswith("cnn/")}
+            lacking = [n for n in self.store.names() if n not in avg]
+            if avg and lacking:
+                raise KeyError("checkpoint carries averaged cnn/* weights but lacks %d of them, e.g. %s%s" % (len(lacking), lacking[0], EMA_SUFFIX))
+            self.ema_warmup = not avg
+            if avg:
+                self._load_into(self.store.average, avg)
+
+    def _load_into(self, view, named):
         for name in self.store.names():
-            dst = self.store.param(name)
+            dst = view(name)
             if tuple(np.shape(named[name])) != tuple(dst.shape):
                 raise ValueError("%s: checkpoint shape %s, model shape %s" % (name, tuple(np.shape(named[name])), tuple(dst.shape)))
             dst.copy_(torch.from_numpy(np.ascontiguousarray(named[name], dtype=np.float32)))
@@ -275,10 +295,18 @@ class VggEngine(object):
         self.w2_valid = False
         for name, arr in imagenet_weights(weight_file).items():
             self.store.param(name).copy_(torch.from_numpy(arr))
+        if self.ema_decay > 0:
+            self.store.slot("ema").copy_(self.store.p)
+            self.ema_warmup = True
 
     def state_dict(self):
         torch.cuda.synchronize()
         return {n: self.store.param(n).detach().cpu().numpy().copy() for n in self.store.names()}
+
+    def averages_dict(self):
+        """The moving averages of the cnn/* variables by name; needs ema_decay > 0."""
+        torch.cuda.synchronize()
+        return {n: self.store.average(n).detach().cpu().numpy().copy() for n in self.store.names()}
 
     def grads_dict(self):
         torch.cuda.synchronize()
@@ -542,11 +570,25 @@ class VggEngine(object):
         final as soon as the fc backward has run: the caller may update them on another stream under the convolution backward);
         "conv" = the convolution layers only.  The update is elementwise, so the two halves equal the whole."""
         p, lib, st, S = self.p, self.lib, _stream(), self.store
+        ema = self.ema_decay > 0
+        if ema:
+            if self.ema_warmup and self.step is None:
+                raise RuntimeError("weight averaging with its warm-up reads the device step counter: set VggEngine.step (the Trainer does)")
+            e_args = (self.ema_omd, P(self.step) if self.ema_warmup else None)
         for which, lo, n, w2o in (("conv", 0, self.o_fc, 0), ("fc", self.o_fc, S.n - self.o_fc, self.w2_blocks[0])):
             if part is not None and part != which:
                 continue
             sl = lambda t: t.data_ptr() + lo * 4
-            if p.cnn_optimizer == "Adam" and self.wd:
+            if p.cnn_optimizer == "Adam" and ema:   # the average of this part's range [lo, lo + n) inside the update's own pass
+                if self.wd:
+                    self._timed("hbm_adam", 36.0 * n, lambda: lib.vc_adam_sumsq_ema_f32(
+                        st, sl(S.p), sl(S.g), sl(S.slot("m")), sl(S.slot("v")), sl(S.slot("ema")), n, scal.data_ptr() + 12, None, 0.8, 0.999, 1e-8,
+                        self.wd, *e_args, self.w2_part.data_ptr() + w2o * 4))
+                else:
+                    self._timed("hbm_adam", 36.0 * n, lambda: lib.vc_adam_ema_f32(
+                        st, sl(S.p), sl(S.g), sl(S.slot("m")), sl(S.slot("v")), sl(S.slot("ema")), n, scal.data_ptr() + 12, None, 0.8, 0.999, 1e-8,
+                        self.wd, *e_args))
+            elif p.cnn_optimizer == "Adam" and self.wd:
                 self._timed("hbm_adam", 28.0 * n, lambda: lib.vc_adam_sumsq_f32(
                     st, sl(S.p), sl(S.g), sl(S.slot("m")), sl(S.slot("v")), n, scal.data_ptr() + 12, None, 0.8, 0.999, 1e-8, self.wd,
                     self.w2_part.data_ptr() + w2o * 4))
@@ -557,6 +599,8 @@ class VggEngine(object):
                 lib.vc_sgd_f32(st, sl(S.p), sl(S.g), n, scal.data_ptr() + 16, None, self.wd)
             else:
                 lib.vc_momentum_f32(st, sl(S.p), sl(S.g), sl(S.slot("a")), n, scal.data_ptr() + 16, None, 0.9, self.wd, None, 0)
+            if ema and p.cnn_optimizer != "Adam":
+                lib.vc_ema_update_f32(st, sl(S.slot("ema")), sl(S.p), n, *e_args)
         # (every block of both halves has written its sum by the time the next forward pass reads them, whatever the order)
         self.w2_valid = p.cnn_optimizer == "Adam" and bool(self.wd)
         self._w2_version = self.store.p._version
@@ -606,6 +650,7 @@ class Trainer(object):
         if self.fine:
             self.vgg = VggEngine(p, device, self.lib, grad_backing=self.gall[n_cap:], seed=seed, rank=rank)
             self.vgg.precision = self.precision
+            self.vgg.step = self.cap.step   # (weight averaging: the warm-up of the cnn/* averages reads the one step counter)
             self.vgg.pool_store_y = os.environ.get("VC_POOL_STORE_Y", "0") == "1"   # (VggEngine.pool_store_y; 1: A/B runs, checkers that read y_<name>)
             self.vgg.wino4v_f32 = "fwd"   # (VggEngine.wino4v_f32: the f32 forward of conv4_x / conv5_x on the once-transformed input)
             if self.vgg.wd:
@@ -615,6 +660,8 @@ class Trainer(object):
         self.dp_stats = None  # list: per-bucket (index, bytes, event before wait, event after wait) when bench.py asks for it
         self.cnn_host = None  # {cnn/* name: array} written into checkpoints when VGG16 is not on device (state_dict)
         self.n_cap = n_cap
+        self.ema_decay = self.cap.ema_decay   # weight averaging (DESIGN.md "Weight averaging"); 0 = off
+        self._ema_swapped = False             # inside `with self.ema_weights()`
         # Data-parallel gradient exchange.  Logically ONE sum-all-reduce of `gall` per step; with VGG
         # fine-tuning it is issued as four asynchronous pieces in the order the gradients become final
         # (caption side | fc1+fc2, 478 MB | conv3_1..conv5_3, 58 MB | conv1_1..conv2_2, 1 MB) so that RCCL
@@ -824,6 +871,8 @@ class Trainer(object):
             self.cap.reduce_fn(self.gall)  # the single gradient all-reduce (RCCL over xGMI)
 
     def train_step(self):
+        if self._ema_swapped:
+            raise RuntimeError("no training step inside ema_weights(): the parameters and their averages have changed places")
         if self.graph is not None:
             self.graph.replay()
             self.cap.param_updates += 1   # the replayed optimiser kernels rewrote the parameters (CaptionEngine.param_version)
@@ -840,6 +889,8 @@ class Trainer(object):
         p = self.p
         if self.fine:
             raise RuntimeError("self-critical training does not train the VGG16: not with --fine_tune")
+        if self.ema_decay > 0:
+            raise RuntimeError("self-critical training updates ranges of the store only: not with --ema_decay")
         if self.collectives:
             raise RuntimeError("self-critical training is single-GPU: not in a data-parallel run")
         if p.mode != "training":
@@ -996,11 +1047,68 @@ class Trainer(object):
             d.update(self.vgg.state_dict())
         elif self.cnn_host is not None:
             d.update(self.cnn_host)
+        # weight averaging: <name>/ExponentialMovingAverage beside every TRAINED variable (the cnn_host constants have none)
+        for eng in self._ema_engines():
+            d.update({k + EMA_SUFFIX: v for k, v in eng.averages_dict().items()})
         return d
 
+    # ------------------------------------------------------------------ weight averaging (DESIGN.md "Weight averaging")
+    def _ema_engines(self):
+        """The engines whose store has the slot "ema": the caption side with ema_decay > 0, and the VGG16 when it is trained as well."""
+        return [e for e in (self.cap, self.vgg) if e is not None and e.ema_decay > 0]
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model IS its moving average: parameters and averages of every averaged store change places in place
+        (vc_swap_f32: no temporary of the VGG16's size) and change back on exit, so eval_rec_loss(), a CaptionGenerator on the engine
+        and everything else that reads the parameters run on the averaged weights.  Both transitions are made visible to the caches
+        that key on parameter identity (CaptionEngine.param_version, the VGG16's sum-of-squares cache).  Not nestable; no training step
+        inside."""
+        if not self.ema_decay > 0:
+            raise RuntimeError("ema_weights() needs weight averaging: give --ema_decay D (Parameters.ema_decay in (0, 1)); it is 0 = off")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() is already entered: the parameters are the averages now (it does not nest)")
+        w2 = self.vgg.w2_valid if self.vgg is not None else False
+        self._swap_averages()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_averages()
+            self._ema_swapped = False
+            if self.vgg is not None:
+                self.vgg.w2_valid = w2   # the parameters are bit for bit the ones those sums were taken of
+
+    def _swap_averages(self):
+        st = _stream()
+        self.cap.join_off_chain()
+        for eng in self._ema_engines():
+            S = eng.store
+            self.lib.vc_swap_f32(st, P(S.p), P(S.slot("ema")), S.n)
+        self.cap.param_updates += 1   # the kernel writes behind torch's back (CaptionEngine.param_version)
+        if self.vgg is not None:
+            self.vgg.w2_valid = False
+
     def load_state_dict(self, d, imagenet_path=None):
+        avg = split_averages(d)
+        if avg and not self.ema_decay > 0:
+            print("checkpoint carries %d averaged variables (<name>%s): ignored, and not written again, with --ema_decay at its default"
+                  % (len(avg), EMA_SUFFIX))
+            d = {k: v for k, v in d.items() if not k.endswith(EMA_SUFFIX)}
+        self._load_state_dict(d, imagenet_path)
+        if self.ema_decay > 0:
+            warm = [e.ema_warmup for e in self._ema_engines()]
+            if all(warm):
+                print("weight averaging: no <name>%s among the loaded variables: the averages start from the parameters, decay "
+                      "min(%g, (1 + t) / (10 + t)) (warm-up on)" % (EMA_SUFFIX, self.ema_decay))
+            else:
+                print("weight averaging: averages loaded%s: constant decay %g (no warm-up: the step counter restarts at 0)"
+                      % ("" if not any(warm) else " for the caption side, the cnn/* averages start from the parameters with the warm-up",
+                         self.ema_decay))
+
+    def _load_state_dict(self, d, imagenet_path):
         self.cap.load_params(d)
-        cnn = {k: v for k, v in d.items() if k.startswith("cnn/")}
+        cnn = {k: v for k, v in d.items() if k.startswith("cnn/") and not k.endswith(EMA_SUFFIX)}
         if self.vgg is not None:
             if not cnn and imagenet_path and os.path.exists(imagenet_path):
                 # a checkpoint written without cnn/* (older runs of this build with precomputed features)
@@ -1022,12 +1130,23 @@ class Trainer(object):
             from . import tf_bundle
             tf_bundle.write_bundle(path, self.state_dict())
 
-    def restore(self, path):
-        """saver.restore (main.py:201-204, gen_caption.py:113-115): every variable of this model must be present."""
+    def restore(self, path, use_ema=False):
+        """saver.restore (main.py:201-204, gen_caption.py:113-115): every variable of this model must be present.
+        use_ema: load each <name>/ExponentialMovingAverage of the checkpoint AS <name> (what tf.train.ExponentialMovingAverage's
+        variables_to_restore() does): the model is then the averaged one for every consumer."""
         inet = getattr(self.p, "image_net_weights_path", None)
         if path.endswith(".npz"):
             with np.load(path) as z:
-                self.load_state_dict({k: z[k] for k in z.files}, imagenet_path=inet)
+                d = {k: z[k] for k in z.files}
         else:
             from . import tf_bundle
-            self.load_state_dict(tf_bundle.read_bundle(path), imagenet_path=inet)
+            d = tf_bundle.read_bundle(path)
+        if use_ema:
+            avg = split_averages(d)
+            if not avg:
+                raise KeyError("--use_ema: checkpoint %s holds no averaged weights (<name>%s): it was written without --ema_decay"
+                               % (path, EMA_SUFFIX))
+            d = {k: v for k, v in d.items() if not k.endswith(EMA_SUFFIX)}
+            d.update(avg)
+            print("restoring the averaged weights of %d variables (--use_ema)" % len(avg))
+        self.load_state_dict(d, imagenet_path=inet)

@@ -39,6 +39,8 @@ _DEFAULTS = dict(
     unlikelihood=0.0, ul_window=128,
     # bag-of-words auxiliary loss (off by default)
     bow_loss=0.0,
+    # weight averaging (off by default)
+    ema_decay=0.0, use_ema=False,
 )
 
 # (flag, attribute, converter or "flag" for store_true, choices).  The reference's flags first, in its order.
@@ -80,6 +82,7 @@ _FLAGS = [
     ("--sched_temperature", "sched_temperature", float, None),
     ("--unlikelihood", "unlikelihood", float, None), ("--ul_window", "ul_window", int, None),
     ("--bow_loss", "bow_loss", float, None),
+    ("--ema_decay", "ema_decay", float, None), ("--use_ema", "use_ema", "flag", None),
 ]
 _KL_FLAGS = ("kl_free_bits", "kl_weight", "kl_cycle_steps", "kl_cycle_ramp", "kl_cycles")
 _SCHED_FLAGS = ("sched_schedule", "sched_ramp_steps", "sched_pick", "sched_temperature")
@@ -178,6 +181,11 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                        "decoder's z step) and must predict which words the caption contains, so that z has a reason of its own to carry "
                        "the caption (finite, >= 0; default 0 = off; adds the variables bow/kernel and bow/bias; validation losses and the "
                        "reported rec_loss stay as they are; not with --no_encoder, --scst or --mode inference)",
+         "--ema_decay": "weight averaging: keep an exponential moving average of every trained variable with this decay, updated "
+                        "inside the optimiser pass (with the num_updates warm-up min(decay, (1 + t) / (10 + t)) unless the averages "
+                        "came from a checkpoint), validate with it as well and write it into the checkpoints as "
+                        "<name>/ExponentialMovingAverage (in [0, 1); default 0 = off; not with --scst or --mode inference)",
+         "--use_ema": "--mode inference: restore the averaged weights that a run with --ema_decay wrote in place of the last iterate",
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
@@ -358,6 +366,17 @@ class Parameters(object):
                 ap.error("--bow_loss shapes the cross-entropy objective, which --scst does not optimise")
             if self.mode != "training":
                 ap.error("--bow_loss is a way of training: not with --mode %s" % self.mode)
+        if not (0.0 <= self.ema_decay < 1.0):
+            ap.error("--ema_decay must be in [0, 1) (0 = off; got %r)" % self.ema_decay)
+        if self.ema_decay > 0:
+            if self.mode != "training":
+                ap.error("--ema_decay averages the weights of a training run: not with --mode %s (give --use_ema to decode with the "
+                         "averages of a checkpoint)" % self.mode)
+            if self.scst:
+                ap.error("--ema_decay does not go with --scst: the policy step updates ranges of the store only, and averaging under "
+                         "it is not built")
+        if self.use_ema and self.mode != "inference":
+            ap.error("--use_ema needs --mode inference (got --mode %s)" % self.mode)
         if self.eval_captions and self.mode != "inference":
             ap.error("--eval_captions needs --mode inference (got --mode %s)" % self.mode)
         if self.eval_self_cider and not self.eval_captions:
