@@ -211,8 +211,10 @@ def roundup(n, m):
 
 
 # (V, ld, offset in floats of the first logit from a 16-byte boundary, rows): register kernel with every quad tail, the memory kernel
-# by size (V > 12288), by pitch (ld % 4 != 0) and by alignment
-XENT_SHAPES = [(203, 204, 0, 7), (204, 204, 0, 7), (205, 208, 0, 7), (203, 212, 0, 7), (12300, 12300, 0, 3), (203, 205, 0, 7), (204, 204, 1, 7)]
+# by size (V > 12288), by pitch (ld % 4 != 0) and by alignment; the last register size and the first memory size (labels >= 1024:
+# the label sits in a later quad of its thread)
+XENT_SHAPES = [(203, 204, 0, 7), (204, 204, 0, 7), (205, 208, 0, 7), (203, 212, 0, 7), (12300, 12300, 0, 3), (203, 205, 0, 7), (204, 204, 1, 7),
+               (12288, 12288, 0, 3), (12289, 12292, 0, 3)]
 
 
 def xent_case(V, ld, off, R):

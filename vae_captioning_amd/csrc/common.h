@@ -92,6 +92,31 @@ __device__ __forceinline__ float block_max(float v, float* sh) {
     return t;
 }
 
+// max and sum of two per-thread values in ONE pass through LDS (block_max + block_sum with their barriers shared)
+__device__ __forceinline__ void block_max_sum(float& mx, float& sm, float* sh /* 8 floats */) {
+    mx = wave_max(mx);
+    sm = wave_sum(sm);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh[w] = mx; sh[4 + w] = sm; }
+    __syncthreads();
+    mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    sm = ((sh[4] + sh[5]) + sh[6]) + sh[7];   // fixed order -> deterministic
+}
+
+// sums of four per-thread values in ONE pass through LDS (block_sum four times with the barriers shared), fixed order
+__device__ __forceinline__ void block_sum4(float& a, float& b, float& c, float& d, float* sh /* 16 floats */) {
+    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); d = wave_sum(d);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh[w] = a; sh[4 + w] = b; sh[8 + w] = c; sh[12 + w] = d; }
+    __syncthreads();
+    a = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    b = ((sh[4] + sh[5]) + sh[6]) + sh[7];
+    c = ((sh[8] + sh[9]) + sh[10]) + sh[11];
+    d = ((sh[12] + sh[13]) + sh[14]) + sh[15];
+}
+
 // ---- Philox4x32-10 (Salmon et al. 2011), counter = (quad index lo, hi, offset lo, hi) -----
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t (&o)[4]) {

@@ -5,8 +5,11 @@
 // Reference: main.py:118-177 (KL, masked CE, lower bound), vae_model/encoder.py:59-109
 // (heads, zs.Normal sample), vae_model/decoder.py:109-110 (the z buffer is consumed as a
 // raw [N, S*L] reshape of [S, N, L] -- quirk Q1 -- i.e. the SAME memory, no kernel).
+#include <type_traits>
+
 #include "row_ops.h"
 #include "vaecap.h"
+#include "xent_row.h"
 
 namespace vc {
 
@@ -26,8 +29,6 @@ static inline int grid_for(long work_items, int per_block = 256, int cap = 2048)
 // HBM traffic = 4 B read + 4 B written per logit (the algorithmic minimum for an unfused
 // softmax-CE with gradient).
 // ---------------------------------------------------------------------------------------
-constexpr int XENT_MAXQ = 12;  // float4 per thread
-
 template <bool WRITE_GRAD>
 __global__ __launch_bounds__(256) void xent_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
                                                        int V, long ld, const float* __restrict__ den, float gscale,
@@ -269,48 +270,6 @@ __global__ __launch_bounds__(256) void kl_rows_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------
-// Gradient w.r.t. (mean, std) of   [sum over the S samples through z]  +  kl_w * KL:
-//   dmean = sum_s dz[s] + dKL/dmean ;  dstd = sum_s dz[s]*eps[s] + dKL/dstd
-// kl_w = ann[0] * kl_scale (device annealing coefficient x host constant: 1/10, and 1/N for
-// the batch-mean Normal KL).  out_logstd: return d/d(logstd) = dstd * std (Normal heads).
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ eps,
-                                                         const float* __restrict__ mean, const float* __restrict__ std_,
-                                                         const float* __restrict__ mu_p, const float* __restrict__ ann,
-                                                         float kl_scale, int S, long NL, int mode, int out_logstd,
-                                                         float* __restrict__ dmean, float* __restrict__ dstd) {
-    const float w = (ann ? ann[0] : 1.f) * kl_scale;
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < NL; j += (long)gridDim.x * 256) {
-        // S == 0: dmean / dstd already hold the sums over the samples (vc_latent_sums_mixed_f32)
-        float dm = S ? 0.f : dmean[j], ds = S ? 0.f : dstd[j];
-        int s = 0;
-        for (; s + 8 <= S; s += 8) {   // sixteen loads in flight, the sums in the same order as the plain loop (a thread per element is all
-            float g[8], e[8];          // the parallelism N * L = 48 000 gives: with one load pair at a time the launch took 65 us at cfg4)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { g[k] = dz[(long)(s + k) * NL + j]; e[k] = eps[(long)(s + k) * NL + j]; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { dm += g[k]; ds += g[k] * e[k]; }
-        }
-        for (; s < S; ++s) {
-            const float g = dz[(long)s * NL + j];
-            dm += g;
-            ds += g * eps[(long)s * NL + j];
-        }
-        const float m = mean[j], sd = std_[j];
-        if (mode == 0) {
-            dm += w * m;
-            ds -= w * (sd / (sd * sd + 1e-5f) - sd);
-        } else {
-            const float den = 2.f * VC_AG_SIGMA * VC_AG_SIGMA + 1e-7f;
-            dm += w * (m - mu_p[j]) / den;
-            ds -= 0.5f * w * (1.f / (sd + 1e-5f) - 2.f * sd / den);
-        }
-        dmean[j] = dm;
-        dstd[j] = out_logstd ? ds * sd : ds;
-    }
-}
-
-// ---------------------------------------------------------------------------------------
 // GMM / AG heads.  heads [N, 2*K*L]: columns [k*L + l] = component means tm[n,k,l],
 // columns [K*L + k*L + l] = log-stds tl[n,k,l]  (vae_model/encoder.py:71-107).
 //   AG : mean = sum_k c[n,k]*tm[n,k,:],  std = sum_k c[n,k]*exp(tl[n,k,:])   (:105-107)
@@ -385,129 +344,39 @@ __global__ void loss_finalize_kernel(const float* ce_num, const float* ce_den, c
 // below is a NEW one beside the plain form above -- with an option off the engine launches the plain entry, unchanged.
 // =======================================================================================
 
-// max and sum of two per-thread values in ONE pass through LDS (block_max + block_sum of common.h with their barriers shared)
-__device__ __forceinline__ void block_max_sum(float& mx, float& sm, float* sh /* 8 floats */) {
-    mx = wave_max(mx);
-    sm = wave_sum(sm);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sh[w] = mx; sh[4 + w] = sm; }
-    __syncthreads();
-    mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-    sm = ((sh[4] + sh[5]) + sh[6]) + sh[7];   // fixed order -> deterministic
-}
-
 // Label-smoothed masked cross-entropy: target (1 - eps) * onehot + eps / V over the V real columns.
 //   row_loss = mask * (lse(x) - (1 - eps) * x[label] - (eps / V) * sum_{v < V} x[v])
 //   dlogits[v] = mask * (gscale / den) * (softmax[v] - (1 - eps) * [v == label] - eps / V)   (v < V)
 // The columns of the row-pitch padding (V <= v < ld) do not exist: they are kept out of sum x (the plain kernel's -inf marker
 // would poison it) and their gradient is written as exactly 0 (dense_bwd_w contracts over the padded pitch).
 // Same traffic as the plain kernel: each logit read once and written once; sum x rides in the max's block reduction.
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(256) void xent_smooth_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                                              int V, long ld, const float* __restrict__ den, float gscale,
-                                                              float eps, float* __restrict__ row_loss) {
+// (The plain entry keeps kernels of its own: compiled with the smoothing taken out, this body's x * inv - m * k does not round the
+// label's column as the plain kernel's branch does, and a cfg2 training step's gradients then differ in their last bits.)
+template <bool REG, bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void xent_smooth_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                          int V, long ld, const float* __restrict__ den, float gscale,
+                                                          float eps, float* __restrict__ row_loss) {
     __shared__ float sh[8];
     const long row = blockIdx.x;
-    float4* p = reinterpret_cast<float4*>(logits + row * ld);
-    const int V4 = (V + 3) >> 2;
+    float* r = logits + row * ld;
     const int label = labels[row];
-    float4 x[XENT_MAXQ];
-    // Straight-line loads: a thread past the row's last quad re-reads that quad (a valid address; its lanes are masked below), so all
-    // twelve 16-byte loads are in flight at once -- with the load inside `if (i < V4)` and the padding handled by branches each
-    // load waited for the one before it and was split into a 12-byte and a 4-byte one (24 serialised round trips per thread).
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
-    float mx = -INFINITY, sx = 0.f;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {
-        const int i = threadIdx.x + q * 256, c = i * 4;
-        // columns >= V (the pitch padding, and every lane of a thread past the row) do not exist: 0 in sum x, -inf for max and exp
-        const bool v0 = c < V, v1 = c + 1 < V, v2 = c + 2 < V, v3 = c + 3 < V;
-        sx += ((v0 ? x[q].x : 0.f) + (v1 ? x[q].y : 0.f)) + ((v2 ? x[q].z : 0.f) + (v3 ? x[q].w : 0.f));
-        x[q].x = v0 ? x[q].x : -INFINITY; x[q].y = v1 ? x[q].y : -INFINITY;
-        x[q].z = v2 ? x[q].z : -INFINITY; x[q].w = v3 ? x[q].w : -INFINITY;
-        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
-    }
+    XentRow<REG> x(r, V);
+    float sx, mx = x.thread_max(&sx);
     block_max_sum(mx, sx, sh);
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {   // (exp(-inf) = 0: the masked lanes add nothing)
-        x[q].x = __expf(x[q].x - mx); x[q].y = __expf(x[q].y - mx);
-        x[q].z = __expf(x[q].z - mx); x[q].w = __expf(x[q].w - mx);
-        s += (x[q].x + x[q].y) + (x[q].z + x[q].w);
-    }
-    s = block_sum<256>(s, sh);
-    const bool live = label != 0;
+    const float s = block_sum<256>(x.exp_sum(mx), sh);
+    const bool live = label != 0, word = label > 0 && label < V;
     const float ev = eps / (float)V;
     if (threadIdx.x == 0) {
         float l = 0.f;
-        if (live && label > 0 && label < V) l = __logf(s) + mx - (1.f - eps) * logits[row * ld + label] - ev * sx;
+        if (word) l = __logf(s) + mx - (1.f - eps) * r[label] - ev * sx;
         row_loss[row] = l;
     }
     if (WRITE_GRAD) {
         __syncthreads();  // thread 0 has read logits[label] before anyone overwrites it
         const float k = live ? gscale / den[0] : 0.f;
         const float inv = k / s, ke = k * ev, kl = k * (1.f - eps);
-        // A scale-and-store with a branch-free patch of the label's column.  lq: which of this thread's quads holds the label, -1 in
-        // every other thread.
-        const bool own = label > 0 && label < V && (int)threadIdx.x == ((label >> 2) & 255);
-        const int lq = own ? (label >> 10) : -1, lc = label & 3;
-        const float a0 = lc == 0 ? kl : 0.f, a1 = lc == 1 ? kl : 0.f, a2 = lc == 2 ? kl : 0.f, a3 = lc == 3 ? kl : 0.f;
-#pragma unroll
-        for (int q = 0; q < XENT_MAXQ; ++q) {
-            const int i = threadIdx.x + q * 256;
-            if (i < V4) {
-                const float m = q == lq ? 1.f : 0.f;
-                p[i] = make_float4((x[q].x * inv - ke) - m * a0, (x[q].y * inv - ke) - m * a1, (x[q].z * inv - ke) - m * a2, (x[q].w * inv - ke) - m * a3);
-            }
-        }
-        // the last quad's padding columns hold exp(-inf) * inv - ke = -ke: the thread that stored them makes them exactly 0
-        float* r = logits + row * ld;
-        if ((int)threadIdx.x == ((V4 - 1) & 255))
-            for (int c = V; c < V4 * 4; ++c) r[c] = 0.f;
-        const int L4 = (int)(ld >> 2);  // quads of the pitch past the last real column: zeros as well
-        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
-    }
-}
-
-// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(256) void xent_smooth_mem_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                                              int V, long ld, const float* __restrict__ den, float gscale,
-                                                              float eps, float* __restrict__ row_loss) {
-    __shared__ float sh[4];
-    const long row = blockIdx.x;
-    float* p = logits + row * ld;
-    const int label = labels[row];
-    float mx = -INFINITY, sx = 0.f;
-    for (int c = threadIdx.x; c < V; c += 256) {
-        const float v = p[c];
-        mx = fmaxf(mx, v);
-        sx += v;
-    }
-    mx = block_max<256>(mx, sh);
-    sx = block_sum<256>(sx, sh);
-    float s = 0.f;
-    for (int c = threadIdx.x; c < V; c += 256) s += __expf(p[c] - mx);
-    s = block_sum<256>(s, sh);
-    const bool live = label != 0;
-    const float ev = eps / (float)V;
-    if (threadIdx.x == 0) {
-        float l = 0.f;
-        if (live && label > 0 && label < V) l = __logf(s) + mx - (1.f - eps) * p[label] - ev * sx;
-        row_loss[row] = l;
-    }
-    if (WRITE_GRAD) {
-        __syncthreads();
-        const float k = live ? gscale / den[0] : 0.f;
-        const float inv = k / s, ke = k * ev, kl = k * (1.f - eps);
-        for (int c = threadIdx.x; c < V; c += 256) {
-            float d = __expf(p[c] - mx) * inv - ke;
-            if (c == label) d -= kl;
-            p[c] = d;
-        }
-        for (long c = V + threadIdx.x; c < ld; c += 256) p[c] = 0.f;
+        x.store([=](float e) { return e * inv - ke; }, word ? label : -1, kl);
+        x.zero_pitch(ld);
     }
 }
 
@@ -554,19 +423,27 @@ __global__ __launch_bounds__(256) void kl_rows_fb_kernel(const float* __restrict
     }
 }
 
-// latent_bwd_kernel under free bits: a dimension held at the floor (kl <= fb, the forward kernel's comparison) gets no KL
-// gradient -- its dmean / dstd are the sums over the samples alone; every other element is latent_bwd_kernel's.
-__global__ __launch_bounds__(256) void latent_bwd_fb_kernel(const float* __restrict__ dz, const float* __restrict__ eps,
-                                                            const float* __restrict__ mean, const float* __restrict__ std_,
-                                                            const float* __restrict__ mu_p, const float* __restrict__ ann,
-                                                            float kl_scale, float fb, int S, long NL, int mode, int out_logstd,
-                                                            float* __restrict__ dmean, float* __restrict__ dstd) {
+// ---------------------------------------------------------------------------------------
+// Gradient w.r.t. (mean, std) of   [sum over the S samples through z]  +  kl_w * KL:
+//   dmean = sum_s dz[s] + dKL/dmean ;  dstd = sum_s dz[s]*eps[s] + dKL/dstd
+// kl_w = ann[0] * kl_scale (device annealing coefficient x host constant: 1/10, and 1/N for
+// the batch-mean Normal KL).  out_logstd: return d/d(logstd) = dstd * std (Normal heads).
+// FB (free bits): a dimension held at the floor (kl <= fb, kl_rows_fb_kernel's comparison) gets no KL gradient -- its dmean / dstd
+// are the sums over the samples alone.
+// ---------------------------------------------------------------------------------------
+template <bool FB>
+__global__ __launch_bounds__(256) void latent_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ eps,
+                                                         const float* __restrict__ mean, const float* __restrict__ std_,
+                                                         const float* __restrict__ mu_p, const float* __restrict__ ann,
+                                                         float kl_scale, float fb, int S, long NL, int mode, int out_logstd,
+                                                         float* __restrict__ dmean, float* __restrict__ dstd) {
     const float w = (ann ? ann[0] : 1.f) * kl_scale;
     for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < NL; j += (long)gridDim.x * 256) {
+        // S == 0: dmean / dstd already hold the sums over the samples (vc_latent_sums_mixed_f32)
         float dm = S ? 0.f : dmean[j], ds = S ? 0.f : dstd[j];
         int s = 0;
-        for (; s + 8 <= S; s += 8) {   // (latent_bwd_kernel's loop: the same sums in the same order)
-            float g[8], e[8];
+        for (; s + 8 <= S; s += 8) {   // sixteen loads in flight, the sums in the same order as the plain loop (a thread per element is all
+            float g[8], e[8];          // the parallelism N * L = 48 000 gives: with one load pair at a time the launch took 65 us at cfg4)
 #pragma unroll
             for (int k = 0; k < 8; ++k) { g[k] = dz[(long)(s + k) * NL + j]; e[k] = eps[(long)(s + k) * NL + j]; }
 #pragma unroll
@@ -579,7 +456,7 @@ __global__ __launch_bounds__(256) void latent_bwd_fb_kernel(const float* __restr
         }
         const float m = mean[j], sd = std_[j];
         const float mup = mode ? mu_p[j] : 0.f;
-        if (kl_elem(mode, m, sd, mup) > fb) {
+        if (!FB || kl_elem(mode, m, sd, mup) > fb) {
             if (mode == 0) {
                 dm += w * m;
                 ds -= w * (sd / (sd * sd + 1e-5f) - sd);
@@ -634,137 +511,56 @@ __global__ void loss_finalize_kl_kernel(const float* ce_num, const float* ce_den
 //   dlogits[v] = live * scale * ( adv[n] * (p_v - [v == label]) + beta * p_v * ((x_v - lse) + H) )   (v < V), exactly 0 for V <= v < ld
 // live = 0 < label < V.  The row is held as d_v = x_v - max (ENT) or exp(d_v) (plain): with H = log s - (sum_v e^d_v d_v) / s and
 // x_v - lse = d_v - log s nothing is ever the logarithm of a probability, so an underflowed p_v adds exactly 0.  ENT = false
-// (beta == 0) compiles the entropy arithmetic away: the kernel is then xent_smooth_reg_kernel's at eps = 0 with a per-row scale.
+// (beta == 0) compiles the entropy arithmetic away: the kernel is then xent_smooth_kernel's at eps = 0 with a per-row scale.
+// The second launch bound is the waves per SIMD the register form runs at (4 with the entropy terms, 6 without, 8 without a gradient):
+// left to itself the scheduler spends 11 to 16 more registers on the ENT = false forms and loses a wave.
 // =======================================================================================
-template <bool WRITE_GRAD, bool ENT>
-__global__ __launch_bounds__(256) void xent_policy_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                                              int V, long ld, const float* __restrict__ adv, int N, float scale,
-                                                              float beta, float* __restrict__ row_lp, float* __restrict__ row_ent) {
+template <bool REG, bool WRITE_GRAD, bool ENT>
+__global__ __launch_bounds__(256, ENT ? 4 : (WRITE_GRAD ? 6 : 8))
+void xent_policy_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels, int V, long ld,
+                        const float* __restrict__ adv, int N, float scale, float beta, float* __restrict__ row_lp,
+                        float* __restrict__ row_ent) {
     __shared__ float sh[4];
     const long row = blockIdx.x;
-    float4* p = reinterpret_cast<float4*>(logits + row * ld);
-    const int V4 = (V + 3) >> 2;
+    float* r = logits + row * ld;
     const int label = labels[row];
-    float4 x[XENT_MAXQ];
-    // straight-line loads, as in xent_smooth_reg_kernel: a thread past the row's last quad re-reads that quad, its lanes are masked below
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {
-        const int c = ((int)threadIdx.x + q * 256) * 4;
-        // columns >= V (the pitch padding, and every lane of a thread past the row) do not exist: -inf for max and exp
-        x[q].x = c < V ? x[q].x : -INFINITY; x[q].y = c + 1 < V ? x[q].y : -INFINITY;
-        x[q].z = c + 2 < V ? x[q].z : -INFINITY; x[q].w = c + 3 < V ? x[q].w : -INFINITY;
-        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
-    }
-    mx = block_max<256>(mx, sh);
-    float s = 0.f, sd = 0.f;   // sum e^d, sum e^d * d
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {   // (exp(-inf) = 0: the masked lanes add nothing)
-        const float d0 = x[q].x - mx, d1 = x[q].y - mx, d2 = x[q].z - mx, d3 = x[q].w - mx;
-        const float e0 = __expf(d0), e1 = __expf(d1), e2 = __expf(d2), e3 = __expf(d3);
-        s += (e0 + e1) + (e2 + e3);
-        if (ENT) {   // a term whose e^d is 0 (masked: d = -inf; underflowed: d finite) is exactly 0, never 0 * -inf
-            sd += ((e0 > 0.f ? e0 * d0 : 0.f) + (e1 > 0.f ? e1 * d1 : 0.f)) + ((e2 > 0.f ? e2 * d2 : 0.f) + (e3 > 0.f ? e3 * d3 : 0.f));
-            x[q] = make_float4(d0, d1, d2, d3);
-        } else {
-            x[q] = make_float4(e0, e1, e2, e3);
-        }
-    }
-    s = block_sum<256>(s, sh);
+    XentRow<REG, ENT> x(r, V);
+    const float mx = block_max<256>(x.thread_max(), sh);
+    float sd = 0.f;   // sum e^d * d
+    const float s = block_sum<256>(x.exp_sum(mx, ENT ? &sd : nullptr), sh);
     if (ENT) sd = block_sum<256>(sd, sh);
     const bool live = label > 0 && label < V;
     const float logs = __logf(s);
     const float H = ENT ? logs - sd / s : 0.f;
     if (threadIdx.x == 0) {
-        row_lp[row] = live ? (logits[row * ld + label] - mx) - logs : 0.f;
+        row_lp[row] = live ? (r[label] - mx) - logs : 0.f;
         if (ENT) row_ent[row] = live ? H : 0.f;
     }
     if (WRITE_GRAD) {
         __syncthreads();  // thread 0 has read logits[label] before anyone overwrites it
         const float ka = live ? scale * adv[row % N] : 0.f, kb = live ? scale * beta : 0.f;
         const float inv = 1.f / s, hb = H - logs;
-        // branch-free patch of the label's column, as in xent_smooth_reg_kernel.  lq: which of this thread's quads holds the label
-        const bool own = live && (int)threadIdx.x == ((label >> 2) & 255);
-        const int lq = own ? (label >> 10) : -1, lc = label & 3;
-        const float a0 = lc == 0 ? ka : 0.f, a1 = lc == 1 ? ka : 0.f, a2 = lc == 2 ? ka : 0.f, a3 = lc == 3 ? ka : 0.f;
-#pragma unroll
-        for (int q = 0; q < XENT_MAXQ; ++q) {
-            const int i = threadIdx.x + q * 256;
-            if (i < V4) {
-                const float m = q == lq ? 1.f : 0.f;
-                float4 g;
-                if (ENT) {   // p_v * (ka + kb * ((d_v - log s) + H)); p_v == 0 -> exactly 0 (a masked lane's d is -inf)
-                    const float p0 = __expf(x[q].x) * inv, p1 = __expf(x[q].y) * inv, p2 = __expf(x[q].z) * inv, p3 = __expf(x[q].w) * inv;
-                    g.x = p0 > 0.f ? p0 * (ka + kb * (x[q].x + hb)) : 0.f; g.y = p1 > 0.f ? p1 * (ka + kb * (x[q].y + hb)) : 0.f;
-                    g.z = p2 > 0.f ? p2 * (ka + kb * (x[q].z + hb)) : 0.f; g.w = p3 > 0.f ? p3 * (ka + kb * (x[q].w + hb)) : 0.f;
-                } else {
-                    const float k = ka * inv;
-                    g = make_float4(x[q].x * k, x[q].y * k, x[q].z * k, x[q].w * k);
-                }
-                p[i] = make_float4(g.x - m * a0, g.y - m * a1, g.z - m * a2, g.w - m * a3);
-            }
+        if (ENT) {   // p_v * (ka + kb * ((d_v - log s) + H)); p_v == 0 -> exactly 0 (a masked lane's d is -inf)
+            x.store([=](float d) { const float pv = __expf(d) * inv; return pv > 0.f ? pv * (ka + kb * (d + hb)) : 0.f; }, live ? label : -1, ka);
+        } else if (REG) {
+            const float k = ka * inv;
+            x.store([=](float e) { return e * k; }, live ? label : -1, ka);
+        } else {   // (the memory form has always rounded e * inv first: p_v * ka, not e_v * (ka / s))
+            x.store([=](float e) { return e * inv * ka; }, live ? label : -1, ka);
         }
-        // the last quad's padding columns and the quads of the pitch past it: exactly 0 (written by the thread that stored that quad)
-        float* r = logits + row * ld;
-        if ((int)threadIdx.x == ((V4 - 1) & 255))
-            for (int c = V; c < V4 * 4; ++c) r[c] = 0.f;
-        const int L4 = (int)(ld >> 2);
-        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
-    }
-}
-
-// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
-template <bool WRITE_GRAD, bool ENT>
-__global__ __launch_bounds__(256) void xent_policy_mem_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                                              int V, long ld, const float* __restrict__ adv, int N, float scale,
-                                                              float beta, float* __restrict__ row_lp, float* __restrict__ row_ent) {
-    __shared__ float sh[4];
-    const long row = blockIdx.x;
-    float* p = logits + row * ld;
-    const int label = labels[row];
-    float mx = -INFINITY;
-    for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, p[c]);
-    mx = block_max<256>(mx, sh);
-    float s = 0.f, sd = 0.f;
-    for (int c = threadIdx.x; c < V; c += 256) {
-        const float d = p[c] - mx, e = __expf(d);
-        s += e;
-        if (ENT) sd += e > 0.f ? e * d : 0.f;
-    }
-    s = block_sum<256>(s, sh);
-    if (ENT) sd = block_sum<256>(sd, sh);
-    const bool live = label > 0 && label < V;
-    const float logs = __logf(s);
-    const float H = ENT ? logs - sd / s : 0.f;
-    if (threadIdx.x == 0) {
-        row_lp[row] = live ? (p[label] - mx) - logs : 0.f;
-        if (ENT) row_ent[row] = live ? H : 0.f;
-    }
-    if (WRITE_GRAD) {
-        __syncthreads();
-        const float ka = live ? scale * adv[row % N] : 0.f, kb = live ? scale * beta : 0.f;
-        const float inv = 1.f / s, hb = H - logs;
-        for (int c = threadIdx.x; c < V; c += 256) {
-            const float d = p[c] - mx, pv = __expf(d) * inv;
-            float g = ENT ? (pv > 0.f ? pv * (ka + kb * (d + hb)) : 0.f) : pv * ka;
-            if (c == label) g -= ka;
-            p[c] = g;
-        }
-        for (long c = V + threadIdx.x; c < ld; c += 256) p[c] = 0.f;
+        x.zero_pitch(ld);
     }
 }
 
 // =======================================================================================
 // Unlikelihood training (DESIGN.md "Unlikelihood training"; Welleck et al. 2020, token level): the smoothed cross-entropy of
-// xent_smooth_*_kernel plus alpha * sum_{c in C} -log(1 - p_c) over the row's candidate set C, the distinct words of the same caption's
+// xent_smooth_kernel plus alpha * sum_{c in C} -log(1 - p_c) over the row's candidate set C, the distinct words of the same caption's
 // up to `window` earlier labels (rows are time-major, r = t * N + n) that are words (0 < c < V) and not the row's own label y.
 //   om_c = 1 - p_c; a candidate with om_c <= 1e-5 is CLAMPED: it adds -log(1e-5) to row_ul and nothing to the gradient (torch.clamp);
 //   r_c = p_c / om_c otherwise, R = sum_c r_c.  live = 0 < y < V, k = live * gscale / den:
 //   row_loss = the smoothed kernel's (cross-entropy alone); row_ul = live * sum_c -log(max(om_c, 1e-5)); row_cand = live * |C|;
 //   row_mass = live * sum_c p_c;  d[v] = k * (p_v * (1 - alpha * R) - (1 - eps) [v == y] - eps / V + alpha * r_v [v in C, unclamped]).
-// How the hazards of doing this in place are handled, in both kernels:
+// How the hazards of doing this in place are handled, in both forms of the row:
 //   * thread i < min(window, t) owns the label i + 1 steps back.  It reads that label, and -- before anything else is waited for -- the
 //     logit x_c of it; thread 0 reads x_y likewise.  All of these loads stand in front of the block reductions, whose barriers every
 //     thread passes before the first store to the row: no x_c or x_y can see a gradient.
@@ -782,19 +578,6 @@ __global__ __launch_bounds__(256) void xent_policy_mem_kernel(float* __restrict_
 // =======================================================================================
 constexpr int UL_MAXW = 128;
 #define VC_UL_CLAMP 1e-5f
-
-// sums of four per-thread values in ONE pass through LDS (block_sum of common.h four times with the barriers shared), fixed order
-__device__ __forceinline__ void block_sum4(float& a, float& b, float& c, float& d, float* sh /* 16 floats */) {
-    a = wave_sum(a); b = wave_sum(b); c = wave_sum(c); d = wave_sum(d);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sh[w] = a; sh[4 + w] = b; sh[8 + w] = c; sh[12 + w] = d; }
-    __syncthreads();
-    a = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-    b = ((sh[4] + sh[5]) + sh[6]) + sh[7];
-    c = ((sh[8] + sh[9]) + sh[10]) + sh[11];
-    d = ((sh[12] + sh[13]) + sh[14]) + sh[15];
-}
 
 // number of owner threads of row `row`: min(window, t), none for a row that is not live
 __device__ __forceinline__ int ul_owners(long row, int N, int window, bool live) {
@@ -827,47 +610,26 @@ __device__ __forceinline__ void ul_terms(float ec, float s, float& ul, float& pc
     rc = clamped ? 0.f : pc / om;
 }
 
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(256) void xent_ul_reg_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                                          int V, long ld, const float* __restrict__ den, float gscale,
-                                                          float eps, int N, float alpha, int window, float* __restrict__ row_loss,
-                                                          float* __restrict__ row_ul, int32_t* __restrict__ row_cand,
-                                                          float* __restrict__ row_mass) {
+template <bool REG, bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void xent_ul_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                      int V, long ld, const float* __restrict__ den, float gscale,
+                                                      float eps, int N, float alpha, int window, float* __restrict__ row_loss,
+                                                      float* __restrict__ row_ul, int32_t* __restrict__ row_cand,
+                                                      float* __restrict__ row_mass) {
     __shared__ float sh[16];
     __shared__ int cand[UL_MAXW];
     const long row = blockIdx.x;
     float* r = logits + row * ld;
-    float4* p = reinterpret_cast<float4*>(r);
-    const int V4 = (V + 3) >> 2;
     const int label = labels[row];
     const bool live = label > 0 && label < V;
-    float4 x[XENT_MAXQ];
-    // straight-line loads, as in xent_smooth_reg_kernel: a thread past the row's last quad re-reads that quad, its lanes are masked below
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
+    XentRow<REG> x(r, V);
     int c = ul_load(labels, row, N, V, ul_owners(row, N, window, live), label, cand);
     const float xc = c >= 0 ? r[c] : 0.f;                            // (a duplicate reads its word's logit too: dropped below)
     const float xy = (threadIdx.x == 0 && live) ? r[label] : 0.f;
-    float mx = -INFINITY, sx = 0.f;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {
-        const int i = threadIdx.x + q * 256, cc = i * 4;
-        const bool v0 = cc < V, v1 = cc + 1 < V, v2 = cc + 2 < V, v3 = cc + 3 < V;
-        sx += ((v0 ? x[q].x : 0.f) + (v1 ? x[q].y : 0.f)) + ((v2 ? x[q].z : 0.f) + (v3 ? x[q].w : 0.f));
-        x[q].x = v0 ? x[q].x : -INFINITY; x[q].y = v1 ? x[q].y : -INFINITY;
-        x[q].z = v2 ? x[q].z : -INFINITY; x[q].w = v3 ? x[q].w : -INFINITY;
-        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
-    }
+    float sx, mx = x.thread_max(&sx);
     block_max_sum(mx, sx, sh);   // (its barriers stand between ul_load's cand[] writes and ul_first's reads)
     c = ul_first(c, cand);
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {
-        x[q].x = __expf(x[q].x - mx); x[q].y = __expf(x[q].y - mx);
-        x[q].z = __expf(x[q].z - mx); x[q].w = __expf(x[q].w - mx);
-        s += (x[q].x + x[q].y) + (x[q].z + x[q].w);
-    }
-    s = block_sum<256>(s, sh);
+    const float s = block_sum<256>(x.exp_sum(mx), sh);
     float ec = 0.f, ul = 0.f, mass = 0.f, rc = 0.f, R, cnt = 0.f;
     if (c >= 0) {
         ec = __expf(xc - mx);
@@ -886,81 +648,10 @@ __global__ __launch_bounds__(256) void xent_ul_reg_kernel(float* __restrict__ lo
     if (WRITE_GRAD) {
         const float k = live ? gscale / den[0] : 0.f;
         const float inv = k * (1.f - alpha * R) / s, ke = k * ev, kl = k * (1.f - eps);
-        const bool own = live && (int)threadIdx.x == ((label >> 2) & 255);
-        const int lq = own ? (label >> 10) : -1, lc = label & 3;
-        const float a0 = lc == 0 ? kl : 0.f, a1 = lc == 1 ? kl : 0.f, a2 = lc == 2 ? kl : 0.f, a3 = lc == 3 ? kl : 0.f;
-#pragma unroll
-        for (int q = 0; q < XENT_MAXQ; ++q) {
-            const int i = threadIdx.x + q * 256;
-            if (i < V4) {
-                const float m = q == lq ? 1.f : 0.f;
-                p[i] = make_float4((x[q].x * inv - ke) - m * a0, (x[q].y * inv - ke) - m * a1, (x[q].z * inv - ke) - m * a2, (x[q].w * inv - ke) - m * a3);
-            }
-        }
-        // the last quad's padding columns and the quads of the pitch past it: exactly 0 (written by the thread that stored that quad)
-        if ((int)threadIdx.x == ((V4 - 1) & 255))
-            for (int cc = V; cc < V4 * 4; ++cc) r[cc] = 0.f;
-        const int L4 = (int)(ld >> 2);
-        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
+        x.store([=](float e) { return e * inv - ke; }, live ? label : -1, kl);
+        x.zero_pitch(ld);
         __syncthreads();   // the candidate columns were vector-stored by other threads: their owners write them behind this barrier
         if (c >= 0) r[c] = (ec * inv - ke) + k * alpha * rc;
-    }
-}
-
-// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(256) void xent_ul_mem_kernel(float* __restrict__ logits, const int32_t* __restrict__ labels,
-                                                          int V, long ld, const float* __restrict__ den, float gscale,
-                                                          float eps, int N, float alpha, int window, float* __restrict__ row_loss,
-                                                          float* __restrict__ row_ul, int32_t* __restrict__ row_cand,
-                                                          float* __restrict__ row_mass) {
-    __shared__ float sh[16];
-    __shared__ int cand[UL_MAXW];
-    const long row = blockIdx.x;
-    float* p = logits + row * ld;
-    const int label = labels[row];
-    const bool live = label > 0 && label < V;
-    int c = ul_load(labels, row, N, V, ul_owners(row, N, window, live), label, cand);
-    const float xc = c >= 0 ? p[c] : 0.f;
-    const float xy = (threadIdx.x == 0 && live) ? p[label] : 0.f;
-    float mx = -INFINITY, sx = 0.f;
-    for (int cc = threadIdx.x; cc < V; cc += 256) {
-        const float v = p[cc];
-        mx = fmaxf(mx, v);
-        sx += v;
-    }
-    mx = block_max<256>(mx, sh);   // (its barriers stand between ul_load's cand[] writes and ul_first's reads)
-    sx = block_sum<256>(sx, sh);
-    c = ul_first(c, cand);
-    float s = 0.f;
-    for (int cc = threadIdx.x; cc < V; cc += 256) s += __expf(p[cc] - mx);
-    s = block_sum<256>(s, sh);
-    float ec = 0.f, ul = 0.f, mass = 0.f, rc = 0.f, R, cnt = 0.f;
-    if (c >= 0) {
-        ec = __expf(xc - mx);
-        ul_terms(ec, s, ul, mass, rc);
-        cnt = 1.f;
-    }
-    R = rc;
-    block_sum4(ul, mass, R, cnt, sh);   // every read of the row stands in front of these barriers, every store behind them
-    const float ev = eps / (float)V;
-    if (threadIdx.x == 0) {
-        row_loss[row] = live ? __logf(s) + mx - (1.f - eps) * xy - ev * sx : 0.f;
-        row_ul[row] = ul;
-        row_cand[row] = (int32_t)cnt;
-        row_mass[row] = mass;
-    }
-    if (WRITE_GRAD) {
-        const float k = live ? gscale / den[0] : 0.f;
-        const float inv = k * (1.f - alpha * R) / s, ke = k * ev, kl = k * (1.f - eps);
-        for (int cc = threadIdx.x; cc < V; cc += 256) {
-            float d = __expf(p[cc] - mx) * inv - ke;
-            if (cc == label) d -= kl;
-            p[cc] = d;
-        }
-        for (long cc = V + threadIdx.x; cc < ld; cc += 256) p[cc] = 0.f;
-        __syncthreads();   // the candidate columns were stored by other threads: their owners write them behind this barrier
-        if (c >= 0) p[c] =(ec * inv - ke) + k * alpha * rc;
     }
 }
 
@@ -971,7 +662,7 @@ __global__ __launch_bounds__(256) void xent_ul_mem_kernel(float* __restrict__ lo
 // of word w, p = softmax over the V real columns, k = gscale / den:
 //   row_loss = m * lse(x) - sum_w c_w x_w;  row_mass = sum over the DISTINCT bag words of p_w;  row_words = their number;
 //   d[v] = k * (m * p_v - c_v) for v < V, exactly 0 in the pitch padding; a row with m = 0 comes back all-zero.
-// In place, with the means of xent_ul_*_kernel:
+// In place, with the means of xent_ul_kernel:
 //   * thread i < T owns position i.  It reads its word and that word's logit x_w in front of the first block reduction, whose barriers
 //     every thread passes before the first store to the row: no x_w can see a gradient.  The words go to LDS.
 //   * behind those barriers an owner KEEPS its word only if no lower-indexed owner holds it (bow_keep); the keeper counts the word's
@@ -1003,41 +694,21 @@ __device__ __forceinline__ int bow_keep(int w, int T, const int* bag) {
     return cnt;
 }
 
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(256) void bow_xent_reg_kernel(float* __restrict__ logits, int V, long ld, const int32_t* __restrict__ labels,
-                                                           int T, long ldl, const float* __restrict__ den, float gscale,
-                                                           float* __restrict__ row_loss, float* __restrict__ row_mass,
-                                                           int32_t* __restrict__ row_words) {
+template <bool REG, bool WRITE_GRAD>
+__global__ __launch_bounds__(256) void bow_xent_kernel(float* __restrict__ logits, int V, long ld, const int32_t* __restrict__ labels,
+                                                       int T, long ldl, const float* __restrict__ den, float gscale,
+                                                       float* __restrict__ row_loss, float* __restrict__ row_mass,
+                                                       int32_t* __restrict__ row_words) {
     __shared__ float sh[16];
     __shared__ int bag[BOW_MAXT];
     const long row = blockIdx.x;
     float* r = logits + row * ld;
-    float4* p = reinterpret_cast<float4*>(r);
-    const int V4 = (V + 3) >> 2;
-    float4 x[XENT_MAXQ];
-    // straight-line loads, as in xent_smooth_reg_kernel: a thread past the row's last quad re-reads that quad, its lanes are masked below
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) x[q] = p[min((int)threadIdx.x + q * 256, V4 - 1)];
+    XentRow<REG> x(r, V);
     const int w = bow_load(labels, row, T, ldl, V, bag);
     const float xw = w >= 0 ? r[w] : 0.f;                            // (a duplicate reads its word's logit too: dropped below)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {
-        const int i = threadIdx.x + q * 256, cc = i * 4;
-        x[q].x = cc < V ? x[q].x : -INFINITY; x[q].y = cc + 1 < V ? x[q].y : -INFINITY;
-        x[q].z = cc + 2 < V ? x[q].z : -INFINITY; x[q].w = cc + 3 < V ? x[q].w : -INFINITY;
-        mx = fmaxf(mx, fmaxf(fmaxf(x[q].x, x[q].y), fmaxf(x[q].z, x[q].w)));
-    }
-    mx = block_max<256>(mx, sh);   // (its barriers stand between bow_load's bag[] writes and bow_keep's reads)
+    const float mx = block_max<256>(x.thread_max(), sh);   // (its barriers stand between bow_load's bag[] writes and bow_keep's reads)
     const int cw = bow_keep(w, T, bag);
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < XENT_MAXQ; ++q) {   // (exp(-inf) = 0: the masked lanes add nothing)
-        x[q].x = __expf(x[q].x - mx); x[q].y = __expf(x[q].y - mx);
-        x[q].z = __expf(x[q].z - mx); x[q].w = __expf(x[q].w - mx);
-        s += (x[q].x + x[q].y) + (x[q].z + x[q].w);
-    }
-    s = block_sum<256>(s, sh);
+    const float s = block_sum<256>(x.exp_sum(mx), sh);
     const float ec = cw > 0 ? __expf(xw - mx) : 0.f;
     float m = w >= 0 ? 1.f : 0.f, cx = (float)cw * (xw - mx), mass = ec / s, words = cw > 0 ? 1.f : 0.f;
     block_sum4(m, cx, mass, words, sh);   // every x_w has been read in front of these barriers: the stores below come behind them
@@ -1049,52 +720,10 @@ __global__ __launch_bounds__(256) void bow_xent_reg_kernel(float* __restrict__ l
     if (WRITE_GRAD) {
         const float k = m > 0.f ? gscale / den[0] : 0.f;
         const float inv = k * m / s;
-#pragma unroll
-        for (int q = 0; q < XENT_MAXQ; ++q) {
-            const int i = threadIdx.x + q * 256;
-            if (i < V4) p[i] = make_float4(x[q].x * inv, x[q].y * inv, x[q].z * inv, x[q].w * inv);   // (masked lanes: 0 * inv = the padding's 0)
-        }
-        const int L4 = (int)(ld >> 2);
-        for (int i = V4 + threadIdx.x; i < L4; i += 256) p[i] = f4zero();
+        x.store([=](float e) { return e * inv; }, -1, 0.f);
+        x.zero_pitch(ld, /*last_quad=*/false);   // (the last quad's masked lanes were stored as 0 * inv)
         __syncthreads();   // the bag columns were vector-stored by other threads: their keepers write them behind this barrier
         if (cw > 0) r[w] = ec * inv - k * (float)cw;
-    }
-}
-
-// Generic V / pitch / alignment: three passes over the row (passes 2 and 3 hit L2).
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(256) void bow_xent_mem_kernel(float* __restrict__ logits, int V, long ld, const int32_t* __restrict__ labels,
-                                                           int T, long ldl, const float* __restrict__ den, float gscale,
-                                                           float* __restrict__ row_loss, float* __restrict__ row_mass,
-                                                           int32_t* __restrict__ row_words) {
-    __shared__ float sh[16];
-    __shared__ int bag[BOW_MAXT];
-    const long row = blockIdx.x;
-    float* p = logits + row * ld;
-    const int w = bow_load(labels, row, T, ldl, V, bag);
-    const float xw = w >= 0 ? p[w] : 0.f;
-    float mx = -INFINITY;
-    for (int cc = threadIdx.x; cc < V; cc += 256) mx = fmaxf(mx, p[cc]);
-    mx = block_max<256>(mx, sh);   // (its barriers stand between bow_load's bag[] writes and bow_keep's reads)
-    const int cw = bow_keep(w, T, bag);
-    float s = 0.f;
-    for (int cc = threadIdx.x; cc < V; cc += 256) s += __expf(p[cc] - mx);
-    s = block_sum<256>(s, sh);
-    const float ec = cw > 0 ? __expf(xw - mx) : 0.f;
-    float m = w >= 0 ? 1.f : 0.f, cx = (float)cw * (xw - mx), mass = ec / s, words = cw > 0 ? 1.f : 0.f;
-    block_sum4(m, cx, mass, words, sh);   // every read of the row stands in front of these barriers, every store behind them
-    if (threadIdx.x == 0) {
-        row_loss[row] = m > 0.f ? m * __logf(s) - cx : 0.f;
-        row_mass[row] = mass;
-        row_words[row] = (int32_t)words;
-    }
-    if (WRITE_GRAD) {
-        const float k = m > 0.f ? gscale / den[0] : 0.f;
-        const float inv = k * m / s;
-        for (int cc = threadIdx.x; cc < V; cc += 256) p[cc] = __expf(p[cc] - mx) * inv;
-        for (long cc = V + threadIdx.x; cc < ld; cc += 256) p[cc] = 0.f;
-        __syncthreads();   // the bag columns were stored by other threads: their keepers write them behind this barrier
-        if (cw > 0) p[w] = ec * inv - k * (float)cw;
     }
 }
 
@@ -1129,6 +758,17 @@ __global__ __launch_bounds__(256) void bow_stats_kernel(const int32_t* __restric
 
 using namespace vc;
 
+// The dispatch of the in-place cross-entropy family: the register form of the row where it fits, the gradient compiled in or out.
+// `launch` is a generic lambda that receives REG and WRITE_GRAD as std::bool_constant values and launches that instantiation.
+template <class F>
+static inline void xent_dispatch(const float* logits, int V, long ld, int write_grad, F launch) {
+    if (xent_row_in_registers(logits, V, ld)) {
+        if (write_grad) launch(std::true_type(), std::true_type()); else launch(std::true_type(), std::false_type());
+    } else {
+        if (write_grad) launch(std::false_type(), std::true_type()); else launch(std::false_type(), std::false_type());
+    }
+}
+
 extern "C" int vc_loss_finalize_f32(void* stream, const float* ce_num, const float* ce_den, const float* reg_sumsq,
                                     float reg_scale, const float* kl_sum, float inv_n, const float* ann, float* out4) {
     VC_CHECK_ARG(ce_num && ce_den && out4, "null pointer");
@@ -1143,16 +783,10 @@ extern "C" int vc_softmax_xent_f32(void* stream, float* logits, const int32_t* l
     VC_CHECK_ARG(!write_grad || den, "den required for the gradient");
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    // register kernel: rows of whole float4 quads -- V % 4 == 0, or a row pitch padded to a multiple of 4 (ld >= roundup(V, 4))
-    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
-    dim3 g((unsigned)rows), b(256);
-    if (reg) {
-        if (write_grad) hipLaunchKernelGGL(xent_reg_kernel<true>, g, b, 0, st, logits, labels, V, ld, den, gscale, row_loss);
-        else hipLaunchKernelGGL(xent_reg_kernel<false>, g, b, 0, st, logits, labels, V, ld, den, gscale, row_loss);
-    } else {
-        if (write_grad) hipLaunchKernelGGL(xent_mem_kernel<true>, g, b, 0, st, logits, labels, V, ld, den, gscale, row_loss);
-        else hipLaunchKernelGGL(xent_mem_kernel<false>, g, b, 0, st, logits, labels, V, ld, den, gscale, row_loss);
-    }
+    xent_dispatch(logits, V, ld, write_grad, [&](auto R, auto W) {
+        auto* kernel = decltype(R)::value ? xent_reg_kernel<decltype(W)::value> : xent_mem_kernel<decltype(W)::value>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, labels, V, ld, den, gscale, row_loss);
+    });
     VC_LAUNCH_CHECK();
     return 0;
 }
@@ -1217,8 +851,8 @@ extern "C" int vc_latent_bwd_f32(void* stream, int S, int N, int L, int mode, in
     VC_CHECK_ARG(mean && std_ && dmean && dstd && S >= 0 && (S == 0 || (dz && eps)) && N > 0 && L > 0, "bad argument");
     VC_CHECK_ARG(mode == 0 || (mode == 1 && mu_p), "mu_p required for the AG prior");
     const long NL = (long)N * L;
-    hipLaunchKernelGGL(latent_bwd_kernel, dim3(grid_for(NL)), dim3(256), 0, (hipStream_t)stream, dz, eps, mean, std_, mu_p, ann,
-                       kl_scale, S, NL, mode, out_logstd, dmean, dstd);
+    hipLaunchKernelGGL(latent_bwd_kernel<false>, dim3(grid_for(NL)), dim3(256), 0, (hipStream_t)stream, dz, eps, mean, std_, mu_p, ann,
+                       kl_scale, 0.f, S, NL, mode, out_logstd, dmean, dstd);
     VC_LAUNCH_CHECK();
     return 0;
 }
@@ -1239,7 +873,7 @@ extern "C" int vc_heads_mix_bwd_f32(void* stream, int N, int K, int L, const flo
     return 0;
 }
 
-// ---- training objective options (each beside its plain entry above; the dispatch rule of the smoothed form is vc_softmax_xent_f32's)
+// ---- training objective options (each beside its plain entry above)
 extern "C" int vc_softmax_xent_smooth_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
                                           const float* den, float gscale, float eps, float* row_loss, int write_grad) {
     VC_CHECK_ARG(logits && labels && row_loss && rows >= 0 && V > 0 && ld >= V, "bad argument");
@@ -1247,15 +881,10 @@ extern "C" int vc_softmax_xent_smooth_f32(void* stream, float* logits, const int
     VC_CHECK_ARG(eps >= 0.f && eps < 1.f, "eps must be in [0, 1)");
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
-    dim3 g((unsigned)rows), b(256);
-    if (reg) {
-        if (write_grad) hipLaunchKernelGGL(xent_smooth_reg_kernel<true>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
-        else hipLaunchKernelGGL(xent_smooth_reg_kernel<false>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
-    } else {
-        if (write_grad) hipLaunchKernelGGL(xent_smooth_mem_kernel<true>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
-        else hipLaunchKernelGGL(xent_smooth_mem_kernel<false>, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, row_loss);
-    }
+    xent_dispatch(logits, V, ld, write_grad, [&](auto R, auto W) {
+        hipLaunchKernelGGL((xent_smooth_kernel<decltype(R)::value, decltype(W)::value>), dim3((unsigned)rows), dim3(256), 0, st,
+                           logits, labels, V, ld, den, gscale, eps, row_loss);
+    });
     VC_LAUNCH_CHECK();
     return 0;
 }
@@ -1275,7 +904,7 @@ extern "C" int vc_latent_bwd_fb_f32(void* stream, int S, int N, int L, int mode,
     VC_CHECK_ARG(mean && std_ && dmean && dstd && S >= 0 && (S == 0 || (dz && eps)) && N > 0 && L > 0, "bad argument");
     VC_CHECK_ARG(mode == 0 || (mode == 1 && mu_p), "mu_p required for the AG prior");
     const long NL = (long)N * L;
-    hipLaunchKernelGGL(latent_bwd_fb_kernel, dim3(grid_for(NL)), dim3(256), 0, (hipStream_t)stream, dz, eps, mean, std_, mu_p, ann,
+    hipLaunchKernelGGL(latent_bwd_kernel<true>, dim3(grid_for(NL)), dim3(256), 0, (hipStream_t)stream, dz, eps, mean, std_, mu_p, ann,
                        kl_scale, free_bits, S, NL, mode, out_logstd, dmean, dstd);
     VC_LAUNCH_CHECK();
     return 0;
@@ -1297,7 +926,7 @@ extern "C" int vc_loss_finalize_kl_f32(void* stream, const float* ce_num, const 
     return 0;
 }
 
-// ---- self-critical training: the policy-gradient loss (dispatch rule: vc_softmax_xent_f32's; beta == 0 runs the kernels without
+// ---- self-critical training: the policy-gradient loss (beta == 0 runs the kernels without
 // the entropy arithmetic, row_ent may then be NULL)
 extern "C" int vc_softmax_xent_policy_f32(void* stream, float* logits, const int32_t* labels, long rows, int V, long ld,
                                           const float* adv, int N, float scale, float beta, float* row_lp, float* row_ent, int write_grad) {
@@ -1307,23 +936,16 @@ extern "C" int vc_softmax_xent_policy_f32(void* stream, float* logits, const int
     VC_CHECK_ARG(beta == 0.f || row_ent, "row_ent required with beta > 0");
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
-    const bool ent = beta > 0.f;
-    dim3 g((unsigned)rows), b(256);
-#define VC_POLICY_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, st, logits, labels, V, ld, adv, N, scale, beta, row_lp, row_ent)
-    if (reg) {
-        if (write_grad) { if (ent) VC_POLICY_LAUNCH((xent_policy_reg_kernel<true, true>)); else VC_POLICY_LAUNCH((xent_policy_reg_kernel<true, false>)); }
-        else { if (ent) VC_POLICY_LAUNCH((xent_policy_reg_kernel<false, true>)); else VC_POLICY_LAUNCH((xent_policy_reg_kernel<false, false>)); }
-    } else {
-        if (write_grad) { if (ent) VC_POLICY_LAUNCH((xent_policy_mem_kernel<true, true>)); else VC_POLICY_LAUNCH((xent_policy_mem_kernel<true, false>)); }
-        else { if (ent) VC_POLICY_LAUNCH((xent_policy_mem_kernel<false, true>)); else VC_POLICY_LAUNCH((xent_policy_mem_kernel<false, false>)); }
-    }
-#undef VC_POLICY_LAUNCH
+    xent_dispatch(logits, V, ld, write_grad, [&](auto R, auto W) {
+        constexpr bool REG = decltype(R)::value, WG = decltype(W)::value;
+        auto* kernel = beta > 0.f ? xent_policy_kernel<REG, WG, true> : xent_policy_kernel<REG, WG, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, labels, V, ld, adv, N, scale, beta, row_lp, row_ent);
+    });
     VC_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- unlikelihood training: the smoothed cross-entropy with the repetition penalty in the same pass (dispatch rule: vc_softmax_xent_f32's)
+// ---- unlikelihood training: the smoothed cross-entropy with the repetition penalty in the same pass
 extern "C" int vc_softmax_xent_ul_f32(void* stream, float* logits, const int32_t* labels, long rows, int N, int V, long ld,
                                       const float* den, float gscale, float eps, float alpha, int window, float* row_loss,
                                       float* row_ul, int32_t* row_cand, float* row_mass, int write_grad) {
@@ -1336,15 +958,10 @@ extern "C" int vc_softmax_xent_ul_f32(void* stream, float* logits, const int32_t
     VC_CHECK_ARG(N > 0 && rows % N == 0, "rows must be a multiple of N (time-major [T, N] rows)");
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
-    dim3 g((unsigned)rows), b(256);
-#define VC_UL_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, st, logits, labels, V, ld, den, gscale, eps, N, alpha, window, row_loss, row_ul, row_cand, row_mass)
-    if (reg) {
-        if (write_grad) VC_UL_LAUNCH(xent_ul_reg_kernel<true>); else VC_UL_LAUNCH(xent_ul_reg_kernel<false>);
-    } else {
-        if (write_grad) VC_UL_LAUNCH(xent_ul_mem_kernel<true>); else VC_UL_LAUNCH(xent_ul_mem_kernel<false>);
-    }
-#undef VC_UL_LAUNCH
+    xent_dispatch(logits, V, ld, write_grad, [&](auto R, auto W) {
+        hipLaunchKernelGGL((xent_ul_kernel<decltype(R)::value, decltype(W)::value>), dim3((unsigned)rows), dim3(256), 0, st,
+                           logits, labels, V, ld, den, gscale, eps, N, alpha, window, row_loss, row_ul, row_cand, row_mass);
+    });
     VC_LAUNCH_CHECK();
     return 0;
 }
@@ -1381,7 +998,7 @@ extern "C" int vc_ul_stats_f32(void* stream, long rows, int V, const int32_t* la
     return 0;
 }
 
-// ---- bag-of-words auxiliary loss: one row of logits per caption against the bag of its words (dispatch rule: vc_softmax_xent_f32's)
+// ---- bag-of-words auxiliary loss: one row of logits per caption against the bag of its words
 extern "C" int vc_bow_xent_f32(void* stream, float* logits, long rows, int V, long ld, const int32_t* labels, int T, long ldl,
                                const float* den, float gscale, float* row_loss, float* row_mass, int32_t* row_words, int write_grad) {
     VC_CHECK_ARG(logits && labels && row_loss && row_mass && row_words, "null pointer");
@@ -1391,15 +1008,10 @@ extern "C" int vc_bow_xent_f32(void* stream, float* logits, long rows, int V, lo
     VC_CHECK_ARG(!write_grad || den, "den required for the gradient");
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const bool reg = (ld % 4 == 0) && (ld >= (long)((V + 3) / 4) * 4) && (V <= XENT_MAXQ * 256 * 4) && (((uintptr_t)logits & 15) == 0);
-    dim3 g((unsigned)rows), b(256);
-#define VC_BOW_LAUNCH(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, st, logits, V, ld, labels, T, ldl, den, gscale, row_loss, row_mass, row_words)
-    if (reg) {
-        if (write_grad) VC_BOW_LAUNCH(bow_xent_reg_kernel<true>); else VC_BOW_LAUNCH(bow_xent_reg_kernel<false>);
-    } else {
-        if (write_grad) VC_BOW_LAUNCH(bow_xent_mem_kernel<true>); else VC_BOW_LAUNCH(bow_xent_mem_kernel<false>);
-    }
-#undef VC_BOW_LAUNCH
+    xent_dispatch(logits, V, ld, write_grad, [&](auto R, auto W) {
+        hipLaunchKernelGGL((bow_xent_kernel<decltype(R)::value, decltype(W)::value>), dim3((unsigned)rows), dim3(256), 0, st,
+                           logits, V, ld, labels, T, ldl, den, gscale, row_loss, row_mass, row_words);
+    });
     VC_LAUNCH_CHECK();
     return 0;
 }
