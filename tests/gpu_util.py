@@ -44,6 +44,38 @@ def host(t):
 P = abi.ptr
 
 
+class BeamState(object):
+    """vc_beam_update's state for Bv (virtual) images of beam n, junk-filled and then started by vc_beam_init (whose LSTM state
+    inputs and outputs are kept as c_in / h_in / c_out / h_out)."""
+    FIELDS = ("pcount", "ccount", "p_score", "p_logprob", "p_len", "c_score", "c_logprob", "c_len", "c_slot", "c_free", "c_sent", "parent", "tok")
+
+    def __init__(self, lib, Bv, n, L, bos, H=8):
+        M = Bv * n
+        junk_i = lambda *shape: torch.full(shape, -7, dtype=torch.int32, device="cuda")
+        junk_d = lambda *shape: torch.full(shape, 3.5, dtype=torch.float64, device="cuda")
+        self.Bv, self.n, self.L, self.M = Bv, n, L, M
+        self.pcount, self.ccount, self.c_free = junk_i(Bv), junk_i(Bv), junk_i(Bv)
+        self.p_score, self.p_logprob, self.p_len = junk_d(M), junk_d(M), junk_i(M)
+        self.sent = [junk_i(M, L), junk_i(M, L)]
+        self.c_score, self.c_logprob, self.c_len, self.c_slot = junk_d(M), junk_d(M), junk_i(M), junk_i(M)
+        self.c_sent = junk_i(Bv * (n + 1), L)
+        self.parent, self.tok = junk_i(M), junk_i(M)
+        self.c_in, self.h_in = torch.randn(Bv, H, device="cuda"), torch.randn(Bv, H, device="cuda")
+        self.c_out, self.h_out = torch.zeros(M, H, device="cuda"), torch.zeros(M, H, device="cuda")
+        lib.vc_beam_init(stream(), Bv, n, L, bos, H, P(self.c_in), P(self.h_in), P(self.c_out), P(self.h_out), P(self.pcount), P(self.ccount),
+                         P(self.p_score), P(self.p_logprob), P(self.p_len), P(self.sent[0]), P(self.sent[1]), P(self.c_score), P(self.c_logprob),
+                         P(self.c_len), P(self.c_slot), P(self.c_free), P(self.c_sent), P(self.parent), P(self.tok))
+
+    def args(self, it):
+        return (P(self.pcount), P(self.ccount), P(self.p_score), P(self.p_logprob), P(self.p_len), P(self.sent[it & 1]), P(self.sent[1 - (it & 1)]),
+                P(self.c_score), P(self.c_logprob), P(self.c_len), P(self.c_slot), P(self.c_free), P(self.c_sent), P(self.parent), P(self.tok))
+
+    def snapshot(self, it):
+        d = {k: host(getattr(self, k)) for k in self.FIELDS}
+        d["sent"] = host(self.sent[1 - (it & 1)])
+        return d
+
+
 def assert_close(got, ref, rtol, atol_scale=None, msg=""):
     """max|got-ref| <= rtol * max|ref| (+ tiny); prints where the worst element is."""
     got = np.asarray(got, dtype=np.float64)

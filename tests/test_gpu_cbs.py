@@ -15,8 +15,7 @@ from vae_captioning_amd.engine import CaptionEngine
 from vae_captioning_amd.generate import CaptionGenerator
 
 from . import cbs_ref
-from .gpu_util import P, dev, host, stream
-from .test_gpu_dbs import BeamState
+from .gpu_util import BeamState, P, dev, host, stream
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -17,43 +17,12 @@ from vae_captioning_amd.engine import CaptionEngine
 from vae_captioning_amd.generate import CaptionGenerator
 
 from . import dbs_ref
-from .gpu_util import P, dev, host, stream
+from .gpu_util import BeamState, P, dev, stream
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOS, EOS = 1, 2
 SHAPES = [(3, 2), (2, 4), (5, 2), (4, 1)]   # the shapes tests/test_dbs_host.py shows float32 and float64 to agree on
-
-
-class BeamState(object):
-    """vc_beam_update's state for Bv (virtual) images of beam n, junk-filled and then started by vc_beam_init."""
-    FIELDS = ("pcount", "ccount", "p_score", "p_logprob", "p_len", "c_score", "c_logprob", "c_len", "c_slot", "c_free", "c_sent", "parent", "tok")
-
-    def __init__(self, lib, Bv, n, L, bos, H=8):
-        M = Bv * n
-        junk_i = lambda *shape: torch.full(shape, -7, dtype=torch.int32, device="cuda")
-        junk_d = lambda *shape: torch.full(shape, 3.5, dtype=torch.float64, device="cuda")
-        self.Bv, self.n, self.L, self.M = Bv, n, L, M
-        self.pcount, self.ccount, self.c_free = junk_i(Bv), junk_i(Bv), junk_i(Bv)
-        self.p_score, self.p_logprob, self.p_len = junk_d(M), junk_d(M), junk_i(M)
-        self.sent = [junk_i(M, L), junk_i(M, L)]
-        self.c_score, self.c_logprob, self.c_len, self.c_slot = junk_d(M), junk_d(M), junk_i(M), junk_i(M)
-        self.c_sent = junk_i(Bv * (n + 1), L)
-        self.parent, self.tok = junk_i(M), junk_i(M)
-        c_in, h_in = torch.randn(Bv, H, device="cuda"), torch.randn(Bv, H, device="cuda")
-        c_out, h_out = torch.zeros(M, H, device="cuda"), torch.zeros(M, H, device="cuda")
-        lib.vc_beam_init(stream(), Bv, n, L, bos, H, P(c_in), P(h_in), P(c_out), P(h_out), P(self.pcount), P(self.ccount), P(self.p_score),
-                         P(self.p_logprob), P(self.p_len), P(self.sent[0]), P(self.sent[1]), P(self.c_score), P(self.c_logprob), P(self.c_len),
-                         P(self.c_slot), P(self.c_free), P(self.c_sent), P(self.parent), P(self.tok))
-
-    def args(self, it):
-        return (P(self.pcount), P(self.ccount), P(self.p_score), P(self.p_logprob), P(self.p_len), P(self.sent[it & 1]), P(self.sent[1 - (it & 1)]),
-                P(self.c_score), P(self.c_logprob), P(self.c_len), P(self.c_slot), P(self.c_free), P(self.c_sent), P(self.parent), P(self.tok))
-
-    def snapshot(self, it):
-        d = {k: host(getattr(self, k)) for k in self.FIELDS}
-        d["sent"] = host(self.sent[1 - (it & 1)])
-        return d
 
 
 def make_tables(rng, rows, kc, rounds, lo, hi):
@@ -97,9 +66,9 @@ def check_round(snap, partial, complete, B, G, w, L, where):
 
 
 KERNEL_SHAPES = [(1, 5, 6, 12, 2), (3, 3, 6, 12, 2), (2, 5, 6, 12, 2), (4, 4, 6, 12, 2), (2, 8, 5, 12, 2), (5, 2, 6, 12, 2), (16, 1, 6, 12, 2),
-                 (2, 2, 70, 80, 3)]
+                 (2, 2, 70, 80, 3), (1, 9, 6, 12, 2), (1, 16, 5, 12, 2)]
 KERNEL_IDS = ["one-group-is-vc_beam_update", "kc9-seven-rows-a-block", "kc10", "exactly-64-candidates", "128-candidates-two-blocks",
-              "default-5x2", "longest-chosen-list", "captions-longer-than-a-wave"]
+              "default-5x2", "longest-chosen-list", "captions-longer-than-a-wave", "one-group-of-nine", "one-group-of-sixteen"]
 
 
 @pytest.mark.parametrize("lam", [0.5, 0.25, 0.3], ids=["lam0.5", "lam0.25", "lam0.3-not-dyadic"])

@@ -207,8 +207,8 @@ def test_sample_mode_generates_valid_tokens(lib):
     assert a == b and all(0 <= t < 40 for s in a for t in s) and all(1 <= len(s) <= 6 for s in a)
 
 
-@pytest.mark.parametrize("n,rounds,L", [(1, 6, 12), (3, 6, 12), (5, 6, 12), (9, 6, 12), (16, 5, 12), (2, 70, 80)],
-                         ids=["beam1", "beam3", "beam5", "beam9-two-candidate-blocks", "beam16-four-candidate-blocks", "captions-longer-than-a-wave"])
+@pytest.mark.parametrize("n,rounds,L", [(1, 6, 12), (3, 6, 12), (5, 6, 12), (8, 6, 12), (9, 6, 12), (16, 5, 12), (2, 70, 80)],
+                         ids=["beam1", "beam3", "beam5", "beam8-slim-at-exactly-64-candidates", "beam9-two-candidate-blocks", "beam16-four-candidate-blocks", "captions-longer-than-a-wave"])
 def test_beam_update_replays_heapq_including_ties(lib, n, rounds, L):
     """vc_beam_update vs the Python TopN / heapq bookkeeping of decoder.py:254-293 on synthetic top-k tables whose
     probabilities are quantised to a few values (many exact score ties, many <EOS> hits): heap ARRAY order, scores,
@@ -217,25 +217,15 @@ def test_beam_update_replays_heapq_including_ties(lib, n, rounds, L):
     those limits.  The starting state comes from vc_beam_init (on buffers filled with garbage)."""
     import torch
     from vae_captioning_amd.utils.top_n import Beam, TopN
-    from .gpu_util import P, dev, host, stream
+    from .gpu_util import BeamState, P, dev, host, stream
     rng = np.random.default_rng(n)
     B, eos, bos, lnf, H = 7, 2, 1, 0.7, 8
     M = B * n
     i32 = dict(dtype=torch.int32, device="cuda")
-    f64 = dict(dtype=torch.float64, device="cuda")
-    junk_i = lambda *shape: torch.full(shape, -7, **i32)
-    junk_d = lambda *shape: torch.full(shape, 3.5, **f64)
-    pcount, ccount = junk_i(B), junk_i(B)
-    p_score, p_logprob, p_len = junk_d(M), junk_d(M), junk_i(M)
-    sent = [junk_i(M, L), junk_i(M, L)]
-    c_score, c_logprob, c_len, c_slot = junk_d(M), junk_d(M), junk_i(M), junk_i(M)
-    c_free = junk_i(B)
-    c_sent = junk_i(B * (n + 1), L)
-    parent, tok = junk_i(M), junk_i(M)
-    c_in, h_in = torch.randn(B, H, device="cuda"), torch.randn(B, H, device="cuda")
-    c_out, h_out = torch.zeros(M, H, device="cuda"), torch.zeros(M, H, device="cuda")
-    lib.vc_beam_init(stream(), B, n, L, bos, H, P(c_in), P(h_in), P(c_out), P(h_out), P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len),
-                     P(sent[0]), P(sent[1]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
+    st = BeamState(lib, B, n, L, bos, H)
+    c_in, h_in, c_out, h_out, sent = st.c_in, st.h_in, st.c_out, st.h_out, st.sent
+    pcount, ccount, p_score, p_logprob, p_len = st.pcount, st.ccount, st.p_score, st.p_logprob, st.p_len
+    c_score, c_logprob, c_len, c_slot, c_free, c_sent, parent, tok = st.c_score, st.c_logprob, st.c_len, st.c_slot, st.c_free, st.c_sent, st.parent, st.tok
     assert torch.equal(c_out, c_in.repeat_interleave(n, 0)) and torch.equal(h_out, h_in.repeat_interleave(n, 0))
     assert bool((pcount == 1).all()) and bool((ccount == 0).all()) and bool((c_free == (1 << (n + 1)) - 1).all())
     assert bool((p_score == 0).all()) and bool((p_logprob == 0).all()) and bool((p_len == 1).all()) and bool((sent[0] == bos).all())
@@ -249,9 +239,7 @@ def test_beam_update_replays_heapq_including_ties(lib, n, rounds, L):
     for it in range(rounds):
         tv = np.sort(rng.choice(levels, size=(M, n)).astype(np.float32), axis=1)[:, ::-1].copy()
         ti = rng.integers(2, 6, size=(M, n)).astype(np.int32)  # small vocabulary: <EOS> (= 2) comes up often
-        lib.vc_beam_update(stream(), B, n, L, eos, lnf, P(dev(tv)), P(dev(ti)), P(pcount), P(ccount), P(p_score), P(p_logprob), P(p_len),
-                           P(sent[it & 1]), P(sent[1 - (it & 1)]), P(c_score), P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent),
-                           P(parent), P(tok))
+        lib.vc_beam_update(stream(), B, n, L, eos, lnf, P(dev(tv)), P(dev(ti)), *st.args(it))
         for b in range(B):  # the reference loop
             lst = partial[b].extract()
             partial[b].reset()

@@ -5,9 +5,9 @@ V = 10 000, default model sizes), beside the plain beam search of the same rows 
   kernels: us per round of vc_beam_update_groups(5 x 2, 10 candidates per row) and of vc_beam_update(beam 10) alone, on full heaps
            (tables of random probabilities over a 50-word vocabulary without <EOS>: every row keeps its beams, words repeat across
            groups).  Device events around a hipGraph replay of 20 rounds, after vc_beam_init and 4 rounds that fill the heaps; the
-           median of --reps such runs.
+           median of --reps such runs.  --plain-beams 5,8,9,16 adds vc_beam_update alone at those widths, the same way.
 Prints one JSON line per part.
-    python tools/experiments/dbs_time.py [--reps 9] [--part calls kernels] [--once]
+    python tools/experiments/dbs_time.py [--reps 9] [--part calls kernels] [--plain-beams 5,8,9,16] [--once]
 --once: one warm call then one call of each search only (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
 import argparse
 import json
@@ -67,18 +67,21 @@ def time_calls(lib, reps, once):
                       "clock": "host perf_counter around a synchronised call, median"}))
 
 
-def time_kernels(lib, reps):
-    n, L, H, fill, timed = G * W, 32, 8, 4, 20   # (captions grow one token a round: 1 + fill + timed < L)
-    M = B * n
+def time_kernels(lib, reps, plain_beams=()):
+    L, H, fill, timed = 32, 8, 4, 20   # (captions grow one token a round: 1 + fill + timed < L)
     st = lambda: torch.cuda.current_stream().cuda_stream
     i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device="cuda")
     f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device="cuda")
-    rng = np.random.default_rng(1)
-    tv = torch.from_numpy(np.sort(rng.uniform(1e-4, 0.3, size=(M, n)).astype(np.float32), axis=1)[:, ::-1].copy()).cuda()
-    ti = torch.from_numpy(np.stack([rng.permutation(np.arange(3, 53))[:n] for _ in range(M)]).astype(np.int32)).cuda()
-    c_in, c_out = torch.zeros(B * G, H, device="cuda"), torch.zeros(M, H, device="cuda")
     out = {}
-    for name, Bv, w in (("vc_beam_update_10", B, n), ("vc_beam_update_groups_5x2", B * G, W)):
+    # (name, groups, beams per group): the two searches of 10 rows per image, then vc_beam_update alone at every width asked for
+    cases = [("vc_beam_update_10", 0, G * W), ("vc_beam_update_groups_5x2", G, W)] + [("vc_beam_update_plain_%d" % n, 0, n) for n in plain_beams]
+    for name, groups, w in cases:
+        n = max(groups, 1) * w               # rows per image = candidates per row
+        M, Bv = B * n, B * max(groups, 1)
+        rng = np.random.default_rng(1)
+        tv = torch.from_numpy(np.sort(rng.uniform(1e-4, 0.3, size=(M, n)).astype(np.float32), axis=1)[:, ::-1].copy()).cuda()
+        ti = torch.from_numpy(np.stack([rng.permutation(np.arange(3, 53))[:n] for _ in range(M)]).astype(np.int32)).cuda()
+        c_in, c_out = torch.zeros(Bv, H, device="cuda"), torch.zeros(M, H, device="cuda")
         pcount, ccount, c_free = i32(Bv), i32(Bv), i32(Bv)
         p_score, p_logprob, p_len = f64(M), f64(M), i32(M)
         sent = [i32(M, L), i32(M, L)]
@@ -88,8 +91,8 @@ def time_kernels(lib, reps):
                             P(c_logprob), P(c_len), P(c_slot), P(c_free), P(c_sent), P(parent), P(tok))
 
         def round_(it):
-            if name.endswith("5x2"):
-                lib.vc_beam_update_groups(st(), B, G, W, n, L, synth.EOS, 0.7, LAM, P(tv), P(ti), *state(it))
+            if groups:
+                lib.vc_beam_update_groups(st(), B, groups, w, n, L, synth.EOS, 0.7, LAM, P(tv), P(ti), *state(it))
             else:
                 lib.vc_beam_update(st(), B, n, L, synth.EOS, 0.7, P(tv), P(ti), *state(it))
 
@@ -121,7 +124,7 @@ def time_kernels(lib, reps):
         assert int(pcount.min()) == w, "the timed rounds must run on full heaps"
         out[name + "_us"] = round(float(np.median(us)), 2)
         out[name + "_us_min_max"] = [round(min(us), 2), round(max(us), 2)]
-    out.update(part="kernels", images=B, rows=M, reps=reps, rounds_per_run=timed,
+    out.update(part="kernels", images=B, rows=B * G * W, reps=reps, rounds_per_run=timed,
                clock="device events around one hipGraph replay of 20 rounds (a chain of launches, their gaps included), median of the runs")
     print(json.dumps(out))
 
@@ -131,13 +134,15 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--part", nargs="+", default=["calls", "kernels"], choices=["calls", "kernels"])
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--plain-beams", type=lambda v: [int(x) for x in v.split(",")], default=[],
+                    help="kernels part: also time vc_beam_update alone at these widths, e.g. 5,8,9,16 (the slim kernel and both edges of the general one)")
     a = ap.parse_args()
     lib = abi.load()
     lib.vc_device_check(0)
     if "calls" in a.part:
         time_calls(lib, a.reps, a.once)
     if "kernels" in a.part and not a.once:
-        time_kernels(lib, a.reps)
+        time_kernels(lib, a.reps, a.plain_beams)
 
 
 if __name__ == "__main__":

@@ -22,8 +22,12 @@
 // S banks' counters, so the banks are rewritten in place one target at a time.  A target's candidates are prepared a lane each: the
 // same-state rows in blocks of floor(64 / kc) whole rows (a word's place among its row's admissible words is a population count over a
 // ballot), a forced source's w * Wc <= 32 words in one block.  The lanes of a block are in the reference's walk order, so the sequential
-// walk is over the set bits of one ballot.  The walk, the heaps and the copies are beam.hip's (beam_heap.h); a new beam's parent is its
-// source row s*w + i of the image, which may lie in another bank.
+// walk is over the set bits of one ballot.  Heaps, sifts, the candidate's arithmetic and the argument block are beam_heap.h's; a new beam's
+// parent is its source row s*w + i of the image, which may lie in another bank.
+//
+// The bank's bookkeeping (pool slot, stores, copies) is written out here, as in beam_groups.hip, and is NOT beam_heap.h's BeamBank:
+// through BeamBank this kernel ran 3 % slower alone (41.2 against 40.0 us per round at C2 w4, profiles/beam_bank_time.md), the wait
+// for a bank's loads landing at the head of the bank loop.  Keep the three steps in step with BeamBank's.
 #include "beam_heap.h"
 
 namespace vc {
@@ -69,10 +73,7 @@ __global__ __launch_bounds__(64) void beam_update_constrained_kernel(BeamArgs a,
     const int fi = lane / Wc, fk = lane - fi * Wc; // this lane's beam and word within a forced block
     for (int t = 0; t < S; ++t) {
         const long v = v0 + t;
-        if (lane < w) {   // defaults for slots that stay empty: continue row v*w with token 0 (ignored)
-            a.parent[v * w + lane] = (int)(v * w);
-            a.tok[v * w + lane] = 0;
-        }
+        beam_next_defaults(a, v);
         const int np_t = lane_get(pc_all, t);
         int feeders = np_t;
         for (int j = 0; j < C; ++j) feeders += ((t >> j) & 1) ? lane_get(pc_all, t ^ (1 << j)) : 0;
@@ -90,10 +91,9 @@ __global__ __launch_bounds__(64) void beam_update_constrained_kernel(BeamArgs a,
         // one block of candidates: lane q holds (ok_q, source row src_q of the image, word tok_q, probability pw); lanes in walk order
         auto walk = [&](bool ok_q, int src_q, int tok_q, float pw) {
             const int len0_q = __shfl(old_len, ok_q ? src_q : 0, 64);
-            const double lp_q = __shfl(old_lp, ok_q ? src_q : 0, 64) + (double)logf(pw);   // decoder.py:282: float32 log, float64 sum
-            double sc_q = lp_q;
-            if (tok_q == a.eos && a.len_norm_f > 0) sc_q = lp_q / pow((double)(len0_q + 1), a.len_norm_f);
-            unsigned long long m = __ballot(ok_q && !((double)pw < 1e-12));   // decoder.py:279: float32 p against the Python float 1e-12
+            const BeamCand cd = beam_candidate(a, __shfl(old_lp, ok_q ? src_q : 0, 64), len0_q, pw, tok_q);
+            const double lp_q = cd.lp, sc_q = cd.score;
+            unsigned long long m = __ballot(ok_q && !cd.skip);
             while (m) {
                 const int c = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
                 m &= m - 1;
@@ -197,13 +197,9 @@ extern "C" int vc_beam_update_constrained(void* stream, int B, int C, int Wc, in
     VC_CHECK_ARG(kc >= w && kc <= w + nw && kc <= V, "candidates per row must be min(beams per state + constraint words, vocabulary) and at least the beams per state");
     VC_CHECK_ARG(ld >= V, "row stride of the probabilities below the vocabulary");
     VC_CHECK_ARG(((long)B << C) * w <= 0x7fffffffL / Lmax, "too many rows");
-    VC_CHECK_ARG((C == 0 || (cons && probs)) && top_p && top_i && pcount && ccount && p_score && p_logprob && p_len && sent_cur && sent_next &&
-                 c_score && c_logprob && c_len && c_slot && c_free && c_sent && parent && tok, "null pointer");
-    BeamArgs a;
-    a.B = B; a.n = w; a.k = kc; a.Lmax = Lmax; a.eos = eos; a.len_norm_f = len_norm_f;
-    a.tv = top_p; a.ti = top_i; a.pcount = pcount; a.ccount = ccount; a.p_len = p_len; a.c_len = c_len; a.c_slot = c_slot;
-    a.c_free = c_free; a.p_score = p_score; a.p_logprob = p_logprob; a.c_score = c_score; a.c_logprob = c_logprob;
-    a.sent_cur = sent_cur; a.sent_next = sent_next; a.c_sent = c_sent; a.parent = parent; a.tok = tok;
+    const BeamArgs a = beam_args(B, w, kc, Lmax, eos, len_norm_f, top_p, top_i, pcount, ccount, p_score, p_logprob, p_len, sent_cur, sent_next,
+                                 c_score, c_logprob, c_len, c_slot, c_free, c_sent, parent, tok);
+    VC_CHECK_ARG((C == 0 || (cons && probs)) && top_p && top_i && beam_state_given(a), "null pointer");
     ConsArgs ca;
     ca.C = C; ca.Wc = C == 0 ? 1 : Wc; ca.V = V; ca.ld = ld; ca.cons = cons; ca.probs = probs;
     hipLaunchKernelGGL(beam_update_constrained_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a, ca);

@@ -24,7 +24,12 @@
 // One wave per IMAGE; its G groups run one after the other inside the wave.  A group's candidates are prepared in blocks of
 // floor(64 / kc) whole rows (a lane per candidate, a row never split between blocks), so a candidate's position within its row is a
 // rank count over its row's kc keys by shuffles, in parallel, before the sequential walk.  The chosen words (<= 15 matter) live in
-// lanes; a candidate's c is a handful of readlane compares.  The walk, the heaps and the copies are beam.hip's (beam_heap.h).
+// lanes; a candidate's c is a handful of readlane compares.  Heaps, sifts and the argument block are beam_heap.h's.
+//
+// The bank's bookkeeping (pool slot, stores, copies) and the candidate's arithmetic are written out here and are NOT beam_heap.h's
+// BeamBank / beam_candidate: through them this kernel ran 1-2 % slower alone (19.76 against 19.61 us per round at 5x2, 38.09 against
+// 37.28 at 4x4, profiles/beam_bank_time.md), and so did this body with only the helper and the Lmax clamp of the copy loops added (19.86,
+// 38.07).  Keep the steps in step with BeamBank's; the copy loops rely on the host's Lmax (captions end below it), as they always have.
 #include "beam_heap.h"
 
 #include <cmath>
@@ -166,13 +171,9 @@ extern "C" int vc_beam_update_groups(void* stream, int B, int groups, int w, int
     VC_CHECK_ARG(kc >= w && kc <= groups * w, "candidates per row must be min(groups * group size, vocabulary) and at least the group size");
     VC_CHECK_ARG(std::isfinite(diversity) && diversity >= 0, "diversity must be finite and >= 0");
     VC_CHECK_ARG((long)B * groups * w <= 0x7fffffffL, "too many rows");
-    VC_CHECK_ARG(top_p && top_i && pcount && ccount && p_score && p_logprob && p_len && sent_cur && sent_next && c_score &&
-                 c_logprob && c_len && c_slot && c_free && c_sent && parent && tok, "null pointer");
-    BeamArgs a;
-    a.B = B; a.n = w; a.k = kc; a.Lmax = Lmax; a.eos = eos; a.len_norm_f = len_norm_f;
-    a.tv = top_p; a.ti = top_i; a.pcount = pcount; a.ccount = ccount; a.p_len = p_len; a.c_len = c_len; a.c_slot = c_slot;
-    a.c_free = c_free; a.p_score = p_score; a.p_logprob = p_logprob; a.c_score = c_score; a.c_logprob = c_logprob;
-    a.sent_cur = sent_cur; a.sent_next = sent_next; a.c_sent = c_sent; a.parent = parent; a.tok = tok;
+    const BeamArgs a = beam_args(B, w, kc, Lmax, eos, len_norm_f, top_p, top_i, pcount, ccount, p_score, p_logprob, p_len, sent_cur, sent_next,
+                                 c_score, c_logprob, c_len, c_slot, c_free, c_sent, parent, tok);
+    VC_CHECK_ARG(top_p && top_i && beam_state_given(a), "null pointer");
     hipLaunchKernelGGL(beam_update_groups_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a, groups, diversity);
     VC_LAUNCH_CHECK();
     return 0;

@@ -17,8 +17,8 @@
 #include <float.h>
 #include <limits.h>
 
+#include "beam_heap.h"
 #include "row_ops.h"
-#include "vaecap.h"
 
 namespace vc {
 
@@ -295,15 +295,7 @@ __global__ __launch_bounds__(64) void sbs_update_kernel(SbsState a, int kc, cons
 __global__ __launch_bounds__(256) void sbs_init_kernel(SbsState a, int H, const float* __restrict__ c_in, const float* __restrict__ h_in,
                                                        float* __restrict__ c_out, float* __restrict__ h_out, int32_t* __restrict__ sent_cur) {
     const long M = (long)a.B * a.n, stride = (long)gridDim.x * 256, t0 = (long)blockIdx.x * 256 + threadIdx.x;
-    for (long i = t0; i < M * H; i += stride) {
-        const long src = (i / H) / a.n * H + i % H;
-        c_out[i] = c_in[src];
-        h_out[i] = h_in[src];
-    }
-    for (long i = t0; i < M * a.Lmax; i += stride) {
-        sent_cur[i] = a.bos;
-        a.sent_next[i] = 0;
-    }
+    beam_rows_init(M, a.n, a.Lmax, H, a.bos, t0, stride, c_in, h_in, c_out, h_out, sent_cur, a.sent_next);
     for (long i = t0; i < M; i += stride) {
         a.p_phi[i] = 0.0; a.p_G[i] = 0.0; a.p_len[i] = 1;
         a.p_done[i] = i % a.n == 0 ? 0 : 1;
