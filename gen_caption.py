@@ -4,9 +4,10 @@
 
     python gen_caption.py --img_path cat.jpg --checkpoint ./checkpoints/last_run.ckpt \\
         --params_path ./pickles/params_Normal_False_last_run_False.pickle --vocab_path ./pickles/capt_vocab.pickle \\
-        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam|constrained_beam|stochastic_beam] [--must_include "dog,puppy;frisbee"] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
+        [--gen_method greedy|beam_search|sample|diverse|marginal_greedy|marginal_beam|constrained_beam|stochastic_beam|contrastive] [--must_include "dog,puppy;frisbee"] [--beam_size 2] [--diverse_draws 20] [--marginal_draws 20] [--vgg_weights ./utils/vgg16_weights.npz]
         [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
         [--typical_p 1.0] [--min_p 0] [--eta_cutoff 0]   (sampled decoding: locally typical / min-p / eta sampling; not with --top_k / --top_p)
+        [--contrastive_k 5] [--contrastive_alpha 0.6]    (--gen_method contrastive: words looked ahead per round, weight of the similarity penalty)
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
 VGG16 fc2 features [1, 4096], imf_emb -> decoder (prior z) -> greedy / beam search, print the caption.
@@ -128,7 +129,7 @@ class Generator(object):
         return fc2.cpu().numpy(), img
 
     def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None, must_include=None,
-                         controls=None, typical_p=None, min_p=None, eta=None):
+                         controls=None, typical_p=None, min_p=None, eta=None, contrastive_k=None, contrastive_alpha=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
         "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
         the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
@@ -140,7 +141,8 @@ class Generator(object):
         controls (additive): a vae_captioning_amd.controls.DecodeControls -- no repeated n-gram, minimum length, repetition penalty,
         banned words -- for every gen_method but the marginal ones.  gen_method "stochastic_beam" (additive): beam_size distinct captions
         sampled without replacement (stochastic beam search); the record holds diverse's lists plus "logprob", "perturbed", "weight",
-        "norm_weight" and "kappa"."""
+        "norm_weight" and "kappa".  gen_method "contrastive" (additive): contrastive search over the contrastive_k most likely words with
+        the similarity penalty weighted by contrastive_alpha (each the params' unless given); the record also holds "logprob"."""
         if top_k is not None:
             self.params.top_k = int(top_k)
         if top_p is not None:
@@ -158,14 +160,17 @@ class Generator(object):
         feature_vector, image = self._get_features(img_path)
         c_v = self._c_v_generator(image) if self.params.use_c_v else None
         mode, own = self.gen_method, {}   # own: what this call gives the mode in place of its params defaults
-        if mode not in ("greedy", "beam_search", "sample", "diverse", "marginal_greedy", "marginal_beam", "constrained_beam", "stochastic_beam"):
-            raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam or stochastic_beam")
+        if mode not in ("greedy", "beam_search", "sample", "diverse", "marginal_greedy", "marginal_beam", "constrained_beam", "stochastic_beam", "contrastive"):
+            raise ValueError("gen_method must be greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam, stochastic_beam "
+                             "or contrastive")
         if mode in ("beam_search", "marginal_greedy", "marginal_beam", "stochastic_beam"):
             own["beam_size"] = int(beam_size)
         if mode == "diverse":
             own["draws"] = diverse_draws
         if mode in ("marginal_greedy", "marginal_beam"):
             own.update(method=mode, draws=marginal_draws)
+        if mode == "contrastive":
+            own.update(k=contrastive_k, alpha=contrastive_alpha)
         if mode == "constrained_beam":
             from vae_captioning_amd.constraints import parse_must_include
             w2i = self.data_dict.word2idx
@@ -181,7 +186,7 @@ if __name__ == "__main__":
     parser.add_argument("--vocab_path", default="./pickles/capt_vocab.pickle", help="Indices to words dictionary")
     parser.add_argument("--gpu", default="", help="Specify GPU number if use GPU")
     parser.add_argument("--c_v_generator", default=None, help="If use cluster vectors, specify tensorflow api model (unused, as in the reference)")
-    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam or stochastic_beam")
+    parser.add_argument("--gen_method", default="greedy", help="greedy, beam_search, sample, diverse, marginal_greedy, marginal_beam, constrained_beam, stochastic_beam or contrastive")
     parser.add_argument("--params_path", default=None, help="specify params pickle file")
     parser.add_argument("--beam_size", default=2, help="If using beam_search, specify beam_size; --gen_method stochastic_beam: distinct captions to sample (1..32)")
     parser.add_argument("--vgg_weights", default=None, help="vgg16_weights.npz for the feature extractor (additive flag)")
@@ -206,6 +211,10 @@ if __name__ == "__main__":
     parser.add_argument("--repetition_penalty", type=float, default=1.0, help="the logit of every word already in the caption is divided "
                                                                               "(positive) or multiplied (negative) by this (1..10; 1 = off)")
     parser.add_argument("--must_exclude", default=None, help="words the caption must not hold, e.g. \"a,the\" (vocabulary words or token ids)")
+    parser.add_argument("--contrastive_k", type=int, default=None, help="--gen_method contrastive: next words looked one decoder step ahead per "
+                                                                        "round (1..16; default: the params', 5)")
+    parser.add_argument("--contrastive_alpha", type=float, default=None, help="--gen_method contrastive: weight of the similarity penalty against "
+                                                                              "the word's probability ([0, 1], 0 = greedy; default: the params', 0.6)")
     parser.add_argument("--use_ema", action="store_true", help="caption with the averaged weights (<name>/ExponentialMovingAverage) that a "
                                                                "run with --ema_decay wrote into the checkpoint")
     args = parser.parse_args()
@@ -234,6 +243,12 @@ if __name__ == "__main__":
         parser.error("--eta_cutoff must be in [0, 1) (got %r)" % args.eta_cutoff)
     if args.gen_method == "stochastic_beam" and not 1 <= int(args.beam_size) <= 32:
         parser.error("--beam_size must be 1..32 with --gen_method stochastic_beam (got %s)" % args.beam_size)
+    if args.gen_method != "contrastive" and (args.contrastive_k is not None or args.contrastive_alpha is not None):
+        parser.error("--contrastive_k / --contrastive_alpha belong to --gen_method contrastive (got --gen_method %s)" % args.gen_method)
+    if args.contrastive_k is not None and not 1 <= args.contrastive_k <= 16:
+        parser.error("--contrastive_k must be 1..16 (got %d)" % args.contrastive_k)
+    if args.contrastive_alpha is not None and not (0.0 <= args.contrastive_alpha <= 1.0):
+        parser.error("--contrastive_alpha must be in [0, 1] (got %r)" % args.contrastive_alpha)
     if args.gpu != "":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
@@ -244,7 +259,7 @@ if __name__ == "__main__":
         words = [int(w) if w.lstrip("-").isdigit() else w for w in (x.strip() for x in (args.must_exclude or "").split(",")) if w]
         controls = DecodeControls(args.no_repeat_ngram, args.min_len, args.repetition_penalty, parse_banned(words, generator.data_dict))
     caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws, args.must_include,
-                                         controls, args.typical_p, args.min_p, args.eta_cutoff)
+                                         controls, args.typical_p, args.min_p, args.eta_cutoff, args.contrastive_k, args.contrastive_alpha)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

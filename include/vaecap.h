@@ -53,6 +53,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the unlikelihood-training entries vc_softmax_xent_ul_f32, vc_ul_stats_f32.
  *      Added within 4 (additive, no layout change): the bag-of-words loss entries vc_bow_xent_f32, vc_bow_stats_f32.
  *      Added within 4 (additive, no layout change): the typical / min-p / eta sampling entry vc_decode_pick_typical_f32.
+ *      Added within 4 (additive, no layout change): the contrastive-search entry vc_contrastive_pick_f32.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -732,6 +733,38 @@ int vc_diverse_rank(void* stream, long rows, int B, int K, int Lmax, const int32
 int vc_decode_controls_f32(void* stream, float* logits, long rows, int V, long ld, const int32_t* hist, long hist_ld, int Lmax, int skip,
                            const int32_t* len, const int32_t* done, int ngram, int min_len, int eos, float penalty, const int32_t* banned,
                            int n_banned);
+
+/* ------------------------------------------------------------------------------------
+ * Contrastive search (csrc/contrastive.hip; generate.py: CaptionGenerator.contrastive_search; Su et al., NeurIPS 2022; DESIGN.md
+ * "Contrastive search").  A deterministic decoder that scores a word by its probability AND by how unlike the caption's earlier
+ * decoder states the state it leads to is.  Definition (normative): a row has emitted y_1..y_n (y_0 = <BOS>); g_j is the decoder
+ * LSTM's output h after feeding y_j, j = 0..n (the vector decoder/rnn_logits reads; the z step's state is no part of the history), and
+ * G_j = g_j / ||g_j||.  p = softmax (temperature 1) of the logits of g_n, after vc_decode_controls_f32 when controls are given.  The
+ * candidates v_1..v_k are the first k words of p under vc_topk_rows_f32's stable descending order, k = min(contrastive_k, V), and h_i is
+ * the LSTM output after feeding v_i from the row's state.
+ *     sim_i = max_{j = 0..n} <h_i, G_j> / ||h_i||       (0 when ||h_i|| = 0, 0 over an empty history)
+ *     s_i   = (1 - alpha) * p(v_i) - alpha * sim_i
+ * The pick is the largest s_i, equal s going to the lower rank.  The row appends v_pick, adds (double)logf(p(v_pick)) to its
+ * log-probability (f32 log of the f32 probability, f64 sum: vc_beam_update's), continues from the picked row's (c, h), appends
+ * h_pick / ||h_pick|| to its history and is done once v_pick == eos.  alpha = 0 or k = 1 is greedy decoding; alpha = 1 ignores the
+ * likelihood inside the top k.
+ *   vc_contrastive_pick_f32  one round's pick, one workgroup per row.  h2 [rows * k, H]: the look-ahead outputs, row r * k + i for
+ *     candidate i of row r; cand_tok / cand_p [rows, k]: the candidates' words and probabilities; hist [rows, Lmax + 1, H]: the unit
+ *     vectors G_j, of which row r holds len[r] + (emit ? 1 : 0); seq [rows, Lmax], len, done [rows], logprob [rows] (float64): the rows'
+ *     captions so far.  For a row with done == 0: hist[r, len + emit] = h_pick / ||h_pick|| (h_pick itself when its norm is 0),
+ *     h_sel [rows, H] row r = h_pick (as it is: the operand of the next logits product), parent[r * k + i] = r * k + pick for every
+ *     i < k (what vc_beam_gather_f32 takes to continue all k rows of the next round from the picked state), pick[r] = the rank and
+ *     score[r, i] = s_i when those are not NULL; and with emit != 0: seq[r, len] = v_pick, len += 1, logprob += (double)logf(p_pick),
+ *     done = (v_pick == eos).  emit == 0 leaves seq / len / logprob / done alone: the <BOS> round, which feeds <BOS> (k = 1, empty
+ *     history) and only starts the history.  A row with done != 0, or one that already holds Lmax words under emit, writes nothing.
+ *     Every history vector is read once per wave and multiplied into the wave's candidates, which stay in registers (H <= 1024);
+ *     sums in a fixed order that depends on H alone, vector stores only, no atomics: a row's outputs do not depend on rows, on its
+ *     place in the launch or on the call.  VC_EINVAL before any device work: a NULL pointer (pick, score may be NULL), k outside
+ *     1..16, H no positive multiple of 4, Lmax < 1, h2 / hist / h_sel not 16-byte aligned, alpha outside [0, 1] or no number.
+ *     rows == 0 launches nothing. */
+int vc_contrastive_pick_f32(void* stream, long rows, int k, int H, int Lmax, const float* h2, const int32_t* cand_tok, const float* cand_p,
+                            float* hist, int32_t* len, int32_t* done, int32_t* seq, double* logprob, float alpha, int eos, int emit,
+                            float* h_sel, int32_t* parent, int32_t* pick, float* score);
 
 /* ------------------------------------------------------------------------------------
  * Stochastic beam search (csrc/sbs.hip; generate.py: CaptionGenerator.stochastic_beam_search; Kool, van Hoof, Welling, ICML 2019): per

@@ -1538,3 +1538,93 @@ class CaptionGenerator(object):
                                  [ibuf, dbuf, parent, tok, ck, cl, ci, rnd, base, pending, cg, hg, xproj, gd, c0, h0, self._ones_for(M)]
                                  + ([ban_t] if ctl is not None else []) + list(bufs.values()), one, reset, K, max_len, check_every, pending)
         return sbs_from_host(*self._to_host(tag, ibuf, dbuf), lay.off, B, n, L, steps, int(eos))
+
+    # ------------------------------------------------------------------ contrastive search
+    def contrastive_search(self, features, c_v=None, eps=None, bos=1, eos=2, k=5, alpha=0.6, max_len=None, check_every=4, controls=None):
+        """Contrastive search (Su et al., NeurIPS 2022; DESIGN.md "Contrastive search"; the definition is in include/vaecap.h) for a batch
+        of images: every round looks one decoder step ahead for the k most likely next words of a row and takes the word that is likely
+        AND whose decoder state is unlike every state the caption has produced so far: the largest (1 - alpha) * p(v) - alpha * max_j
+        cos(h_v, g_j), equal scores to the more likely word.  The states are the decoder LSTM's outputs (what rnn_logits reads).
+        Deterministic; alpha = 0 or k = 1 is greedy().  Returns per image (tokens, logprob): the words up to and including <EOS> (max_len
+        of them without it) and the sum of their log-probabilities (f32 terms, f64 sum).
+        One round, all on the current stream: vc_beam_gather_f32 (the picked state to the B*k look-ahead rows, the candidates' input
+        projections from _project_vocab's table when _xproj_for says it pays) -> step(want="state") on B*k rows ->
+        vc_contrastive_pick_f32 -> the logits product on the B picked rows only -> (controls, against the rows' words so far) ->
+        softmax + top-k into the candidate buffers -> vc_decode_round_end_i32.  Rounds replay as hipGraph chunks of check_every rounds
+        with a 4-byte "all ended" read between chunks (VC_DECODE_GRAPH=0: the eager loop, same kernels, same result).  The <BOS> round
+        runs once before them on B rows: the pick kernel with k = 1 and emit = 0 starts the history.
+        There is no temperature in this mode: p is the model's distribution (after the controls).  controls: a
+        controls.DecodeControls; p, the top k and logprob are then taken under the processed distribution, as in the other decoders."""
+        lib, e, p = self.lib, self.e, self.p
+        k_, alpha = int(k), float(alpha)
+        if k_ != k or k_ < 1 or k_ > 16:
+            raise ValueError("contrastive_search: k must be 1..16, got %r" % (k,))
+        if not (0.0 <= alpha <= 1.0):   # (a NaN fails both comparisons)
+            raise ValueError("contrastive_search: alpha must be finite and in [0, 1], got %r" % (alpha,))
+        max_len = int(max_len or p.gen_max_len)
+        ctl = self._checked_controls(controls, eos, max_len)
+        c0, h0 = self.init_state(features, c_v, eps)
+        B, Hd, V, E = int(c0.shape[0]), p.decoder_hidden, e.V, p.embed_size
+        k = min(k_, V)
+        M, i32 = B * k, torch.int32
+        fused = k <= 8   # (the fused softmax-top-k holds 8 candidates: _beam_part's rule)
+        tag = "cs%d_%d_%d_" % (B, k, max_len)
+        cand = self._candidates(tag, B, max_len)
+        hist, h_sel = self._b(tag + "hist", (B, max_len + 1, Hd)), self._b(tag + "h_sel", (B, Hd))
+        logits, probs = self._b(tag + "logits", (B, V)), (None if fused else self._b(tag + "probs", (B, V)))
+        tv, ti, parent = self._b(tag + "tv", (B, k)), self._b(tag + "ti", (B, k), i32), self._b(tag + "parent", (M,), i32)
+        tv0, ti0, parent0 = self._b(tag + "tv0", (B, k)), self._b(tag + "ti0", (B, k), i32), self._b(tag + "parent0", (M,), i32)
+        tok0, pending = self._b(tag + "tok0", (B,), i32), self._b(tag + "pending", (1,))
+        cg, hg = self._b(tag + "cg", (M, Hd)), self._b(tag + "hg", (M, Hd))
+        bufs = {"x": self._b(tag + "x", (M, E)), "gact": self._b(tag + "gact", (M, 4 * Hd)), "c2": self._b(tag + "c2", (M, Hd)),
+                "h2": self._b(tag + "h2", (M, Hd))}
+        bufs0 = {"x": self._b(tag + "x0", (B, E)), "gact": self._b(tag + "gact0", (B, 4 * Hd)), "c2": self._b(tag + "c20", (B, Hd)),
+                 "h2": self._b(tag + "h20", (B, Hd))}
+        ban_t = self._controls_table(tag, ctl) if ctl is not None else None
+        xproj = self._xproj_for(M, max_len)
+        self._pack_wh(M)
+        e._need_ws(lib.vc_gemm_workspace_bytes(B, V, Hd))
+        W, bias = e.store.param("decoder/rnn_logits/kernel"), e.store.param("decoder/rnn_logits/bias")
+
+        def tail(timed):   # h_sel -> the rows' next candidates: the logits product runs over B rows, not B*k
+            s_ = _stream()
+            e.gemm(0, 0, B, V, Hd, h_sel, Hd, W, e.Vp, logits, V, bias, tag="logits_gemm" if timed else None)
+            if ctl is not None:
+                self._apply_controls(ctl, ban_t, logits, B, cand.seq, max_len, 0, cand.len, cand.ended, eos)
+            if fused:
+                lib.vc_softmax_topk_rows_f32(s_, P(logits), B, V, V, k, P(tv), P(ti))
+            else:
+                lib.vc_softmax_rows_f32(s_, P(logits), B, V, V, P(probs), V)
+                lib.vc_topk_rows_f32(s_, P(probs), B, V, V, k, P(tv), P(ti))
+
+        # ---- the <BOS> round, once per call on B rows: g_0 starts the history (k = 1, emit = 0: no word is emitted, ti / tv are not read
+        # for a decision), its logits give the first candidates; every look-ahead row r*k + i of round 0 continues row r of its state
+        cand.ended.zero_(); cand.len.zero_(); cand.logprob.zero_()
+        tok0.fill_(bos)
+        _, c1, h1 = self.step(tok0, c0, h0, want="state", bufs=bufs0)
+        lib.vc_contrastive_pick_f32(_stream(), B, 1, Hd, max_len, P(h1), P(ti), P(tv), P(hist), P(cand.len), P(cand.ended), P(cand.seq),
+                                    P(cand.logprob), alpha, int(eos), 0, P(h_sel), P(parent0), None, None)
+        tail(True)
+        tv0.copy_(tv); ti0.copy_(ti)
+        parent0.copy_(torch.arange(M, dtype=i32, device=e.dev) // k)
+
+        def reset():   # what round 0 starts from (the history's slot 0 is never written again)
+            tv.copy_(tv0); ti.copy_(ti0); parent.copy_(parent0)
+            bufs["c2"][:B].copy_(c1); bufs["h2"][:B].copy_(h1)
+            cand.ended.zero_(); cand.len.zero_(); cand.logprob.zero_()
+
+        def one(r, timed):
+            s_ = _stream()
+            lib.vc_beam_gather_f32(s_, P(bufs["c2"]), P(bufs["h2"]), P(parent), M, Hd, P(cg), P(hg), P(xproj), P(ti), V, 4 * Hd, P(bufs["gact"]))
+            self.step(ti.view(M), cg, hg, want="state", bufs=bufs, timed=timed, projected=xproj is not None)
+            lib.vc_contrastive_pick_f32(s_, B, k, Hd, max_len, P(bufs["h2"]), P(ti), P(tv), P(hist), P(cand.len), P(cand.ended), P(cand.seq),
+                                        P(cand.logprob), alpha, int(eos), 1, P(h_sel), P(parent), None, None)
+            tail(timed)
+            lib.vc_decode_round_end_i32(s_, P(cand.ended), B, P(pending), None)
+
+        K = self._chunk_rounds(check_every)
+        self._run_chunks(("contrastive", B, k, max_len, K, float(alpha), int(eos)) + (ctl.key() if ctl is not None else ()),
+                         [cand.seq, cand.len, cand.ended, cand.logprob, hist, h_sel, logits, probs, tv, ti, parent, tv0, ti0, parent0, pending,
+                          cg, hg, xproj, c1, h1, self._ones_for(M), ban_t] + list(bufs.values()), one, reset, K, max_len, check_every, pending)
+        rows, lens, lps = cand.seq.cpu().numpy(), cand.len.cpu().numpy(), cand.logprob.cpu().numpy()
+        return [(rows[b, :lens[b]].tolist(), float(lps[b])) for b in range(B)]

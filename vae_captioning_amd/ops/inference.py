@@ -22,6 +22,8 @@ caption's log-likelihood over the draws) and `"draws"`.
 `sample_gen == "constrained_beam"` (additive): constrained beam search (`decoder.constrained_beam_search` with the
 `constraints.Constraints` attached to the decoder); the records of `./val_{gen_name}.json` gain `"constraints"` (the token ids used),
 `"satisfied"` (one bool per constraint) and `"score"`.
+`sample_gen == "contrastive"` (additive): contrastive search (`decoder.contrastive_search`, `params.contrastive_k` /
+`params.contrastive_alpha`); the records of `./val_{gen_name}.json` gain `"logprob"` (the log-probability of the caption's words).
 `params.score_draws = K >= 1` (additive): the validation images' HUMAN captions are also scored under K prior draws
 (`decoder.score_captions`) -> `./val_{gen_name}_scores.json`, and the corpus perplexity exp(-sum marginal / sum tokens) is printed.
 `params.bound_draws = K >= 1` (additive): the same human captions are bounded with K draws from the model's own posterior
@@ -145,7 +147,7 @@ def store_bounds(params, bound_records, stats):
 
 EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "diverse_rerank", "consensus_k", "consensus_m", "beam_groups",
               "beam_diversity", "top_k", "top_p", "typical_p", "min_p", "eta", "marginal_draws", "constraints", "cbs_width",
-              "no_repeat_ngram", "min_len", "repetition_penalty", "banned_words")
+              "no_repeat_ngram", "min_len", "repetition_penalty", "banned_words", "contrastive_k", "contrastive_alpha")
 
 
 def store_metrics(params, metrics, images, captions):

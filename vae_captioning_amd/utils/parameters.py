@@ -28,7 +28,7 @@ _DEFAULTS = dict(
     diverse_draws=20, diverse_method="greedy", diverse_rerank="likelihood", consensus_k=90, consensus_m=125,
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, typical_p=1.0, min_p=0.0, eta=0.0, eval_captions=False, eval_self_cider=False,
     bound_draws=0, bound_mi=0, marginal_draws=20, constraints=None, cbs_width=0,
-    no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None,
+    no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None, contrastive_k=5, contrastive_alpha=0.6,
     # training objective options (every one off by default: the reference's objective)
     kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
     # self-critical training (off by default)
@@ -71,6 +71,7 @@ _FLAGS = [
     ("--constraints", "constraints", str, None), ("--cbs_width", "cbs_width", int, None),
     ("--no_repeat_ngram", "no_repeat_ngram", int, None), ("--min_len", "min_len", int, None),
     ("--repetition_penalty", "repetition_penalty", float, None), ("--banned_words", "banned_words", str, None),
+    ("--contrastive_k", "contrastive_k", int, None), ("--contrastive_alpha", "contrastive_alpha", float, None),
     ("--kl_free_bits", "kl_free_bits", float, None), ("--kl_weight", "kl_weight", float, None),
     ("--kl_cycle_steps", "kl_cycle_steps", int, None), ("--kl_cycle_ramp", "kl_cycle_ramp", float, None),
     ("--kl_cycles", "kl_cycles", int, None), ("--label_smoothing", "label_smoothing", float, None),
@@ -143,6 +144,10 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
                                  "(negative) by this (1..10; default 1.0 = off)",
          "--banned_words": "decoding controls: JSON file with a list of words (vocabulary strings or integer token ids, at most 256) that "
                            "no caption may hold; not with --sample_gen marginal_greedy / marginal_beam, like the three flags above",
+         "--contrastive_k": "--sample_gen contrastive: next words looked one decoder step ahead per round (1..16; default 5; 1 = greedy)",
+         "--contrastive_alpha": "--sample_gen contrastive: weight of the degeneration penalty, the largest cosine similarity between a "
+                                "candidate's decoder state and the states of the caption so far, against the word's probability "
+                                "(in [0, 1]; default 0.6; 0 = greedy)",
          "--kl_free_bits": "training objective: KL floor in nats per latent dimension and caption row (free bits: a dimension whose KL "
                            "is at or below it is held at the floor and gets no KL gradient; >= 0; default 0 = off)",
          "--kl_weight": "training objective: weight beta of the KL term in the lower bound and its gradient (> 0; default 1.0)",
@@ -189,7 +194,9 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--sample_gen": "decoding of the validation images: beam_search (default), greedy, sample, diverse, diverse_beam, or the search "
                          "under the mixture of --marginal_draws latent draws: marginal_greedy, marginal_beam (--beam_size beams, 1..16), or "
                          "constrained_beam: beam search whose captions mention the words of --constraints, or stochastic_beam: --beam_size "
-                         "distinct captions sampled without replacement, each with its probability and importance weight"}
+                         "distinct captions sampled without replacement, each with its probability and importance weight, or "
+                         "contrastive: contrastive search over the --contrastive_k most likely words (deterministic; --contrastive_alpha "
+                         "weighs the similarity of a word's decoder state to the caption's earlier ones against its probability)"}
 
 
 class Parameters(object):
@@ -265,6 +272,16 @@ class Parameters(object):
                 ap.error("--cbs_width must be 0..16 (0 = the largest that fits; got %d)" % self.cbs_width)
         elif self.constraints is not None or args["cbs_width"] is not None:
             ap.error("--constraints / --cbs_width belong to --sample_gen constrained_beam (got --sample_gen %s)" % self.sample_gen)
+        if self.sample_gen == "contrastive":
+            if not 1 <= self.contrastive_k <= 16:
+                ap.error("--contrastive_k must be 1..16 (got %d)" % self.contrastive_k)
+            if not (0.0 <= self.contrastive_alpha <= 1.0):
+                ap.error("--contrastive_alpha must be in [0, 1] (got %r)" % self.contrastive_alpha)
+            if self.temperature != 1.0:
+                ap.error("--temperature must be 1 with --sample_gen contrastive: its scores weigh the model's own probabilities "
+                         "against a similarity (got %r)" % self.temperature)
+        elif args["contrastive_k"] is not None or args["contrastive_alpha"] is not None:
+            ap.error("--contrastive_k / --contrastive_alpha belong to --sample_gen contrastive (got --sample_gen %s)" % self.sample_gen)
         if not 0 <= self.no_repeat_ngram <= 8:
             ap.error("--no_repeat_ngram must be 0..8 (0 = off; got %d)" % self.no_repeat_ngram)
         if not 0 <= self.min_len < self.gen_max_len:

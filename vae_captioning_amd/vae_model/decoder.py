@@ -10,7 +10,8 @@ from ..generate import CaptionGenerator
 
 DECODE_METHODS = {"greedy": "online_inference", "sample": "online_inference", "beam_search": "beam_search", "diverse": "diverse_inference",
                   "diverse_beam": "diverse_beam_search", "stochastic_beam": "stochastic_beam_search", "marginal_greedy": "marginal_inference",
-                  "marginal_beam": "marginal_inference", "constrained_beam": "constrained_beam_search"}   # decode mode -> the method that runs it
+                  "marginal_beam": "marginal_inference", "constrained_beam": "constrained_beam_search",
+                  "contrastive": "contrastive_search"}   # decode mode -> the method that runs it
 DIVERSE_FILE_MODES = ("diverse", "diverse_beam", "stochastic_beam")   # their full per-image lists are also written to val_{gen_name}_diverse.json
 
 
@@ -267,6 +268,21 @@ class Decoder(object):
                              "constraints": [[int(v) for v in st] for st in sets],
                              "satisfied": [bool((state >> j) & 1) for j in range(len(sets))], "score": score})
         self.last_token_ids = token_ids
+        return cap_list
+
+    def contrastive_search(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, k=None, alpha=None):
+        """Contrastive search (Su et al. 2022; generate.py: contrastive_search): every round the `k` (params.contrastive_k, 1..16) most
+        likely next words are looked one decoder step ahead, and the word taken is likely and leads to a decoder state unlike those of
+        the caption so far, weighted by `alpha` (params.contrastive_alpha, in [0, 1]; 0 = greedy).  Deterministic.  Returns cap_list:
+        per image {"image_id", "caption", "logprob": the log-probability of the caption's words}."""
+        self.last_token_ids = None
+        bos, eos, use_cv = self._call(c_v)
+        k = int(k if k is not None else getattr(self.params, "contrastive_k", 5))
+        alpha = float(alpha if alpha is not None else getattr(self.params, "contrastive_alpha", 0.6))
+        res = self._gen().contrastive_search(self._features(in_pictures), use_cv, None, bos, eos, k=k, alpha=alpha,
+                                             max_len=self.params.gen_max_len, controls=self.controls)
+        cap_list = [{"image_id": pid, "caption": self._text(toks, (bos, eos)), "logprob": float(lp)} for pid, (toks, lp) in zip(picture_ids, res)]
+        self.last_token_ids = [[list(toks)] for toks, _ in res]
         return cap_list
 
     def marginal_inference(self, sess, picture_ids, in_pictures, image_f_inputs, c_v=None, method=None, draws=None, beam_size=None,
