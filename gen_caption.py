@@ -8,6 +8,7 @@
         [--top_k 0] [--top_p 1.0]     (sampled decoding: draw from the k best words / the nucleus holding a share p; default: the params')
         [--typical_p 1.0] [--min_p 0] [--eta_cutoff 0]   (sampled decoding: locally typical / min-p / eta sampling; not with --top_k / --top_p)
         [--contrastive_k 5] [--contrastive_alpha 0.6]    (--gen_method contrastive: words looked ahead per round, weight of the similarity penalty)
+        [--diverse_select dpp] [--select_n 5] [--dpp_quality 1.0]   (--gen_method diverse / stochastic_beam: keep select_n captions chosen jointly for quality and difference)
 
 Flow (gen_caption.py:73-130): load the pickled Parameters and the vocabulary, decode + resize the image,
 VGG16 fc2 features [1, 4096], imf_emb -> decoder (prior z) -> greedy / beam search, print the caption.
@@ -129,7 +130,8 @@ class Generator(object):
         return fc2.cpu().numpy(), img
 
     def generate_caption(self, img_path, beam_size=2, diverse_draws=None, top_k=None, top_p=None, marginal_draws=None, must_include=None,
-                         controls=None, typical_p=None, min_p=None, eta=None, contrastive_k=None, contrastive_alpha=None):
+                         controls=None, typical_p=None, min_p=None, eta=None, contrastive_k=None, contrastive_alpha=None, diverse_select=None,
+                         select_n=None, dpp_quality=None):
         """-> [{'image_id': file name, 'caption': text}]  (gen_caption.py:73-130).  gen_method "diverse" (additive): the record also holds
         "captions" / "scores" / "counts", every distinct caption of `diverse_draws` latent draws, best first.  top_k / top_p (additive):
         the truncation of sampled decoding ("sample", "diverse" with params.diverse_method "sample"), like the temperature taken from
@@ -142,7 +144,14 @@ class Generator(object):
         banned words -- for every gen_method but the marginal ones.  gen_method "stochastic_beam" (additive): beam_size distinct captions
         sampled without replacement (stochastic beam search); the record holds diverse's lists plus "logprob", "perturbed", "weight",
         "norm_weight" and "kappa".  gen_method "contrastive" (additive): contrastive search over the contrastive_k most likely words with
-        the similarity penalty weighted by contrastive_alpha (each the params' unless given); the record also holds "logprob"."""
+        the similarity penalty weighted by contrastive_alpha (each the params' unless given); the record also holds "logprob".
+        diverse_select "dpp" (additive; gen_method "diverse" / "stochastic_beam"): select_n of the image's captions chosen jointly for
+        quality and for difference from each other (DPP selection, quality weight dpp_quality; each the params' unless given); the
+        record's lists hold them in selection order and gain "dpp_gain" and "dpp_chosen".  No training captions are at hand here, so
+        the in-set CIDEr-D behind the selection weighs every n-gram alike (idf 1) where main.py uses the training captions' idf."""
+        for name, val, conv in (("diverse_select", diverse_select, str), ("select_n", select_n, int), ("dpp_quality", dpp_quality, float)):
+            if val is not None:
+                setattr(self.params, name, conv(val))
         if top_k is not None:
             self.params.top_k = int(top_k)
         if top_p is not None:
@@ -156,6 +165,14 @@ class Generator(object):
         self._build()
         decoder = Decoder(None, None, None, self.params, self.data_dict)
         decoder.controls = controls
+        if getattr(self.params, "diverse_select", "none") == "dpp":
+            if self.gen_method not in ("diverse", "stochastic_beam"):
+                raise ValueError("diverse_select dpp selects from a list of captions: gen_method diverse or stochastic_beam")
+            import torch
+            from vae_captioning_amd.mbr import CiderGram
+            w2i, dev = self.data_dict.word2idx, self._trainer.cap.dev
+            empty = (torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.float32, device=dev), 0, 1.0)
+            decoder.mbr = CiderGram(self._trainer.cap, None, w2i["<BOS>"], w2i["<EOS>"], df_table=empty)   # no df table: every n-gram's idf is 1
         im_id = [img_path.split("/")[-1]]
         feature_vector, image = self._get_features(img_path)
         c_v = self._c_v_generator(image) if self.params.use_c_v else None
@@ -215,6 +232,11 @@ if __name__ == "__main__":
                                                                         "round (1..16; default: the params', 5)")
     parser.add_argument("--contrastive_alpha", type=float, default=None, help="--gen_method contrastive: weight of the similarity penalty against "
                                                                               "the word's probability ([0, 1], 0 = greedy; default: the params', 0.6)")
+    parser.add_argument("--diverse_select", default=None, choices=["none", "dpp"], help="--gen_method diverse / stochastic_beam: dpp keeps "
+                        "--select_n captions chosen jointly for quality and for difference from each other (default: the params')")
+    parser.add_argument("--select_n", type=int, default=None, help="--diverse_select dpp: captions kept (1..32; default: the params', 5)")
+    parser.add_argument("--dpp_quality", type=float, default=None, help="--diverse_select dpp: the best-ranked caption weighs e^W times the "
+                                                                        "worst ([0, 8], 0 = diversity alone; default: the params', 1.0)")
     parser.add_argument("--use_ema", action="store_true", help="caption with the averaged weights (<name>/ExponentialMovingAverage) that a "
                                                                "run with --ema_decay wrote into the checkpoint")
     args = parser.parse_args()
@@ -249,6 +271,14 @@ if __name__ == "__main__":
         parser.error("--contrastive_k must be 1..16 (got %d)" % args.contrastive_k)
     if args.contrastive_alpha is not None and not (0.0 <= args.contrastive_alpha <= 1.0):
         parser.error("--contrastive_alpha must be in [0, 1] (got %r)" % args.contrastive_alpha)
+    if args.diverse_select == "dpp" and args.gen_method not in ("diverse", "stochastic_beam"):
+        parser.error("--diverse_select dpp belongs to --gen_method diverse / stochastic_beam (got --gen_method %s)" % args.gen_method)
+    if args.diverse_select != "dpp" and (args.select_n is not None or args.dpp_quality is not None):
+        parser.error("--select_n / --dpp_quality belong to --diverse_select dpp")
+    if args.select_n is not None and not 1 <= args.select_n <= 32:
+        parser.error("--select_n must be 1..32 (got %d)" % args.select_n)
+    if args.dpp_quality is not None and not (0.0 <= args.dpp_quality <= 8.0):
+        parser.error("--dpp_quality must be in [0, 8] (got %r)" % args.dpp_quality)
     if args.gpu != "":
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
     generator = Generator(checkpoint_path=args.checkpoint, params_path=args.params_path, vocab_path=args.vocab_path,
@@ -259,7 +289,8 @@ if __name__ == "__main__":
         words = [int(w) if w.lstrip("-").isdigit() else w for w in (x.strip() for x in (args.must_exclude or "").split(",")) if w]
         controls = DecodeControls(args.no_repeat_ngram, args.min_len, args.repetition_penalty, parse_banned(words, generator.data_dict))
     caption = generator.generate_caption(args.img_path, args.beam_size, args.diverse_draws, args.top_k, args.top_p, args.marginal_draws, args.must_include,
-                                         controls, args.typical_p, args.min_p, args.eta_cutoff, args.contrastive_k, args.contrastive_alpha)
+                                         controls, args.typical_p, args.min_p, args.eta_cutoff, args.contrastive_k, args.contrastive_alpha,
+                                         args.diverse_select, args.select_n, args.dpp_quality)
     if args.gen_method == "diverse":
         for text, score, count in zip(caption[0]["captions"], caption[0]["scores"], caption[0]["counts"]):
             print("%.4f x%d %s" % (score, count, text))

@@ -54,6 +54,7 @@ extern "C" {
  *      Added within 4 (additive, no layout change): the bag-of-words loss entries vc_bow_xent_f32, vc_bow_stats_f32.
  *      Added within 4 (additive, no layout change): the typical / min-p / eta sampling entry vc_decode_pick_typical_f32.
  *      Added within 4 (additive, no layout change): the contrastive-search entry vc_contrastive_pick_f32.
+ *      Added within 4 (additive, no layout change): the DPP selection entry vc_dpp_select_f64.
  *   3  the 3x3-convolution family (vc_conv3x3_wino_*, vc_conv3x3_wino4_*, vc_conv3x3_wino_wgrad_*, vc_conv1_fwd* / vc_conv1_wgrad*,
  *      vc_maxpool2x2_bwd_bits_f32) takes and returns activations in the C4 layout [B][C/4][H][W][4] (v2: NHWC) and the pool routing
  *      codes / ReLU mask bits follow it; the vc_conv3x3_patch_*, vc_conv3x3_pack_f32, *_packed_f32 and wgrad_patch_* entries of v2 are
@@ -856,6 +857,41 @@ int vc_consensus_score(void* stream, int B, int k, const int32_t* nbr, const int
  *                other images or the row's place in its group.  One workgroup per image and 4 rows, 12 KiB LDS. */
 int vc_cider_gram(void* stream, int B, const int32_t* cand_img, int max_cands, const int32_t* off, const int32_t* nnz, const uint64_t* keys,
                   const float* w, const float* norm, const int32_t* words, const double* weight, float* gram, long ld, double* mbr);
+
+/* ------------------------------------------------------------------------------------
+ * DPP selection (mbr.py: CiderGram.select; csrc/dpp.hip; DESIGN.md "DPP selection"): n of an image's m captions chosen jointly for
+ * quality and for difference from each other -- the fast greedy MAP of a determinantal point process (Chen, Zhang & Zhou, NeurIPS
+ * 2018) over the image's in-set CIDEr-D matrix.  Per image: m captions (0 <= m <= 256) in list order, their vc_cider_gram matrix G
+ * (f32), a positive quality q_i per caption (float64), a count n (1 <= n <= 32).  Everything below is float64.
+ *   similarity   S_ij = min(1, max(0, ((double)G_ij + (double)G_ji) / 20)) for i != j, S_ii = 1.  (CIDEr-D is scaled by 10 and is not
+ *                symmetric; the diagonal is SET, not read: an empty caption's self-score is 0.)
+ *   kernel       L_ij = q_i S_ij q_j.
+ *   state        d_i = q_i^2; no caption is taken; vectors c_t[.] exist for the steps t done so far.
+ *   step k = 0, 1, ... while fewer than min(n, m) captions are taken:
+ *                a caption is LIVE if it is not taken and d_i > DPP_EPS * q_i^2.  No caption live: stop.  Otherwise
+ *                j = argmax over the live i of d_i (equal values go to the lower index); sel[k] = j, gain[k] = d_j, j is taken.
+ *                For every untaken i: acc = q_j S_ji q_i; for t = 0 .. k-1 in ascending order acc -= c_t[j] * c_t[i];
+ *                e = acc / sqrt(d_j); c_k[i] = e; d_i -= e * e.
+ *   after        n_dpp = the number of steps taken.  Fewer than min(n, m) taken: the remaining slots hold the untaken captions in
+ *                ascending index with gain 0 (what is left are duplicates and numerically dependent captions; they go in rank order).
+ *                Slots at or past min(n, m): sel = -1, gain = 0.
+ * The steps maximise log det L_Y one element at a time; CIDEr-D's clipping means S need not be positive semidefinite, and the live
+ * rule makes the procedure well defined anyway.  When the qualities differ, sel[0] is the caption with the largest q.
+ *   dpp_select   cand_img [B + 1], gram and ld are vc_cider_gram's: table row i lives at gram + i * ld, image b owns the rows
+ *                cand_img[b] .. cand_img[b+1] - 1 (n_b <= max_cands; a longer list is cut at max_cands as vc_cider_gram cuts it), so
+ *                the selection runs on the block that call has just written.  q [C]: one quality per table row.  sel, gain [B, n],
+ *                n_dpp [B]; sel holds indices WITHIN the image.  n_b == 0: sel = -1, gain = 0, n_dpp = 0.
+ *                One workgroup per image, one lane per caption; d, q and the taken flags in registers, the c vectors in LDS (n x 256
+ *                doubles: 16 KiB up to n = 8, 64 KiB above); row j and column j of G are read once per step; the argmax is an
+ *                index-carrying xor shuffle tree per wave, then the four wave results through LDS in wave order.  No atomics; no
+ *                product is contracted into a fused multiply-add.  An image's outputs depend on its own rows, q and n only: not on B,
+ *                its place in the launch, max_cands or the call -- two calls give identical bits.
+ *                q_i finite and > 0 is the caller's to check (mbr.py does): the kernel does not.
+ *                VC_EINVAL before any device work: B < 0, max_cands outside 1..256, n outside 1..32, ld < max_cands, a NULL pointer
+ *                with B > 0.  B == 0 launches nothing (no pointer is looked at). */
+#define DPP_EPS 1e-9
+int vc_dpp_select_f64(void* stream, int B, const int32_t* cand_img, int max_cands, const float* gram, long ld, const double* q, int n,
+                      int32_t* sel, double* gain, int32_t* n_dpp);
 
 /* ------------------------------------------------------------------------------------
  * Evaluation of caption sets (evaluate.py: CaptionEvaluator; csrc/evaluate.hip): BLEU-style clipped n-gram counts.

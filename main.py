@@ -102,9 +102,9 @@ def consensus_index(params, tr, cap_dict, coco_train):
     return ConsensusIndex(tr.cap, feats, caps, bos, eos, k=params.consensus_k, m=params.consensus_m, vocab_size=cap_dict.vocab_size)
 
 
-def mbr_gram(params, tr, cap_dict, coco_train, real=None):
-    """--diverse_rerank mbr: the idf table of the training captions (per image; no features are read, so --fine_tune works) that the
-    in-set CIDEr-D of an image's captions is weighted with."""
+def mbr_gram(params, tr, cap_dict, coco_train, real=None, flag="--diverse_rerank mbr", what="mbr re-ranking"):
+    """--diverse_rerank mbr / --diverse_select dpp: the idf table of the training captions (per image; no features are read, so
+    --fine_tune works) that the in-set CIDEr-D of an image's captions is weighted with."""
     from vae_captioning_amd.mbr import CiderGram
     if real is not None:
         corpus = [real.caps[n] for n in real.names if real.caps[n]]
@@ -114,8 +114,8 @@ def mbr_gram(params, tr, cap_dict, coco_train, real=None):
     elif params.synthetic:
         corpus = training_index_data(params, None)[1]
     else:
-        raise SystemExit("--diverse_rerank mbr needs the MSCOCO training captions (--coco_dir) or --synthetic for its idf")
-    print("mbr re-ranking: idf over the captions of %d training images" % len(corpus))
+        raise SystemExit("%s needs the MSCOCO training captions (--coco_dir) or --synthetic for its idf" % flag)
+    print("%s: idf over the captions of %d training images" % (what, len(corpus)))
     return CiderGram(tr.cap, corpus, cap_dict.word2idx["<BOS>"], cap_dict.word2idx["<EOS>"], cap_dict.vocab_size)
 
 
@@ -357,6 +357,8 @@ def main(params):
             decoder.consensus_index = consensus_index(params, tr, cap_dict, coco_train)
         if params.sample_gen in ("diverse", "stochastic_beam") and params.diverse_rerank == "mbr":
             decoder.mbr = mbr_gram(params, tr, cap_dict, coco_train, real)
+        if getattr(params, "diverse_select", "none") == "dpp" and decoder.mbr is None:   # (the parser admits it in the three list modes only)
+            decoder.mbr = mbr_gram(params, tr, cap_dict, coco_train, real, "--diverse_select dpp", "dpp selection")
         if params.sample_gen == "constrained_beam":   # the words the captions must mention, looked up in the vocabulary once
             from vae_captioning_amd.constraints import load_constraints
             decoder.constraints = load_constraints(params.constraints, cap_dict.word2idx, cap_dict.vocab_size, cap_dict.word2idx["<BOS>"],
@@ -377,6 +379,7 @@ def main(params):
             return
         rng = np.random.default_rng(params.seed + 5)
         captions_gen, scores, bounds, references, decoded = [], [], [], [], []
+        selecting, ranked_gen = getattr(params, "diverse_select", "none") == "dpp", []
         for it in range(2):
             b = synth.make_batch(rng, params.batch_size, 1, 20, params.vocab_size, use_ci=spec.uses_ci(params), images=params.fine_tune)
             ids = ["synthetic_%06d" % (it * params.batch_size + i) for i in range(params.batch_size)]
@@ -393,6 +396,8 @@ def main(params):
                 for r in sent:
                     say("%s: %s" % (r["image_id"], " | ".join("%s (logp %.3f, w %.3g)" % (t, lp, w) for t, lp, w in zip(r["captions"], r["logprob"], r["norm_weight"]))))
             captions_gen += sent
+            # --diverse_select dpp: ./val_{gen_name}.json keeps the records of the whole ranked lists, the file of a run without the flag
+            ranked_gen += decoder.last_ranked_records if selecting else sent
             if params.eval_captions:   # the batch's own captions (one per image, by construction) are its "human" references
                 from vae_captioning_amd.ops.inference import decoded_ids, human_captions
                 references += human_captions((b["cap_dec"], b["cap_enc"]), b["lengths"])
@@ -406,7 +411,7 @@ def main(params):
         say("Generated {} captions".format(len(captions_gen)))
         if rank == 0:
             with open("./val_{}.json".format(params.gen_name), "w") as wj:
-                json.dump(captions_gen, wj)
+                json.dump(ranked_gen, wj)
             if params.sample_gen in DIVERSE_FILE_MODES:   # the full per-image lists under the name ops/inference.py gives them
                 with open("./val_{}_diverse.json".format(params.gen_name), "w") as wj:
                     json.dump(captions_gen, wj)

@@ -8,6 +8,9 @@ Both need one matrix per image: G[i][j] = CIDEr-D(hypothesis = caption i, refere
   decoder pass; the weights are how often each distinct caption was drawn (`diverse`) or the captions' `norm_weight` (stochastic beam
   search).  The sum runs over all j, i itself included.
 * Self-CIDEr (Wang & Chan, CVPR 2019): `self_cider(G)`, a function of the eigenvalues of the symmetrised matrix, on the host in float64.
+* DPP selection (Chen, Zhang & Zhou, NeurIPS 2018): `CiderGram.select`, n captions chosen jointly for quality and for difference from
+  each other -- greedy MAP of a determinantal point process whose kernel is the same symmetrised matrix scaled by the captions'
+  qualities (csrc/dpp.hip: vc_dpp_select_f64, on the device block vc_cider_gram has just written; the matrix is not copied to the host).
 
 `CiderGram` holds the df / idf table of a CORPUS (the training captions per image) on the device, as scst.CiderReward does; words, keys
 and limits are consensus.py's: token ids without <BOS>, <EOS> and PAD (0), at most 64 words per caption, ids <= 65535, at most 256
@@ -24,6 +27,7 @@ from .generate import DIVERSE_MAX_DRAWS
 
 ZERO_EIG = float(np.finfo(np.float64).eps)   # self_cider: eigenvalues up to ZERO_EIG * m * (the largest) are zeros (numpy.linalg.matrix_rank's rule)
 GRAM_BLOCK_BYTES = 256 << 20   # the [captions, ld] f32 block of one vc_cider_gram call stays under this (one image always goes)
+DPP_MAX_SELECT = 32            # vc_dpp_select_f64: captions selected per image (the c vectors of 32 steps x 256 captions fill 64 KiB of LDS)
 
 
 def self_cider(G):
@@ -70,16 +74,37 @@ def _launch(lib, B, cand_img, max_cands, v, weight, gram, ld, mbr):
                       gram, int(ld), mbr)
 
 
+def _blocks(lib, dev, v, cand_img_dev, per, start, wdev, mbr_dev):
+    """The chunk loop of gram_of_table and select_of_table: one vc_cider_gram call per chunk of `chunks(per, GRAM_BLOCK_BYTES)` into ONE
+    device block that every chunk reuses.  Yields (b0, b1, ld, r0, n, block, base) after a chunk's launch: images b0 .. b1 - 1, table
+    rows r0 .. r0 + n - 1, block[:n * ld] = their [n, ld] f32 rows, base = the `gram` pointer of the call (table row i lives at base +
+    4 * i * ld with i the row's index in the WHOLE table: the chunk's block starts at row r0).  Chunks without captions are skipped."""
+    parts = chunks(per, GRAM_BLOCK_BYTES)
+    rows_max = max(int(start[b1] - start[b0]) * ld for b0, b1, ld in parts)
+    block = torch.empty(max(1, rows_max), dtype=torch.float32, device=dev)
+    for b0, b1, ld in parts:
+        r0, n = int(start[b0]), int(start[b1] - start[b0])
+        if n == 0:
+            continue
+        base = P(block) - 4 * r0 * ld
+        _launch(lib, b1 - b0, P(cand_img_dev) + 4 * b0, int(per[b0:b1].max()), v, P(wdev), base, ld, P(mbr_dev))
+        yield b0, b1, ld, r0, n, block, base
+
+
+def _starts(per):
+    per = np.asarray(per, np.int64)
+    start = np.zeros(per.size + 1, np.int64)
+    start[1:] = np.cumsum(per)
+    return per, start
+
+
 def gram_of_table(lib, dev, v, cand_img_dev, per, weights=None):
     """The matrices and means of every image of an idf-weighted ngram_vectors table `v`: image b owns rows sum(per[:b]) .. +per[b],
     cand_img_dev is the device int32 [B + 1] array of those offsets, weights a host float64 [C] array or None (uniform).
     -> (G: per image float32 [n_b, n_b], mbr: per image float64 [n_b]).  Images go in `chunks` of GRAM_BLOCK_BYTES; a row's bits do not
     depend on its chunk."""
-    per = np.asarray(per, np.int64)
-    B = int(per.size)
-    start = np.zeros(B + 1, np.int64)
-    start[1:] = np.cumsum(per)
-    C = int(start[-1])
+    per, start = _starts(per)
+    B, C = int(per.size), int(start[-1])
     if C == 0:
         return [np.zeros((0, 0), np.float32) for _ in range(B)], [np.zeros(0, np.float64) for _ in range(B)]
     wdev = None
@@ -89,16 +114,8 @@ def gram_of_table(lib, dev, v, cand_img_dev, per, weights=None):
             raise ValueError("%d weights for %d captions" % (wh.size, C))
         wdev = upload(dev, wh)
     mbr_dev = torch.empty(C, dtype=torch.float64, device=dev)
-    parts = chunks(per, GRAM_BLOCK_BYTES)
-    rows_max = max(int(start[b1] - start[b0]) * ld for b0, b1, ld in parts)
-    block = torch.empty(max(1, rows_max), dtype=torch.float32, device=dev)
     G = [None] * B
-    for b0, b1, ld in parts:
-        r0, n = int(start[b0]), int(start[b1] - start[b0])
-        if n == 0:
-            continue
-        # gram row i lives at gram + i * ld with i the row's index in the WHOLE table: the chunk's block starts at row r0
-        _launch(lib, b1 - b0, P(cand_img_dev) + 4 * b0, int(per[b0:b1].max()), v, P(wdev), P(block) - 4 * r0 * ld, ld, P(mbr_dev))
+    for b0, b1, ld, r0, n, block, _ in _blocks(lib, dev, v, cand_img_dev, per, start, wdev, mbr_dev):
         blk = block[:n * ld].cpu().numpy().reshape(n, ld)
         for b in range(b0, b1):
             G[b] = blk[start[b] - r0:start[b + 1] - r0, :per[b]].copy()
@@ -107,6 +124,60 @@ def gram_of_table(lib, dev, v, cand_img_dev, per, weights=None):
             G[b] = np.zeros((0, 0), np.float32)
     m = mbr_dev.cpu().numpy()
     return G, [m[start[b]:start[b + 1]].copy() for b in range(B)]
+
+
+def dpp_quality(keys, weight):
+    """The qualities of one image's captions for the DPP selection from their ranking keys (higher = better): r_i = (key_i - min) /
+    (max - min) over the image's finite keys -- 0 when they are all equal, 0 for a non-finite key -- and q_i = exp(weight * r_i), float64
+    [m].  The best-ranked caption weighs e^weight times the worst; weight 0 gives all ones (selection on diversity alone)."""
+    k = np.asarray(keys, np.float64).reshape(-1)
+    r = np.zeros(k.size, np.float64)
+    fin = np.isfinite(k)
+    if fin.any():
+        lo, hi = float(k[fin].min()), float(k[fin].max())
+        if hi > lo:
+            r[fin] = (k[fin] - lo) / (hi - lo)
+    return np.exp(float(weight) * r)
+
+
+def list_keys(entries):
+    """The default keys of one image's ranked entries: the value the list is ordered by -- entry[1], or the fourth field of an entry
+    that a `rerank` extended -- as a running minimum down the list.  For a list ordered by that value alone this IS the value; the
+    ranked lists put <EOS>-ended captions before captions cut at max_len whatever their scores, and there a caption gets no better
+    key than the captions ranked above it, so the list's first caption always has the largest quality.  (A NaN key is passed over.)"""
+    k = np.array([e[3] if len(e) > 3 else e[1] for e in entries], np.float64)
+    return np.fmin.accumulate(k) if k.size else k
+
+
+def select_of_table(lib, dev, v, cand_img_dev, per, q, n):
+    """vc_dpp_select_f64 over every image of an ngram_vectors table (arguments as gram_of_table's; q: host float64 [C], one finite
+    positive quality per table row; n: 1..DPP_MAX_SELECT), on each chunk's device block right behind the vc_cider_gram call that wrote
+    it: the matrices never reach the host.  -> (sel int32 [B, n]: indices within the image, -1 past min(n, n_b); gain float64 [B, n];
+    n_dpp int32 [B]).  An image's results do not depend on its chunk."""
+    per, start = _starts(per)
+    B, C, n = int(per.size), int(start[-1]), int(n)
+    if not 1 <= n <= DPP_MAX_SELECT:
+        raise ValueError("n must be 1..%d (got %d)" % (DPP_MAX_SELECT, n))
+    qh = np.ascontiguousarray(q, np.float64).reshape(-1)
+    if qh.size != C:
+        raise ValueError("%d qualities for %d captions" % (qh.size, C))
+    if not (np.isfinite(qh) & (qh > 0)).all():
+        raise ValueError("the qualities must be finite and > 0")
+    sel, gain, n_dpp = np.full((B, n), -1, np.int32), np.zeros((B, n), np.float64), np.zeros(B, np.int32)
+    if C == 0:
+        return sel, gain, n_dpp
+    qdev = upload(dev, qh)
+    sel_d, gain_d, nd_d = (torch.empty(B * n, dtype=torch.int32, device=dev), torch.empty(B * n, dtype=torch.float64, device=dev),
+                           torch.empty(B, dtype=torch.int32, device=dev))
+    done = np.zeros(B, bool)
+    for b0, b1, ld, r0, rows, block, base in _blocks(lib, dev, v, cand_img_dev, per, start, None, None):
+        lib.vc_dpp_select_f64(_stream(), b1 - b0, P(cand_img_dev) + 4 * b0, int(per[b0:b1].max()), base, ld, P(qdev), n, P(sel_d) + 4 * b0 * n,
+                              P(gain_d) + 8 * b0 * n, P(nd_d) + 4 * b0)
+        done[b0:b1] = True
+    if done.any():   # (images of a chunk without captions keep -1 / 0 / 0: the kernel's own answer for n_b = 0)
+        sel[done], gain[done], n_dpp[done] = (sel_d.cpu().numpy().reshape(B, n)[done], gain_d.cpu().numpy().reshape(B, n)[done],
+                                              nd_d.cpu().numpy()[done])
+    return sel, gain, n_dpp
 
 
 class CiderGram(object):
@@ -128,10 +199,9 @@ class CiderGram(object):
         self.df_keys = upload(self.dev, df_keys.view(np.int64) if self.n_df else np.zeros(1, np.int64))
         self.idf = upload(self.dev, idf if self.n_df else np.zeros(1, np.float32))
 
-    def gram(self, candidates_per_image, weights=None):
-        """candidates_per_image: per image a list of token lists (<= 256); weights: per image a list of one number per caption (None:
-        uniform).  -> (G, mbr): per image a float32 [n_b, n_b] array, G[i][j] = CIDEr-D(caption i, reference caption j), and a float64
-        [n_b] array, mbr[i] = sum_j w_j G[i][j] / sum_j w_j (0.0 when the weights sum to 0).  An empty list gives (0, 0) / (0,) arrays."""
+    def _rows(self, candidates_per_image):
+        """host side of the caption table: -> (per: captions per image, cand_img [B + 1], flat: the captions in table order, W, L: their
+        word rows), limits checked"""
         B = len(candidates_per_image)
         per = np.fromiter((len(c) for c in candidates_per_image), np.int64, B)
         if B and per.max() > DIVERSE_MAX_DRAWS:
@@ -141,14 +211,25 @@ class CiderGram(object):
         image_of = np.repeat(np.arange(B), per)
         flat = [c for cs in candidates_per_image for c in cs]
         W, L = word_rows(flat, self.bos, self.eos, owner=lambda i: "candidate %d of image %d" % (i - cand_img[image_of[i]], image_of[i]))
+        return per, cand_img, flat, W, L
+
+    def _vectors(self, cand_img, W, L):
+        """the idf-weighted ngram_vectors table of the word rows; v.head = the device cand_img"""
+        return ngram_vectors(self.lib, self.dev, W, L, self.bos, self.eos, self.df_keys, self.idf, self.n_df, self.idf_unseen, head=cand_img)
+
+    def gram(self, candidates_per_image, weights=None):
+        """candidates_per_image: per image a list of token lists (<= 256); weights: per image a list of one number per caption (None:
+        uniform).  -> (G, mbr): per image a float32 [n_b, n_b] array, G[i][j] = CIDEr-D(caption i, reference caption j), and a float64
+        [n_b] array, mbr[i] = sum_j w_j G[i][j] / sum_j w_j (0.0 when the weights sum to 0).  An empty list gives (0, 0) / (0,) arrays."""
+        per, cand_img, flat, W, L = self._rows(candidates_per_image)
         wh = None
         if weights is not None:
-            if len(weights) != B or any(len(w) != n for w, n in zip(weights, per)):
+            if len(weights) != len(per) or any(len(w) != n for w, n in zip(weights, per)):
                 raise ValueError("weights must hold one number per caption of every image")
             wh = np.fromiter((float(x) for w in weights for x in w), np.float64, len(flat))
         if not flat:
             return gram_of_table(self.lib, self.dev, None, None, per)
-        v = ngram_vectors(self.lib, self.dev, W, L, self.bos, self.eos, self.df_keys, self.idf, self.n_df, self.idf_unseen, head=cand_img)
+        v = self._vectors(cand_img, W, L)
         return gram_of_table(self.lib, self.dev, v, v.head, per, wh)
 
     def rerank(self, diverse_result, weights=None, n_best=None):
@@ -159,3 +240,31 @@ class CiderGram(object):
             weights = [[float(e[2]) for e in entries] for entries in diverse_result]
         _, mbr = self.gram([[e[0] for e in entries] for entries in diverse_result], weights)
         return [rerank_entries(entries, m, n_best) for entries, m in zip(diverse_result, mbr)]
+
+    def select(self, diverse_result, n, quality=1.0, keys=None, weights=None):
+        """DPP selection (DESIGN.md "DPP selection"): n of every image's captions chosen jointly for quality and for difference from each
+        other by vc_dpp_select_f64 over the image's in-set CIDEr-D matrix, which stays on the device.
+        diverse_result: per image its ranked entries (tokens, score, ...), at most 256.  An entry's key is the value its list is ordered
+        by (`list_keys`: entry[1], or the fourth field of an entry that a `rerank` extended) unless `keys` gives one number per caption
+        of every image; its quality is dpp_quality(the image's keys, quality).  `weights` (per image one finite positive number per caption) gives
+        the qualities themselves, in place of keys and quality.
+        -> (selected: per image the chosen entries in selection order, each extended by its gain -- at most n, fewer for a shorter
+        list; n_dpp: per image how many of them the greedy steps chose, the rest being the fill in list order with gain 0)."""
+        B = len(diverse_result)
+        if keys is not None and weights is not None:
+            raise ValueError("give keys or weights, not both")
+        given = weights if weights is not None else keys
+        if given is not None and (len(given) != B or any(len(g) != len(e) for g, e in zip(given, diverse_result))):
+            raise ValueError("%s must hold one number per caption of every image" % ("weights" if weights is not None else "keys"))
+        if weights is not None:
+            qs = [np.asarray(w, np.float64).reshape(-1) for w in weights]
+        else:
+            if keys is None:
+                keys = [list_keys(entries) for entries in diverse_result]
+            qs = [dpp_quality(k, quality) for k in keys]
+        per, cand_img, flat, W, L = self._rows([[e[0] for e in entries] for entries in diverse_result])
+        q = np.concatenate(qs) if qs else np.zeros(0, np.float64)
+        v = self._vectors(cand_img, W, L) if flat else None
+        sel, gain, n_dpp = select_of_table(self.lib, self.dev, v, v.head if flat else None, per, q, n)
+        out = [[tuple(entries[j]) + (float(g),) for j, g in zip(row.tolist(), gr.tolist()) if j >= 0] for entries, row, gr in zip(diverse_result, sel, gain)]
+        return out, [int(x) for x in n_dpp]

@@ -43,7 +43,11 @@ evaluator also makes its in-set CIDEr-D pass (mbr.py, vc_cider_gram) and the fil
 `mbr_cider_d`.
 `params.no_repeat_ngram` / `min_len` / `repetition_penalty` / `banned_words` (additive): the decoding controls
 (`controls.DecodeControls`, attached to the decoder as `decoder.controls`) go to whichever mode decodes, the test set's
-`online_inference` included; the caption records gain nothing, `./val_{gen_name}_metrics.json` lists the four flags."""
+`online_inference` included; the caption records gain nothing, `./val_{gen_name}_metrics.json` lists the four flags.
+`params.diverse_select == "dpp"` (additive; the three list modes): `params.select_n` captions per image are chosen from the ranked
+list by the DPP selection (`mbr.CiderGram.select`, attached as `decoder.mbr`); the records of `./val_{gen_name}_diverse.json` hold them
+in selection order with `"dpp_gain"` and `"dpp_chosen"`, `./val_{gen_name}.json` keeps the ranked list's first caption, `--eval_captions`
+evaluates the selected lists, and `./val_{gen_name}_metrics.json` gains `diverse_select`, `select_n` and `dpp_quality`."""
 import json
 import math
 import os
@@ -150,6 +154,9 @@ EVAL_FLAGS = ("beam_size", "temperature", "diverse_draws", "diverse_method", "di
               "no_repeat_ngram", "min_len", "repetition_penalty", "banned_words", "contrastive_k", "contrastive_alpha")
 
 
+SELECT_FLAGS = ("diverse_select", "select_n", "dpp_quality")   # recorded only when a selection ran: without one the file is unchanged
+
+
 def store_metrics(params, metrics, images, captions):
     """./val_{gen_name}_metrics.json: the evaluator's dict without its per-image arrays, the number of images and of captions evaluated,
     sample_gen and the decoding flags in force; one printed line per metric.  With params.eval_self_cider also the two SET_METRICS
@@ -163,7 +170,9 @@ def store_metrics(params, metrics, images, captions):
         out["eval_self_cider"] = True
     if getattr(params, "use_ema", False):   # --use_ema: the captions come from the averaged weights
         out["use_ema"] = True
-    path = "./val_{}_metrics.json".format(params.gen_name)
+    if getattr(params, "diverse_select", "none") != "none":   # --diverse_select dpp: the lists evaluated are the selected ones
+        out.update({k: getattr(params, k) for k in SELECT_FLAGS})
+    path ="./val_{}_metrics.json".format(params.gen_name)
     if os.path.exists(path):
         os.remove(path)
     with open(path, "w") as fh:

@@ -29,6 +29,7 @@ _DEFAULTS = dict(
     score_draws=0, beam_groups=5, beam_diversity=0.5, top_k=0, top_p=1.0, typical_p=1.0, min_p=0.0, eta=0.0, eval_captions=False, eval_self_cider=False,
     bound_draws=0, bound_mi=0, marginal_draws=20, constraints=None, cbs_width=0,
     no_repeat_ngram=0, min_len=0, repetition_penalty=1.0, banned_words=None, contrastive_k=5, contrastive_alpha=0.6,
+    diverse_select="none", select_n=5, dpp_quality=1.0,
     # training objective options (every one off by default: the reference's objective)
     kl_free_bits=0.0, kl_weight=1.0, kl_cycle_steps=0, kl_cycle_ramp=0.5, kl_cycles=0, label_smoothing=0.0, word_drop=0.0,
     # self-critical training (off by default)
@@ -72,6 +73,8 @@ _FLAGS = [
     ("--no_repeat_ngram", "no_repeat_ngram", int, None), ("--min_len", "min_len", int, None),
     ("--repetition_penalty", "repetition_penalty", float, None), ("--banned_words", "banned_words", str, None),
     ("--contrastive_k", "contrastive_k", int, None), ("--contrastive_alpha", "contrastive_alpha", float, None),
+    ("--diverse_select", "diverse_select", str, ["none", "dpp"]), ("--select_n", "select_n", int, None),
+    ("--dpp_quality", "dpp_quality", float, None),
     ("--kl_free_bits", "kl_free_bits", float, None), ("--kl_weight", "kl_weight", float, None),
     ("--kl_cycle_steps", "kl_cycle_steps", int, None), ("--kl_cycle_ramp", "kl_cycle_ramp", float, None),
     ("--kl_cycles", "kl_cycles", int, None), ("--label_smoothing", "label_smoothing", float, None),
@@ -148,6 +151,14 @@ _HELP = {"--synthetic": "train on seeded synthetic batches (no MSCOCO needed)", 
          "--contrastive_alpha": "--sample_gen contrastive: weight of the degeneration penalty, the largest cosine similarity between a "
                                 "candidate's decoder state and the states of the caption so far, against the word's probability "
                                 "(in [0, 1]; default 0.6; 0 = greedy)",
+         "--diverse_select": "--sample_gen diverse / diverse_beam / stochastic_beam: which of an image's ranked captions are kept -- none: "
+                             "the list as ranked; dpp: --select_n of them chosen jointly for quality and for difference from each "
+                             "other (greedy MAP of a determinantal point process over the image's in-set CIDEr-D matrix, after "
+                             "--diverse_rerank; needs only the training captions for its idf; default none)",
+         "--select_n": "--diverse_select dpp: captions kept per image (1..32; default 5)",
+         "--dpp_quality": "--diverse_select dpp: weight W of a caption's rank in its quality exp(W * rank score scaled to [0, 1] over "
+                          "the image): the best-ranked caption weighs e^W times the worst (in [0, 8]; 0 = diversity alone; default "
+                          "1.0, a choice that no captioning run has tuned)",
          "--kl_free_bits": "training objective: KL floor in nats per latent dimension and caption row (free bits: a dimension whose KL "
                            "is at or below it is held at the floor and gets no KL gradient; >= 0; default 0 = off)",
          "--kl_weight": "training objective: weight beta of the KL term in the lower bound and its gradient (> 0; default 1.0)",
@@ -282,6 +293,16 @@ class Parameters(object):
                          "against a similarity (got %r)" % self.temperature)
         elif args["contrastive_k"] is not None or args["contrastive_alpha"] is not None:
             ap.error("--contrastive_k / --contrastive_alpha belong to --sample_gen contrastive (got --sample_gen %s)" % self.sample_gen)
+        if self.diverse_select == "dpp":
+            if self.sample_gen not in ("diverse", "diverse_beam", "stochastic_beam"):
+                ap.error("--diverse_select dpp selects from a list of captions per image: --sample_gen diverse, diverse_beam or "
+                         "stochastic_beam (got --sample_gen %s)" % self.sample_gen)
+            if not 1 <= self.select_n <= 32:
+                ap.error("--select_n must be 1..32 (got %d)" % self.select_n)
+            if not (0.0 <= self.dpp_quality <= 8.0):
+                ap.error("--dpp_quality must be in [0, 8] (0 = diversity alone; got %r)" % self.dpp_quality)
+        elif args["select_n"] is not None or args["dpp_quality"] is not None:
+            ap.error("--select_n / --dpp_quality belong to --diverse_select dpp")
         if not 0 <= self.no_repeat_ngram <= 8:
             ap.error("--no_repeat_ngram must be 0..8 (0 = off; got %d)" % self.no_repeat_ngram)
         if not 0 <= self.min_len < self.gen_max_len:

@@ -31,9 +31,12 @@ class Decoder(object):
         self.c_i_ph = None
         self.cap_clusters = None
         self.consensus_index = None  # consensus.ConsensusIndex: --diverse_rerank consensus re-ranks diverse captions against it
-        self.mbr = None              # mbr.CiderGram: --diverse_rerank mbr re-ranks diverse captions by their expected CIDEr-D against the set
+        self.mbr = None              # mbr.CiderGram: --diverse_rerank mbr re-ranks diverse captions by their expected CIDEr-D against the set;
+                                     # --diverse_select dpp selects from them by the same in-set CIDEr-D matrix
         self.last_token_ids = None   # per image of the last generation call its ranked token-id lists (what --eval_captions evaluates);
                                      # every generation method clears it first, so a call that fails leaves None, never older ids
+        self.last_ranked_records = None   # --diverse_select dpp: the records of the last call's whole ranked lists, as a run without the
+                                     # flag returns them (what ./val_{gen_name}.json is written from, so that the flag never changes that file)
         self.bound_stats = None      # bound_captions: skipped images and the running sums behind the active-units count
         self.constraints = None      # constraints.Constraints: what --sample_gen constrained_beam makes the captions mention
         self.controls = None         # controls.DecodeControls: what the captions may NOT say (--no_repeat_ngram, --min_len, --repetition_penalty,
@@ -87,13 +90,21 @@ class Decoder(object):
         """token ids as a caption's text, without the ids in `skip` (<BOS>, <EOS>)"""
         return " ".join(self.data_dict.idx2word[t] for t in tokens if t not in skip)
 
-    def _ranked_record(self, pid, entries, skip, counts, extra=(), rerank="likelihood"):
-        """diverse_inference's record of an image's ranked entries (tokens, score, .., [the re-ranking's own value]), `extra` items after it"""
+    def _ranked_record(self, pid, entries, skip, counts, extra=(), rerank="likelihood", picked=None):
+        """diverse_inference's record of an image's ranked entries (tokens, score, .., [the re-ranking's own value]), `extra` items after it.
+        picked = (the ranked list's first tokens or None, n_dpp) under --diverse_select dpp: `entries` are then the selected ones in
+        selection order, each ending in its gain; "caption" stays the ranked list's first and the record gains "dpp_gain" (aligned
+        with "captions") and "dpp_chosen"."""
         texts = [self._text(e[0], skip) for e in entries]
         rec = {"image_id": pid, "caption": texts[0] if texts else "", "captions": texts, "scores": [float(e[1]) for e in entries], "counts": counts}
         rec.update(extra)
         if rerank in ("consensus", "marginal", "mbr"):
             rec[rerank] = [float(e[3]) for e in entries]
+        if picked is not None:
+            first, chosen = picked
+            rec["caption"] = self._text(first, skip) if first is not None else ""
+            rec["dpp_gain"] = [float(e[-1]) for e in entries]
+            rec["dpp_chosen"] = int(chosen)
         return rec
 
     def _rerank(self):
@@ -107,6 +118,21 @@ class Decoder(object):
             raise RuntimeError("diverse_rerank = 'mbr' needs the idf of the training captions: attach one with decoder.mbr = "
                                "vae_captioning_amd.mbr.CiderGram(engine, train_captions_per_image, bos, eos)")
         return mode
+
+    def _select(self):
+        """params.diverse_select: None ("none"), or (select_n, dpp_quality) for "dpp" (RuntimeError without an attached mbr.CiderGram)"""
+        if getattr(self.params, "diverse_select", "none") != "dpp":
+            return None
+        if self.mbr is None:
+            raise RuntimeError("diverse_select = 'dpp' needs the idf of the training captions: attach one with decoder.mbr = "
+                               "vae_captioning_amd.mbr.CiderGram(engine, train_captions_per_image, bos, eos)")
+        return int(getattr(self.params, "select_n", 5)), float(getattr(self.params, "dpp_quality", 1.0))
+
+    def _dpp(self, ranked, select):
+        """--diverse_select dpp on every image's ranked entries -> (the selected entries in selection order, each ending in its gain;
+        per image `picked` for _ranked_record: the ranked list's first tokens and how many entries the greedy steps chose)"""
+        chosen, n_dpp = self.mbr.select(ranked, select[0], quality=select[1])
+        return chosen, [(entries[0][0] if entries else None, k) for entries, k in zip(ranked, n_dpp)]
 
     def decode(self, mode, picture_ids, in_pictures, c_v=None, sess=None, placeholder=None, **overrides):
         """The cap_list of a batch in decode mode `mode` (params.sample_gen, gen_caption's gen_method) from the mode's method (DECODE_METHODS),
@@ -163,12 +189,20 @@ class Decoder(object):
         over ALL draws of the image (generate.py: diverse(rerank="marginal")); "scores" are those scores and the records gain "marginal"
         (aligned with "captions").  params.diverse_rerank == "mbr": every distinct caption is re-ranked by its expected CIDEr-D against
         the image's own captions, each weighted by its count (the attached `mbr`: mbr.CiderGram), before n_best cuts the list; the
-        records gain "mbr" (aligned with "captions") and "caption" is the minimum-Bayes-risk choice."""
+        records gain "mbr" (aligned with "captions") and "caption" is the minimum-Bayes-risk choice.
+        params.diverse_select == "dpp": after the re-ranking and in place of the n_best cut, params.select_n captions are chosen from the
+        whole ranked list jointly for quality and difference (the attached `mbr`: CiderGram.select, quality weight params.dpp_quality);
+        "captions" and the fields aligned with it hold them in selection order, the records gain "dpp_gain" (aligned) and "dpp_chosen",
+        and "caption" stays the ranked list's first."""
         self.last_token_ids = None
         bos, eos, use_cv = self._call(c_v)
         draws = int(draws if draws is not None else self.params.diverse_draws)
         method = method if method is not None else self.params.diverse_method
         rerank = self._rerank()
+        select = self._select()
+        self.last_ranked_records = None
+        if select is not None:
+            n_best = None
         consensus, marginal, mbr = rerank == "consensus", rerank == "marginal", rerank == "mbr"
         feats = self._features(in_pictures)
         res = self._gen().diverse(feats, use_cv, None, bos, eos, draws=draws, method=method, n_best=None if consensus or mbr else n_best,
@@ -178,7 +212,15 @@ class Decoder(object):
             res = self.consensus_index.rerank(feats, res, n_best=n_best)
         if mbr:
             res = self.mbr.rerank(res, n_best=n_best)     # weights: the counts
-        cap_list = [self._ranked_record(pid, entries, (bos, eos), [int(e[2]) for e in entries], rerank=rerank) for pid, entries in zip(picture_ids, res)]
+
+        def records(lists, picked):
+            return [self._ranked_record(pid, entries, (bos, eos), [int(e[2]) for e in entries], rerank=rerank, picked=pk)
+                    for pid, entries, pk in zip(picture_ids, lists, picked)]
+        picked = [None] * len(res)
+        if select is not None:
+            self.last_ranked_records = records(res, picked)
+            res, picked = self._dpp(res, select)
+        cap_list = records(res, picked)
         self.last_token_ids = [[list(e[0]) for e in entries] for entries in res]
         return cap_list
 
@@ -188,9 +230,12 @@ class Decoder(object):
         beam_size / groups beams per image (params.beam_size in all), a word costing a candidate `diversity` (params.beam_diversity)
         per live beam of the round's earlier groups that has just taken it.  Equal captions of different groups are merged under
         their best score and ranked.  Returns cap_list in diverse_inference's record shape: per image {"image_id", "caption": the
-        best text, "captions": [texts], "scores": [...], "counts": [groups that produced the caption], "groups": [[group ids]]}."""
+        best text, "captions": [texts], "scores": [...], "counts": [groups that produced the caption], "groups": [[group ids]]}.
+        params.diverse_select == "dpp" selects from the merged list as diverse_inference does."""
         self.last_token_ids = None
         bos, eos, use_cv = self._call(c_v)
+        select = self._select()
+        self.last_ranked_records = None
         total = int(beam_size if beam_size is not None else self.params.beam_size)
         G = int(groups if groups is not None else self.params.beam_groups)
         lam = float(diversity if diversity is not None else self.params.beam_diversity)
@@ -200,8 +245,15 @@ class Decoder(object):
                                               diversity=lam, max_len=self.params.gen_max_len, len_norm_f=len_norm_f,
                                               controls=self.controls)
         merged = [merge_groups(per_group) for per_group in res]
-        cap_list = [self._ranked_record(pid, entries, (bos, eos), [len(e[2]) for e in entries], {"groups": [[int(g) for g in e[2]] for e in entries]})
-                    for pid, entries in zip(picture_ids, merged)]
+
+        def records(lists, picked):
+            return [self._ranked_record(pid, entries, (bos, eos), [len(e[2]) for e in entries], {"groups": [[int(g) for g in e[2]] for e in entries]}, picked=pk)
+                    for pid, entries, pk in zip(picture_ids, lists, picked)]
+        picked = [None] * len(merged)
+        if select is not None:
+            self.last_ranked_records = records(merged, picked)
+            merged, picked = self._dpp(merged, select)
+        cap_list = records(merged, picked)
         self.last_token_ids = [[list(e[0]) for e in entries] for entries in merged]
         return cap_list
 
@@ -213,11 +265,15 @@ class Decoder(object):
         distinct), "logprob", "perturbed", "weight", "norm_weight" (aligned with "captions"), "kappa"}.  params.diverse_rerank ==
         "consensus" re-ranks by the attached consensus index and adds "consensus"; "marginal" adds "marginal" (one latent draw per
         image: the caption's logprob, so the order is the likelihood order); "mbr" re-ranks by the expected CIDEr-D against the image's
-        captions, each weighted by its norm_weight (the weights that estimate an expectation under the model), and adds "mbr"."""
+        captions, each weighted by its norm_weight (the weights that estimate an expectation under the model), and adds "mbr".
+        params.diverse_select == "dpp" selects from the ranked list as diverse_inference does; the aligned per-caption fields follow
+        the selection."""
         self.last_token_ids = None
         bos, eos, use_cv = self._call(c_v)
         n = int(beam_size if beam_size is not None else self.params.beam_size)
         rerank = self._rerank()
+        select = self._select()
+        self.last_ranked_records = None
         consensus, marginal = rerank == "consensus", rerank == "marginal"
         feats = self._features(in_pictures)
         res = self._gen().stochastic_beam_search(feats, use_cv, None, bos, eos, beam_size=n, max_len=self.params.gen_max_len,
@@ -233,12 +289,20 @@ class Decoder(object):
             ranked = self.mbr.rerank(ranked, weights=[[float(by[tuple(e[0])][5]) for e in entries] for entries, by in zip(ranked, by_words)])
         if marginal:
             ranked = [rerank_by_marginal(entries, [by[tuple(e[0])][1] for e in entries], eos, len_norm_f) for entries, by in zip(ranked, by_words)]
-        cap_list = []
-        for pid, entries, r, by in zip(picture_ids, ranked, res, by_words):
-            own = [by[tuple(e[0])] for e in entries]
-            extra = {"logprob": [float(c[1]) for c in own], "perturbed": [float(c[2]) for c in own], "weight": [float(c[4]) for c in own],
-                     "norm_weight": [float(c[5]) for c in own], "kappa": float(r["kappa"])}
-            cap_list.append(self._ranked_record(pid, entries, (bos, eos), [1] * len(entries), extra, rerank))
+
+        def records(lists, picked):
+            out = []
+            for pid, entries, r, by, pk in zip(picture_ids, lists, res, by_words, picked):
+                own = [by[tuple(e[0])] for e in entries]
+                extra = {"logprob": [float(c[1]) for c in own], "perturbed": [float(c[2]) for c in own], "weight": [float(c[4]) for c in own],
+                         "norm_weight": [float(c[5]) for c in own], "kappa": float(r["kappa"])}
+                out.append(self._ranked_record(pid, entries, (bos, eos), [1] * len(entries), extra, rerank, picked=pk))
+            return out
+        picked = [None] * len(ranked)
+        if select is not None:
+            self.last_ranked_records = records(ranked, picked)
+            ranked, picked = self._dpp(ranked, select)
+        cap_list = records(ranked, picked)
         self.last_token_ids = [[list(e[0]) for e in entries] for entries in ranked]
         return cap_list
 
